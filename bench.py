@@ -1,7 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- RichSem training hot path (multi-scale deformable attention) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it sets up the inputs, warms up, times K steps of the headline
+distribution and prints one JSON line (`metric`, `value`, `unit`, `ms_per_step`, ...).  Its timed loop carries no
+profiling events.  Everything else on the line -- the other distributions, the roofline and per-kernel table, the
+collective-free step, graph replay, host issue time, the second encoder shape, bf16, the MFMA rows, the composed
+training step and the CPU baselines -- is measured only with `--full` (the `--no-*` options trim that run).
+
+`--dump-outputs DIR` writes, after the timed loop, what the last timed step returned to its caller (rank 0): for
+every layer l of the step, `DIR/<call><l>_out.npy` (forward) and `_grad_value`, `_grad_loc`, `_grad_attn` (backward),
+float32, flattened.  An array of more than DUMP_SAMPLE elements is cut to a fixed sample of DUMP_SAMPLE of them (the
+flat indices drawn by torch.Generator().manual_seed(DUMP_SEED), the same for every run), so the whole dump is
+48 MiB (50 MB).  The inputs are seeded, so two builds run with the same arguments can be compared file by file (the backward
+accumulates grad_value with atomics: expect differences in the last bits).  The timed steps of such a run keep their
+outputs alive until the next step begins, which the steps of a run without the option do not.
 
 `--gpus N` with N > 1 launches its own N ranks (one process per GPU, `python -m torch.distributed.run`, started
 before this process touches the GPU); under an external launcher (WORLD_SIZE set) it is one of the ranks.
@@ -17,18 +31,18 @@ inputs instead of re-reading one cache-resident set.  Inputs are resident in HBM
 value = images/s of THIS PATH (images per step / step time), aggregated over all GPUs; the backbone, the GEMMs and
 the criterion of a full training step are not part of the path and not in the number.
 
-Three sampling-location distributions are timed in the same run (SURVEY.md section 8d asks for the local and the
-uniform one; sigma4 sits between): "init" = reference points + the module's initial offsets + N(0, 1 px) -- the
+With --full, three sampling-location distributions are timed in the same run (SURVEY.md section 8d asks for the
+local and the uniform one; sigma4 sits between): "init" = reference points + the module's initial offsets + N(0, 1 px) -- the
 top-level `value`; "sigma4" = the same with N(0, 4 px); "uniform" = U[0,1)^2.  `value_sigma4`, `value_uniform` and
 `distributions` carry the other two with their own rooflines.
 
 Multi-GPU: the path shards by image (data parallel): every rank owns its own 2 images.  The one
 collective of the reference's training step (DDP gradient all-reduce, reference main.py:204-206: ~47.6 M trainable
 parameters = 190 MB fp32 in 25 MB buckets) is issued on RCCL, bucket by bucket between the backward calls, so that it
-overlaps with them as DDP's does; `ms_per_step_no_collective` is the same step without it.  Weak scaling.
+overlaps with them as DDP's does; `ms_per_step_no_collective` (--full) is the same step without it.  Weak scaling.
 Timing = barrier + synchronize on both sides, max over ranks.
 
-Also on the JSON line:
+Also on the JSON line of a --full run:
   roofline      dominant kernel of the step: achieved = algorithmic bytes per launch / average
                 launch duration, measured live by HIP events recorded by the library around that call's kernels on the
                 stream they are launched on, inside the timed region; peak = HBM3E 8 TB/s.
@@ -66,6 +80,8 @@ HIP_KERNELS = {
 }
 VARIANT_NAMES = {1: "direct", 2: "tiled", 3: "split", 4: "routed", 5: "band", 6: "tiled_prep"}
 PROFILE_DOMINANT = (1 + 1) * 16 + 4   # library option "profile_filter": backward calls of variant 4 (the routed kernels)
+DUMP_SAMPLE = 1 << 18   # --dump-outputs: elements kept per array (48 arrays x 1 MiB fp32)
+DUMP_SEED = 0
 
 
 def parse_args(argv=None):
@@ -73,8 +89,14 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (other distributions, rooflines, bf16, Em, MFMA rows, "
+                         "composed step, CPU baselines); off: only the headline step is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned (rank 0) to DIR/<name>.npy, float32, sampled (see the docstring)")
     ap.add_argument("--loc", default="init,sigma4,uniform",
-                    help="comma-separated sampling-location distributions to time (the first is the headline)")
+                    help="comma-separated sampling-location distributions to time (the first is the headline; the others "
+                         "only with --full)")
     ap.add_argument("--images-per-gpu", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-collective", action="store_true", help="N > 1: leave the gradient all-reduce out")
@@ -128,6 +150,33 @@ def bucket_schedule(n_buckets, n_backward_calls):
     """After which backward call (1-based) each bucket is launched: spread evenly over the backward pass, the last
     bucket after the last call (like DDP, whose last bucket is the one nothing is left to hide)."""
     return [-(-(i + 1) * n_backward_calls // n_buckets) for i in range(n_buckets)]
+
+
+def step_output_names(calls):
+    """--dump-outputs: the file stems of one step's outputs in the order the step returns them -- every layer's forward
+    output, then every layer's three gradients, the layers in reverse (the backward runs from the last layer down)."""
+    layer_names = [f"{c.name}{layer}" for c, reps in calls for layer in range(reps)]
+    return [n + "_out" for n in layer_names] + \
+        [n + sfx for n in reversed(layer_names) for sfx in ("_grad_value", "_grad_loc", "_grad_attn")]
+
+
+def dump_outputs(named, out_dir, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """Write each (name, tensor) as out_dir/<name>.npy, float32, flattened.  A tensor of more than `sample` elements is cut to
+    the elements at `sample` flat indices drawn by a CPU generator seeded with `seed` (the same indices for every run and every
+    tensor of that size); the gather runs where the tensor is.  Returns the bytes written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in named:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > sample:
+            idx = torch.randint(flat.numel(), (sample,), generator=torch.Generator().manual_seed(seed))
+            flat = flat[idx.to(flat.device)]
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    return total
 
 
 def free_port():
@@ -282,6 +331,26 @@ def grid_sample_baseline(calls, n_images, cores):
         return {"error": f"{type(e).__name__}: {str(e)[:200]}"}
     finally:
         torch.set_num_threads(old)
+
+
+def headline_line(args, world, n_img, loc, collective, elapsed, settle_steps):
+    """The result line of a plain run (a --full run adds to it): `elapsed` = seconds of the args.steps timed steps."""
+    par = f"dp{world}" + (" (gradient all-reduce 190 MB fp32 in 25 MB buckets on RCCL, overlapped with backward)"
+                          if collective else " (replicas, no collective)")
+    return {
+        "metric": "training images/sec, RichSem R50 4-scale 1333x800 (MSDeformAttn hot path: 12 fwd + 12 bwd "
+                  "calls per step)",
+        "value": round(total_images(n_img, world) / (elapsed / args.steps), 3), "unit": "img/s",
+        "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 3), "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"configs[1]: R50 4-scale 800x1344 (S=22323), bs={n_img}/GPU, M=8 D=32 L=P=4; "
+                               f"per step 6x E(Lq=22323) + 6x Dd(Lq=1092), forward and backward, 12 distinct "
+                               f"per-layer tensor sets; loc-{loc}",
+                   "loc": loc, "images_per_gpu": n_img, "parallelism": par},
+        "settle": {"untimed_steps_before_warmup": settle_steps,
+                   "why": "one untimed rehearsal of the first measurement loop: the first timed loop of a process on a freshly leased box "
+                          "ran 0.4-0.5 ms per step slower than later ones with the same kernel times (BENCH_r03 / r04)"},
+    }
 
 
 # ---- the measured loop -----------------------------------------------------------------------------------------------
@@ -494,6 +563,8 @@ def main(argv=None):
     for m in modes:
         if m not in W.LOC_MODES:
             raise SystemExit(f"unknown --loc {m}; choose from {W.LOC_MODES}")
+    if not args.full:
+        modes = modes[:1]   # a plain run times the headline distribution only
     n_img = args.images_per_gpu
     calls = W.training_step_calls(n_img)
     # inputs resident in HBM before the timed region: one tensor set PER LAYER, every rank its own images (seed by rank)
@@ -513,14 +584,19 @@ def main(argv=None):
         buckets = grad_buckets(W.GRAD_ALLREDUCE_ELEMS, W.DDP_BUCKET_BYTES)
         fire_after = bucket_schedule(len(buckets), len(layers))
 
-    def step(mode, with_collective, bf16=False, layers_=None):
+    def step(mode, with_collective, bf16=False, layers_=None, keep=None):
+        """one step; `keep` (a list): holds what the calls returned until the next step that is given it begins.  Without it
+        every result is dropped as soon as its call returns."""
         vk, gk = ("value_bf16", "grad_out_bf16") if bf16 else ("value", "grad_out")
         layers_ = layers if layers_ is None else layers_
+        if keep is not None:
+            keep.clear()
+        sink = keep.append if keep is not None else (lambda r: None)
         for c, t, locs in layers_:
-            MSDA.ms_deform_attn_forward(t[vk], t["shapes"], t["lsi"], locs[mode], t["aw"], 64)
+            sink(MSDA.ms_deform_attn_forward(t[vk], t["shapes"], t["lsi"], locs[mode], t["aw"], 64))
         nb = 0
         for k, (c, t, locs) in enumerate(reversed(layers_), 1):
-            MSDA.ms_deform_attn_backward(t[vk], t["shapes"], t["lsi"], locs[mode], t["aw"], t[gk], 64)
+            sink(MSDA.ms_deform_attn_backward(t[vk], t["shapes"], t["lsi"], locs[mode], t["aw"], t[gk], 64))
             while with_collective and nb < len(buckets) and fire_after[nb] <= k:
                 s, e = buckets[nb]
                 works.append(dist.all_reduce(flat_grads[s:e], async_op=True))   # RCCL, its own stream: overlaps
@@ -534,10 +610,10 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(mode, with_collective, profile, bf16=False, layers_=None):
+    def timed(mode, with_collective, profile, bf16=False, layers_=None, keep=None):
         _lib.set_option("locality_monitor", _lib.get_option("locality_monitor"))   # forget the previous distribution
         for _ in range(max(args.warmup, 3)):   # (the locality monitor settles within the first two steps)
-            step(mode, with_collective, bf16, layers_)
+            step(mode, with_collective, bf16, layers_, keep)
         fence()
         n_calls = (calls_per_step if layers_ is None else 2 * len(layers_)) * args.steps
         if profile:
@@ -550,7 +626,7 @@ def main(argv=None):
         fence()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step(mode, with_collective, bf16, layers_)
+            step(mode, with_collective, bf16, layers_, keep)
         fence()
         elapsed = time.perf_counter() - t0
         records = []
@@ -603,7 +679,7 @@ def main(argv=None):
     # path's steady state, so the same loop runs once before it is timed.  W warm-up steps then K timed steps still follow, as asked.
     settle_steps = 0
     if not args.no_settle:
-        timed(modes[0], collective, True)
+        timed(modes[0], collective, args.full)
         settle_steps = max(args.warmup, 3) + args.steps
 
     def host_issue_us(mode):
@@ -619,11 +695,28 @@ def main(argv=None):
 
     results = {}
     for mode in modes:
-        elapsed, records = timed(mode, collective, True)
+        kept = [] if (args.dump_outputs and mode == modes[0]) else None
+        elapsed, records = timed(mode, collective, args.full, keep=kept)
+        if kept is not None:   # the headline's last timed step, as its caller received it
+            if rank == 0:
+                outs = [x for r in kept for x in (r if isinstance(r, list) else [r])]   # (a backward call returns a list of three)
+                named = zip(step_output_names(calls), outs, strict=True)
+                nbytes = dump_outputs(named, args.dump_outputs)
+                print(f"[bench] {nbytes / 1e6:.1f} MB of outputs written to {args.dump_outputs}", file=sys.stderr)
+            kept.clear()
         res = {"elapsed": elapsed, "records": records}
-        if collective:
+        if collective and args.full:
             res["elapsed_nc"], _ = timed(mode, False, False)
         results[mode] = res
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, n_img, modes[0], collective, results[modes[0]]["elapsed"], settle_steps)),
+                  flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     graph_ms = graph_replay(modes[0]) if (world == 1 and not args.no_graph) else None
     host_us = host_issue_us(modes[0])
     # The second encoder shape of BASELINE.json's configs[2] / [3]: every other step there is a 1280 x 1280 ImageNet-LVIS mosaic batch
@@ -690,18 +783,8 @@ def main(argv=None):
 
         summ = {m: summarise(m) for m in modes}
         head = summ[modes[0]]
-        par = f"dp{world}" + (" (gradient all-reduce 190 MB fp32 in 25 MB buckets on RCCL, overlapped with backward)"
-                              if collective else " (replicas, no collective)")
-        line = {
-            "metric": "training images/sec, RichSem R50 4-scale 1333x800 (MSDeformAttn hot path: 12 fwd + 12 bwd "
-                      "calls per step)",
-            "value": head["value"], "unit": "img/s",
-            "n_gpus": world, "steps": args.steps, "warmup": max(args.warmup, 3), "ms_per_step": head["ms_per_step"],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"configs[1]: R50 4-scale 800x1344 (S=22323), bs={n_img}/GPU, M=8 D=32 L=P=4; "
-                                   f"per step 6x E(Lq=22323) + 6x Dd(Lq=1092), forward and backward, 12 distinct "
-                                   f"per-layer tensor sets; loc-{modes[0]}",
-                       "loc": modes[0], "images_per_gpu": n_img, "parallelism": par},
+        line = headline_line(args, world, n_img, modes[0], collective, results[modes[0]]["elapsed"], settle_steps)
+        line.update({
             "roofline": head["roofline"],
             "kernels": head["kernels"],
             "host_us_per_call": round(host_us, 2),
@@ -710,10 +793,7 @@ def main(argv=None):
                          "(`kernels[].measured`) -- bracketing all 24 calls of a step cost the step 0.2 ms of event packets; a bracket includes 1-2 us of its own "
                          "packets, so the brackets' sum (`kernel_ms_per_step`) can come out above the step they were not all part of",
             "kernel_ms_per_step": round(sum(k["total_ms"] for k in head["kernels"]) / args.steps, 4),
-            "settle": {"untimed_steps_before_warmup": settle_steps,
-                       "why": "one untimed rehearsal of the first measurement loop: the first timed loop of a process on a freshly leased box "
-                              "ran 0.4-0.5 ms per step slower than later ones with the same kernel times (BENCH_r03 / r04)"},
-        }
+        })
         if "ms_per_step_no_collective" in head:
             line["ms_per_step_no_collective"] = head["ms_per_step_no_collective"]
         for m in modes[1:]:

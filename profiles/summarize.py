@@ -59,7 +59,7 @@ def main():
         out += ["## bench.py line (un-profiled run)", "", "```json", json.dumps(line, indent=1), "```", ""]
     except Exception as e:  # pragma: no cover
         out += [f"(no bench line: {e})", ""]
-    out += ["## `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline`", "",
+    out += ["## `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline`", "",
             "| kernel | calls | avg µs | total ms | % |", "|---|---|---|---|---|"]
     other_calls, other_ms, other_pct = 0, 0.0, 0.0
     for name, calls, avg, tot, pct in kernel_stats(d):
@@ -70,7 +70,7 @@ def main():
     out.append(f"| (PyTorch / MIOpen / hipBLASLt / RCCL / memset kernels of the comparison rows and the harness) | {other_calls} | | {other_ms:.2f} | {other_pct:.1f} |")
     init_rows = [r for r in kernel_stats(d, "trace_init") if ours(r[0])]
     if init_rows:
-        out += ["", "### the headline distribution alone: `... bench.py --steps 10 --warmup 3 --loc init --no-bf16 --no-em --no-settle --no-cpu-baseline --no-full-step`", "",
+        out += ["", "### the headline distribution alone: `... bench.py --full --steps 10 --warmup 3 --loc init --no-bf16 --no-em --no-settle --no-cpu-baseline --no-full-step`", "",
                 "(the trace above mixes the init / sigma4 / uniform distributions, bf16 storage and the mosaic shape in one row per kernel; `roofline.avg_launch_us` of the",
                 "bench line is the routed backward at the init pattern: `rps_route_kernel` + `rps_tile_kernel` of THIS table, plus the 1-2 us of its event pair)", "",
                 "| kernel | calls | avg µs | total ms | % |", "|---|---|---|---|---|"]
