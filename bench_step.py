@@ -172,7 +172,7 @@ class Step(nn.Module):
     @torch.no_grad()
     def prepare(self, mask, targets):
         """what depends on the batch's geometry only (level shapes, padding masks, valid ratios, encoder reference points, denoising
-        layout) and on the frozen text side (the two-stage scorer's packed operand): built once per batch shape -- a few small
+        layout) and the two-stage scorer's binding to the projection and the frozen text side: built once per batch shape -- a few small
         launches and host -> device copies a trainer repeats per step; kept out of the step so that it can be captured into a graph"""
         dev = mask.device
         shapes = list(W.pyramid_shapes(self.H, self.Wpad))
@@ -191,7 +191,7 @@ class Step(nn.Module):
         st["known_num"] = [len(t["labels"]) for t in targets]
         st["lay"] = prepare_dn_layout(st["known_num"], DN_NUMBER, NUM_QUERIES, use_cdn=True)
         st["scale"] = self.logit_scale.detach().clone()
-        self.scorer.prepare(self.dino_visual_proj.weight, self.text_embed, self.logit_scale)      # (once per weight update)
+        self.scorer.prepare(self.dino_visual_proj.weight, self.text_embed, self.logit_scale)      # (its operand follows the weight's updates)
         self.static = st
         self._targets = targets
         return st
@@ -447,9 +447,14 @@ def pin_grad_accumulators(params):
 CLIP_MAX_NORM = 0.1      # reference config/RichSem/baseline_4scale.py:19 (clip_max_norm), engine.py:110-112
 
 
-def make_optimizer(params):
-    """AdamW as the reference builds it (main.py:213-214; lr / weight_decay of config/RichSem/baseline_4scale.py:7,14), one fused launch per step"""
-    return torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-4, fused=True)
+LR = 1e-4
+
+
+def make_optimizer(params, lr=LR):
+    """AdamW as the reference builds it (main.py:213-214; lr / weight_decay of config/RichSem/baseline_4scale.py:7,14), one fused launch per
+    step (fused optimizers do not bump the parameters' version counters; richsem_amd/param_cache.py's step hook does, so the bf16 layers'
+    packed weights follow every step)"""
+    return torch.optim.AdamW(params, lr=lr, weight_decay=1e-4, fused=True)
 
 
 def optimizer_step(opt, params):
@@ -459,14 +464,17 @@ def optimizer_step(opt, params):
     opt.step()
 
 
-def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None):
-    """time `steps` composed steps (forward + loss + backward); returns the dict bench.py attaches as ``full_step``"""
-    model = Step(n_img=n_img, dev=dev)
+def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, **step_kwargs):
+    """time `steps` composed steps (forward + loss + backward); returns the dict bench.py attaches as ``full_step`` (tests: ``lr``,
+    ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model" --, ``step_kwargs``: a smaller Step)"""
+    model = Step(n_img=n_img, dev=dev, **step_kwargs)
     model.stop_at = stop_at      # (profiling aid: the step cut off after a section, see tools/step_sections.sh)
     images, mask, targets = model.batch()
     model.prepare(mask, targets)
+    if noise_seed is not None:
+        model.freeze_noise(noise_seed)
     params = [p for p in model.parameters() if p.requires_grad]
-    opt = make_optimizer(params)
+    opt = make_optimizer(params, lr)
 
     def step(indices=None, optimize=True):
         for p in params:
@@ -516,6 +524,8 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None):
            "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
            "forward_rows_ms": {k: round(sum(v) / len(v), 3) for k, v in rows.items()},
            "backward_ms": round(sum(bwds) / len(bwds), 2)}
+    if return_model:
+        out["model"] = model
     if not graph:
         return out
     # the device part as a captured graph: the assignment of the last eager step held fixed (the matcher's host round trip cannot be captured)
@@ -593,12 +603,14 @@ class _LossPart(nn.Module):
         return self.step[0].loss_part(*tensors)
 
 
-def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, **step_kwargs):
+def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, **step_kwargs):
     """The composed step as a trainer can run it WITHOUT freezing the matcher: the two device-only parts -- everything up to the matcher,
     and the criterion -- each captured once, forward and backward, with ``torch.cuda.make_graphed_callables`` (HIP graphs replayed by
     autograd), the Hungarian assignment between them live on the host every step.  Eagerly the step is bound by ~2900 kernel launches
     (ms above); this is the same work with three launches' worth of host time.  Returns the dict bench.py attaches as
-    ``full_step.graphed_sections`` (``step_kwargs``: a smaller Step for the tests)."""
+    ``full_step.graphed_sections`` (``step_kwargs``: a smaller Step for the tests; ``return_model``: the trained Step and the graphed model
+    part under "model" / "ga", ``images`` under "images").  The packed / cast forms of the parameters are built INSIDE the captured graphs
+    (richsem_amd/param_cache.py): every replay re-packs from the current masters, the frozen teacher's graph included."""
     model = Step(n_img=n_img, dev=dev, **step_kwargs)
     model.timing = False
     images, mask, targets = model.batch()
@@ -646,7 +658,7 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
             with quiet_gc(), torch.cuda.graph(teacher_graph, stream=side):
                 t_static = model.teacher_part(images)
             params = [p for p in model.parameters() if p.requires_grad]
-            opt = make_optimizer(params) if optimizer else None
+            opt = make_optimizer(params, lr) if optimizer else None
             last = {}
 
             def step():
@@ -684,17 +696,19 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
             "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
             "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
             **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
-                "indices": last["assign"], "topk": model.last_topk.clone()} if return_grads else {})}
+                "indices": last["assign"], "topk": model.last_topk.clone()} if return_grads else {}),
+            **({"model": model, "ga": ga, "images": images} if return_model else {})}
 
 
-def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None, backend_device=None):
+def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None, backend_device=None, lr=LR, return_model=False):
     """The composed step as a data-parallel TRAINING step (round-3 verdict item 5; reference main.py:204-206 wraps the whole model in
     DistributedDataParallel, engine.py:100-114 runs backward + optimizer step): the module in ``DistributedDataParallel`` (nccl = RCCL
     on GPUs; ``gradient_as_bucket_view=True``, DDP's own 25 MB buckets overlapped with the backward), AdamW on every trained parameter,
     every rank on its own images.  Called by ALL ranks.  Returns, on every rank, the dict bench.py attaches as ``full_step_ddp``:
     ``ms`` (max over ranks, barrier + synchronise on both sides of the timed steps), ``ms_no_collective`` (the same steps under
     ``no_sync()``: no all-reduce) and the job's images per second.  ``make_model``: a stand-in module factory (tests/test_dist_gloo.py
-    runs the protocol on CPU with gloo; the module needs ``batch()`` -> forward arguments and optionally ``prepare(*batch()[1:])``)."""
+    runs the protocol on CPU with gloo; the module needs ``batch()`` -> forward arguments and optionally ``prepare(*batch()[1:])``;
+    ``return_model``: the trained module under "model")."""
     import contextlib
     from torch.nn.parallel import DistributedDataParallel as DDP
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
@@ -711,8 +725,8 @@ def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None
     else:
         ddp = model
     params = [p for p in model.parameters() if p.requires_grad]
-    opt = (torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-4, fused=True) if is_cuda else
-           torch.optim.AdamW(params, lr=1e-4, weight_decay=1e-4)) if optimizer else None      # main.py:213-214
+    opt = (torch.optim.AdamW(params, lr=lr, weight_decay=1e-4, fused=True) if is_cuda else
+           torch.optim.AdamW(params, lr=lr, weight_decay=1e-4)) if optimizer else None      # main.py:213-214
 
     def step(sync=True):
         if opt is not None:
@@ -758,7 +772,8 @@ def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None
                     "ms = max over ranks",
             "world": world, "ms": round(ms, 2), "ms_no_collective": round(ms_nc, 2), "img_per_s": round(world * n_img / (ms * 1e-3), 2),
             "img_per_s_per_rank": round(n_img / (ms * 1e-3), 2), "optimizer": "AdamW" if optimizer else None, "loss": loss,
-            "trained_parameters": sum(p.numel() for p in params), "parameters_without_gradient": unused}
+            "trained_parameters": sum(p.numel() for p in params), "parameters_without_gradient": unused,
+            **({"model": model} if return_model else {})}
 
 
 if __name__ == "__main__":

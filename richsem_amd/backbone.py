@@ -135,6 +135,8 @@ class FrozenBatchNorm2d(nn.Module):
         super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def scale_shift(self):
+        # (its own version key, not a VersionCache: the four BUFFERS are frozen -- no optimizer writes them -- and the fold stays outside
+        # any graph that captures the backbone: a replay reads the eager fold, which lives as long as this module)
         ver = (self.weight._version, self.bias._version, self.running_mean._version, self.running_var._version, self.weight.data_ptr())
         if getattr(self, "_folded_ver", None) != ver:       # the buffers are frozen: folded once (and again after a load_state_dict)
             self._folded = fold_bn(self.weight, self.bias, self.running_mean, self.running_var, 1e-5)

@@ -10,6 +10,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .param_cache import VersionCache, capturing
 
 
 def _stream(dev):
@@ -263,9 +264,10 @@ def _pack(w):
 class PackCache:
     """Packed forms of ONE convolution weight, owned by the module that owns the parameter (no global table: a freed tensor's address
     can come back with the same version counter): the forward weight and the flipped / transposed / scale-folded weight of the input
-    gradient, refreshed when the parameter (or the scale) has been modified in place -- i.e. after an optimizer step, a
-    ``load_state_dict`` or any other in-place op that autograd's version counter sees.  Writes through ``param.data`` bypass that
-    counter: call :meth:`clear` after them."""
+    gradient, refreshed when the parameter (or the scale) has been modified in place -- i.e. after any optimizer step (fused ones
+    included: richsem_amd/param_cache.py bumps the version counters of what an optimizer step updates), a ``load_state_dict`` or any
+    other in-place op that autograd's version counter sees.  Writes through ``param.data`` bypass that counter: call :meth:`clear`
+    after them.  During a graph capture :meth:`get` packs on every call and keeps nothing (param_cache.py, rule 2)."""
 
     def __init__(self):
         self._slots = {}
@@ -274,6 +276,8 @@ class PackCache:
         self._slots.clear()
 
     def get(self, weight, scale, transposed):
+        if capturing(weight):
+            return _pack_form(weight, scale, transposed)
         ver = (weight.data_ptr(), weight._version, scale.data_ptr() if transposed else 0, scale._version if transposed else 0,
                tuple(weight.shape))
         hit = self._slots.get(transposed)
@@ -384,16 +388,13 @@ class ConvBNAct(torch.nn.Module):
         self.register_buffer("running_var", torch.ones(out_channels))
         self.stride, self.padding, self.relu = stride, padding, relu
         self._pack_cache = PackCache()
+        self._folded = VersionCache()
 
     def scale_shift(self):
         """the frozen affine, folded once and again only after the buffers changed (a fresh tensor per call would defeat the
         PackCache's key, or -- at a recycled address -- alias a stale scale-folded weight)"""
-        ver = (self.bn_weight._version, self.bn_bias._version, self.running_mean._version, self.running_var._version,
-               self.bn_weight.data_ptr())
-        if getattr(self, "_folded_ver", None) != ver:
-            self._folded = fold_bn(self.bn_weight, self.bn_bias, self.running_mean, self.running_var, 1e-5)
-            self._folded_ver = ver
-        return self._folded
+        return self._folded.get((self.bn_weight, self.bn_bias, self.running_mean, self.running_var),
+                                lambda: fold_bn(self.bn_weight, self.bn_bias, self.running_mean, self.running_var, 1e-5))
 
     def forward(self, x, residual=None):
         scale, shift = self.scale_shift()

@@ -8,6 +8,7 @@ import ctypes
 import torch
 
 from .. import _lib
+from ..param_cache import VersionCache  # noqa: F401  (the caches' home: richsem_amd/param_cache.py)
 
 
 def linear_wgrad_supported(out_features, in_features):
@@ -190,26 +191,6 @@ class LinearBf16CachedFunction(torch.autograd.Function):
             grads = (dw[:split] if dw is not None else None, dw[split:] if dw is not None else None,
                      db[:split] if db is not None else None, db[split:] if db is not None else None)
         return (dx, None, None, None) + tuple(g.to(dt) if g is not None and n else None for g, dt, n in zip(grads, dts, need))
-
-
-class VersionCache:
-    """A derived form of a few parameters (bf16 casts, packed weights, stacked projections) kept across calls and rebuilt when one of
-    them has been modified in place (optimizer step, ``load_state_dict``, ``copy_``: whatever bumps autograd's version counter).  Writes
-    THROUGH ``param.data`` bypass that counter: call :meth:`clear` after them."""
-
-    def __init__(self):
-        self._ver = self._val = None
-
-    def clear(self):
-        self._ver = self._val = None
-
-    def get(self, params, build):
-        ver = tuple((p.data_ptr(), p._version) for p in params)
-        if ver != self._ver:
-            with torch.no_grad():
-                self._val = build()
-            self._ver = ver
-        return self._val
 
 
 def pack_linear256(weights, biases):

@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from ..param_cache import VersionCache
 from ..roi import ROIAlign
 
 
@@ -25,6 +26,7 @@ class AttentionPool2d(nn.Module):
         self.v_proj = nn.Linear(embed_dim, embed_dim)
         self.c_proj = nn.Linear(embed_dim, output_dim or embed_dim)
         self.num_heads = num_heads
+        self._derived_caches = {}       # dtype -> VersionCache of the derived forms below
 
     @torch.no_grad()
     def forward(self, x):
@@ -59,16 +61,17 @@ class AttentionPool2d(nn.Module):
 
     def _derived(self, dt):
         """per-dtype forms of the (frozen) parameters, rebuilt when a parameter has been modified: scaled query projection, per-head
-        views of the key / value projections, the output bias with the value bias folded in"""
+        views of the key / value projections, the output bias with the value bias folded in (built inside a graph that captures the
+        pool: richsem_amd/param_cache.py)"""
         ps = (self.positional_embedding, self.q_proj.weight, self.q_proj.bias, self.k_proj.weight, self.v_proj.weight, self.v_proj.bias,
               self.c_proj.weight, self.c_proj.bias)
-        ver = (dt,) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_derived_ver", None) != ver:
+
+        def build():
             C, H = self.q_proj.weight.shape[0], self.num_heads
             hd = C // H
             scale = hd ** -0.5
             wc = self.c_proj.weight.detach().to(dt)
-            self._derived_cache = {
+            return {
                 "pos": self.positional_embedding.detach().to(dt).contiguous(),
                 "pos_t": self.positional_embedding.detach().to(dt).t().contiguous(),
                 "wq_t": (self.q_proj.weight.detach().to(dt) * scale).t().contiguous(),
@@ -78,8 +81,7 @@ class AttentionPool2d(nn.Module):
                 "wc_t": wc.t().contiguous(),
                 "bc": (self.c_proj.bias.detach().to(dt) + wc @ self.v_proj.bias.detach().to(dt)).contiguous(),
             }
-            self._derived_ver = ver
-        return self._derived_cache
+        return self._derived_caches.setdefault(dt, VersionCache()).get(ps, build)
 
 
 @torch.no_grad()

@@ -41,7 +41,7 @@ class MSDeformAttn(nn.Module):
         # True (default): one GEMM for offsets + attention logits, softmax / location arithmetic / padding mask in the library's
         # own kernels (functions/fused.py).  False: the reference's op-by-op sequence.  Same parameters, same results.
         self.fused = True
-        self._bf16_ver = self._bf16_cache = None
+        self._bf16 = VersionCache()       # bf16 casts of the projections (other widths)
         self._packs = VersionCache()      # lin256 forms of the four projections (d_model = 256)
 
         self.sampling_offsets = nn.Linear(d_model, n_heads * n_levels * n_points * 2)
@@ -70,11 +70,11 @@ class MSDeformAttn(nn.Module):
 
     def invalidate_bf16_cache(self):
         """Drop the cached bf16 forms of the parameters.  They are refreshed by themselves after every in-place update autograd's
-        version counter sees (optimizer steps, ``load_state_dict``, ``copy_``); writes THROUGH ``param.data`` (``constant_(w.data, ...)``,
-        some third-party optimizers, manual EMA / weight surgery) bypass that counter: call this after them."""
-        self._bf16_ver = None
-        self._bf16_cache = None
+        version counter sees (optimizer steps -- fused ones through richsem_amd/param_cache.py's step hook --, ``load_state_dict``,
+        ``copy_``); writes THROUGH ``param.data`` (``constant_(w.data, ...)``, manual EMA / weight surgery) bypass that counter: call
+        this after them."""
         if hasattr(self, "_packs"):
+            self._bf16.clear()
             self._packs.clear()
 
     def _load_from_state_dict(self, *args, **kwargs):
@@ -86,15 +86,9 @@ class MSDeformAttn(nn.Module):
         them has been modified in place (optimizer step, load_state_dict; see :meth:`invalidate_bf16_cache` for ``.data`` writes)"""
         ps = (self.value_proj.weight, self.value_proj.bias, self.sampling_offsets.weight, self.sampling_offsets.bias,
               self.attention_weights.weight, self.attention_weights.bias, self.output_proj.weight, self.output_proj.bias)
-        ver = tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_bf16_ver", None) != ver:
-            with torch.no_grad():
-                b16 = lambda t: t.detach().to(torch.bfloat16).contiguous()
-                self._bf16_cache = {
-                    "wv": b16(ps[0]), "bv": b16(ps[1]), "wq": b16(torch.cat((ps[2], ps[4]), 0)), "bq": b16(torch.cat((ps[3], ps[5]), 0)),
-                    "wo": b16(ps[6]), "bo": b16(ps[7])}
-            self._bf16_ver = ver
-        return self._bf16_cache
+        b16 = lambda t: t.detach().to(torch.bfloat16).contiguous()
+        return self._bf16.get(ps, lambda: {"wv": b16(ps[0]), "bv": b16(ps[1]), "wq": b16(torch.cat((ps[2], ps[4]), 0)),
+                                           "bq": b16(torch.cat((ps[3], ps[5]), 0)), "wo": b16(ps[6]), "bo": b16(ps[7])})
 
     def _lin256_packs(self):
         ps = (self.value_proj.weight, self.value_proj.bias, self.sampling_offsets.weight, self.sampling_offsets.bias,
@@ -102,22 +96,23 @@ class MSDeformAttn(nn.Module):
         return self._packs.get(ps, lambda: {"v": pack_linear256([ps[0]], [ps[1]]), "q": pack_linear256([ps[2], ps[4]], [ps[3], ps[5]]),
                                             "o": pack_linear256([ps[6]], [ps[7]])})
 
-    def project_value(self, input_flatten, input_padding_mask=None, params=None):
+    def project_value(self, input_flatten, input_padding_mask=None, params=None, pk=None):
         """bf16, d_model = 256: ``value_proj(input_flatten)`` with the rows of padded pixels zeroed (reference :94-96), (N, S, C);
-        ``params``: stand-ins for (value_proj.weight, value_proj.bias) to route the gradients to"""
-        pk = self._lin256_packs()
+        ``params``: stand-ins for (value_proj.weight, value_proj.bias) to route the gradients to; ``pk``: :meth:`_lin256_packs` when the
+        caller has them"""
+        pk = self._lin256_packs() if pk is None else pk
         mask = input_padding_mask.contiguous() if input_padding_mask is not None else None
         vw, vb = params if params is not None else (self.value_proj.weight, self.value_proj.bias)
         return Lin256Function.apply(input_flatten.to(torch.bfloat16), pk["v"], mask, False, vw, vb)
 
-    def forward_from_value(self, query, reference_points, value, input_spatial_shapes, input_level_start_index, params=None):
+    def forward_from_value(self, query, reference_points, value, input_spatial_shapes, input_level_start_index, params=None, pk=None):
         """bf16, d_model = 256: the module's forward behind the value projection (reference :97-114) -- for callers that project the
         memory for several layers at once (richsem_amd/modules/decoder.py).  ``params``: stand-ins for (sampling_offsets.weight,
         attention_weights.weight, sampling_offsets.bias, attention_weights.bias, output_proj.weight, output_proj.bias) to route the
-        gradients to (a layer's WgradBoundary aliases: functions/linear.py)"""
+        gradients to (a layer's WgradBoundary aliases: functions/linear.py); ``pk``: :meth:`_lin256_packs` when the caller has them"""
         N, S = value.shape[0], value.shape[1]
         H, L, P = self.n_heads, self.n_levels, self.n_points
-        pk = self._lin256_packs()
+        pk = self._lin256_packs() if pk is None else pk
         if params is None:
             params = (self.sampling_offsets.weight, self.attention_weights.weight, self.sampling_offsets.bias, self.attention_weights.bias,
                       self.output_proj.weight, self.output_proj.bias)
@@ -155,17 +150,17 @@ class MSDeformAttn(nn.Module):
                 # value_proj with the padding mask in its epilogue, offsets + logits as ONE 256 -> 384 projection, output_proj; their
                 # input gradients on the same kernel where the layer is 256 -> 256, the weight gradients on the weight-gradient kernel
                 # (the three weight gradients in one launch -- functions/linear.py: WgradGroup -- unless a caller's group is active)
-                group = None
+                group, pk = None, self._lin256_packs()      # (one lookup: during a graph capture every lookup packs)
                 if WgradGroup.active() is None and WgradGroup.enabled and torch.is_grad_enabled() and self.value_proj.weight.requires_grad:
                     group = WgradGroup()
                     al = wgrad_boundary(group, self.value_proj.weight, self.value_proj.bias, self.sampling_offsets.weight,
                                              self.attention_weights.weight, self.sampling_offsets.bias, self.attention_weights.bias,
                                              self.output_proj.weight, self.output_proj.bias)
                     with group:
-                        return self.forward_from_value(query, reference_points, self.project_value(input_flatten, input_padding_mask, al[:2]),
-                                                       input_spatial_shapes, input_level_start_index, params=al[2:])
-                return self.forward_from_value(query, reference_points, self.project_value(input_flatten, input_padding_mask),
-                                               input_spatial_shapes, input_level_start_index)
+                        return self.forward_from_value(query, reference_points, self.project_value(input_flatten, input_padding_mask, al[:2], pk),
+                                                       input_spatial_shapes, input_level_start_index, params=al[2:], pk=pk)
+                return self.forward_from_value(query, reference_points, self.project_value(input_flatten, input_padding_mask, pk=pk),
+                                               input_spatial_shapes, input_level_start_index, pk=pk)
             if dt == torch.bfloat16:
                 # bf16, other widths: library GEMMs for the forward and the input gradient, the library's own MFMA kernel for the weight
                 # gradient (its contraction runs over the tokens); the bf16 casts of the parameters and the stacked offsets / logits

@@ -137,8 +137,21 @@ def test_composed_step_under_ddp_with_optimizer(nccl_world1):
         m.batch = batch
         return m
 
-    res = bench_step.run_ddp(2, dev, dist, steps=2, warmup=1, optimizer=True, make_model=make)
+    res = bench_step.run_ddp(2, dev, dist, steps=2, warmup=1, optimizer=True, make_model=make, lr=2e-3, return_model=True)
     assert res["world"] == 1 and res["ms"] > 0 and res["ms_no_collective"] > 0
     assert res["parameters_without_gradient"] == [], res["parameters_without_gradient"]
     assert np.isfinite(res["loss"])
     assert not torch.equal(holder["m"].encoder[0].linear1.weight.detach(), holder["w0"])      # AdamW moved the weights
+    # ... and the bf16 layers compute with the moved weights: the trained module's model part equals a fresh Step's loaded with the
+    # trained state_dict, and differs from one with the initial weights (tests/test_gpu_param_caches.py: check_trained_step)
+    from test_gpu_param_caches import check_trained_step
+    model = res.pop("model")
+    assert model is holder["m"]
+    model.freeze_noise(3)
+    images, mask, targets = bench_step.Step.batch(model, seed=0)
+    with torch.no_grad():
+        got = [t.detach().float().clone() for t in model.model_part(images, mask, targets, teacher=False)]
+    topk, operand = model.last_topk.clone(), model.scorer.packed.clone()
+    state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    del model, holder["m"]
+    check_trained_step(got, topk, state, seed=3, tag="ddp", scorer_operand=operand)
