@@ -29,6 +29,7 @@ from richsem_amd.backbone import InputProjection, ResNet50
 from richsem_amd.capture import quiet_gc
 from richsem_amd.clip_resnet import ModifiedResNetTeacher
 from richsem_amd.dn import prepare_dn_layout
+from richsem_amd.fed_loss import FedClassSampler, MaskedFocalNegativeSum, class_weights_from_image_counts
 from richsem_amd.functions.linear import Lin256Function, VersionCache, pack_linear256
 from richsem_amd.matcher import BoxPairLoss, FocalNegativeSum, FocalPositiveSum, HungarianMatcher
 from richsem_amd.modules import (MLP, refine_boxes, DeformableTransformerDecoderLayer, DeformableTransformerEncoderLayer, TransformerDecoder,
@@ -99,7 +100,8 @@ def encoder_output_proposals(memory_padding_mask, shapes):
 class Step(nn.Module):
     """the rows with their (synthetic) parameters; ``forward`` = model forward + criterion, returns the loss and section times"""
 
-    def __init__(self, n_img=2, height=800, width=1333, boxes_per_image=12, seed=0, dev="cuda"):
+    def __init__(self, n_img=2, height=800, width=1333, boxes_per_image=12, seed=0, dev="cuda", fed_loss=False, fed_num_sample_cats=50,
+                 class_image_counts=None):
         super().__init__()
         torch.manual_seed(seed)
         self.n_img, self.H, self.Wimg, self.K = n_img, height, width, boxes_per_image
@@ -139,6 +141,14 @@ class Step(nn.Module):
         # fp32 from the input projections on (PyTorch ops around the operator's fp32 entry points; the backbone stays on the bf16
         # convolution kernels, its output is cast) -- the yardstick of tests/test_gpu_step.py
         self.act_dtype = torch.bfloat16
+        # the federated loss (reference use_fed_loss / fed_num_sample_cats, richsem.py:956-961): opt-in, see loss_part.  Without
+        # class_image_counts the class weights come from synthetic_image_counts() -- a made-up long tail, NOT LVIS's counts
+        self.fed_loss = bool(fed_loss)
+        self.fed_sampler = None
+        if self.fed_loss:
+            counts = synthetic_image_counts(NUM_CLASSES) if class_image_counts is None else class_image_counts
+            self.fed_sampler = FedClassSampler(fed_num_sample_cats, class_weights_from_image_counts(counts, NUM_CLASSES))
+        self.last_fed_mask = None
 
     # synthetic LVIS-shaped batch
     def batch(self, seed=0):
@@ -307,6 +317,7 @@ class Step(nn.Module):
 
     _model_only = False
     frozen_noise = None
+    frozen_fed = None
 
     def freeze_noise(self, seed):
         """draw the denoising noise ONCE from ``seed`` and use it in every later step (a training step draws it anew each time,
@@ -318,6 +329,19 @@ class Step(nn.Module):
         self.frozen_noise = {"p": torch.rand(n, device=dev, generator=g), "labels": torch.randint(0, NUM_CLASSES, (n,), device=dev, generator=g),
                              "sign": torch.randint(0, 2, (n, 4), device=dev, generator=g).float() * 2 - 1,
                              "rand": torch.rand((n, 4), device=dev, generator=g)}
+
+    def fed_groups(self):
+        """how many class draws a step of the federated loss makes: one per reference loss_labels call -- the matching part of every
+        decoder layer, their denoising parts, the two-stage output"""
+        return 2 * len(self.decoder.layers) + 1
+
+    def freeze_fed(self, seed):
+        """draw the federated loss's class masks ONCE from ``seed`` (for the batch ``prepare`` saw) and use them in every later step (a
+        training step draws them anew each time): eager and graphed forms of the step can then be compared on the same draws"""
+        dev = self.level_embed.device
+        labels = torch.cat([t["labels"] for t in self._targets])
+        g = torch.Generator(device=dev).manual_seed(seed)
+        self.frozen_fed, _ = self.fed_sampler.sample(labels, self.fed_groups(), generator=g)
 
     def model_part(self, images, mask=None, targets=None, teacher=True):
         """the step up to the matcher: -> (logits (6, N, Q, C), boxes (6, N, Q, 4), two-stage logits, two-stage boxes, distillation logits,
@@ -374,14 +398,20 @@ class Step(nn.Module):
 
     def loss_part(self, logits, coords, il, ib, clip_logits, t_logits, labels, boxes, m_dec, m_int, m_dis):
         """criterion (richsem.py:1124-1306, compact): the same per-output sums as the reference's loop over the 6 + 1 outputs -- sigmoid focal
-        loss (over every query incl. the denoising part's negative slots, whose target is no-object; the federated-loss class sampling of
-        use_fed_loss is not restated: all classes count), L1 + GIoU on the matched pairs and on the denoising queries' positive slots, KL
-        distillation -- formed in ONE pass per kind over
+        loss (over every query incl. the denoising part's negative slots, whose target is no-object), L1 + GIoU on the matched pairs and on
+        the denoising queries' positive slots, KL distillation -- formed in ONE pass per kind over
         the stacked outputs: the all-negative focal term of a whole logit tensor is one kernel each way (matcher.FocalNegativeSum), and the
         positive entries / box pairs of the matched, two-stage and denoising parts are concatenated with a weight each (1 / num_boxes, or
         1 / (num_boxes x groups)) so that every loss formula runs once -- as one kernel each (matcher.FocalPositiveSum, matcher.BoxPairLoss:
         value and gradient in one launch; a loop over the outputs is ~40 small launches per output and kind).
-        Tensors in, the loss out."""
+        By default every class counts in the focal loss.  With ``fed_loss`` (the reference's use_fed_loss, richsem.py:956-961) each of the
+        13 reference loss_labels calls -- the matching part of decoder layers 0-5, their denoising parts, the two-stage output, in that
+        order -- takes it over a class subset of its own: the batch's target classes (what every one of those calls passes to
+        get_fed_loss_inds: the Hungarian matching assigns every target, the denoising targets repeat the same labels) topped up to
+        fed_num_sample_cats by weighted draws without replacement, drawn afresh every step on the device (fed_loss.FedClassSampler, no host
+        sync: the draw is captured and replayed with the rest) -- or the masks of ``freeze_fed``.  The all-negative term then runs
+        with a class mask per row (fed_loss.MaskedFocalNegativeSum); the positive entries are appeared classes, always in the mask.
+        The last masks are kept as ``last_fed_mask`` (13, C).  Tensors in, the loss out."""
         st = self.static
         dev = logits.device
         lay = st["lay"]
@@ -406,9 +436,20 @@ class Step(nn.Module):
                    "dn_n": torch.arange(N, device=dev)[None, :, None].expand(nl, N, pos_slots.numel()).reshape(-1),
                    "dn_q": pos_slots[None, None, :].expand(nl, N, -1).reshape(-1),
                    "w_dn": torch.full((n_dn,), 1.0 / nbx, dtype=torch.float32, device=dev)}
+            if self.fed_loss:      # the class draw each row's focal term uses: layer l's matching part -> l, its denoising part -> nl + l; two-stage -> 2 nl
+                g_q = torch.arange(nl, dtype=torch.int32, device=dev)[:, None, None].expand(nl, N, Q).clone()
+                g_q[:, :, :pad] += nl
+                cst["g_rows"] = g_q.contiguous()
+                cst["g_int"] = torch.full(il.shape[:2], 2 * nl, dtype=torch.int32, device=dev)
             st["loss_static"] = cst
         # ---- classification: all-negative term of every entry, then what the positive entries contribute instead ------------------------
-        loss = FocalNegativeSum.apply(logits, cst["w_rows"], alpha) + FocalNegativeSum.apply(il, cst["w_int"], alpha)
+        if self.fed_loss:
+            fed = self.frozen_fed if self.frozen_fed is not None else self.fed_sampler.sample(labels, 2 * nl + 1)[0]
+            self.last_fed_mask = fed
+            loss = MaskedFocalNegativeSum.apply(logits, cst["w_rows"], cst["g_rows"], fed, alpha) + \
+                MaskedFocalNegativeSum.apply(il, cst["w_int"], cst["g_int"], fed, alpha)
+        else:
+            loss = FocalNegativeSum.apply(logits, cst["w_rows"], alpha) + FocalNegativeSum.apply(il, cst["w_int"], alpha)
         li, bi, si, tj = m_dec
         _, ibi, isi, itj = m_int
         dn_lab = labels.view(N, -1).repeat(1, groups)[None].expand(nl, -1, -1).reshape(-1)      # every image has `single` boxes here
@@ -432,6 +473,14 @@ class Step(nn.Module):
             out[name] = prev.elapsed_time(ev)
             prev = ev
         return out
+
+
+def synthetic_image_counts(C, seed=1203):
+    """a fixed, seeded, SYNTHETIC long-tail table of per-class image counts for the federated loss's weights when no dataset's counts are
+    given -- made up, not LVIS's: class 0 gets 0 (LVIS has no category 0), classes 1..C-1 a random order of 1 + 10000 / rank"""
+    g = torch.Generator().manual_seed(seed)
+    rank = torch.randperm(C - 1, generator=g) + 1
+    return torch.cat((torch.zeros(1, dtype=torch.int64), 1 + 10000 // rank))
 
 
 def pin_grad_accumulators(params):
@@ -575,7 +624,8 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
     try:
         del model
         torch.cuda.empty_cache()
-        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup)
+        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts")}
+        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
         traceback.print_exc(file=sys.stderr)
@@ -603,13 +653,14 @@ class _LossPart(nn.Module):
         return self.step[0].loss_part(*tensors)
 
 
-def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, **step_kwargs):
+def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, fed_seed=None,
+                **step_kwargs):
     """The composed step as a trainer can run it WITHOUT freezing the matcher: the two device-only parts -- everything up to the matcher,
     and the criterion -- each captured once, forward and backward, with ``torch.cuda.make_graphed_callables`` (HIP graphs replayed by
     autograd), the Hungarian assignment between them live on the host every step.  Eagerly the step is bound by ~2900 kernel launches
     (ms above); this is the same work with three launches' worth of host time.  Returns the dict bench.py attaches as
     ``full_step.graphed_sections`` (``step_kwargs``: a smaller Step for the tests; ``return_model``: the trained Step and the graphed model
-    part under "model" / "ga", ``images`` under "images").  The packed / cast forms of the parameters are built INSIDE the captured graphs
+    part under "model" / "ga", ``images`` under "images", the training step under "step"; ``fed_seed``: Step.freeze_fed).  The packed / cast forms of the parameters are built INSIDE the captured graphs
     (richsem_amd/param_cache.py): every replay re-packs from the current masters, the frozen teacher's graph included."""
     model = Step(n_img=n_img, dev=dev, **step_kwargs)
     model.timing = False
@@ -618,6 +669,8 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
     model._mask = mask
     if noise_seed is not None:
         model.freeze_noise(noise_seed)
+    if fed_seed is not None:
+        model.freeze_fed(fed_seed)
     part_a, part_b = _ModelPart(model), _LossPart(model)
     # ONE side stream for the eager warm-up, the captures and the training steps: torch captures on its class-wide capture stream, which is
     # set to that stream here -- the library's workspaces are per (device, stream) and are not allocated during capture (on a cold stream
@@ -697,7 +750,15 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
             "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
             **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
                 "indices": last["assign"], "topk": model.last_topk.clone()} if return_grads else {}),
-            **({"model": model, "ga": ga, "images": images} if return_model else {})}
+            **({"model": model, "ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else {})}
+
+
+def _on_stream(stream, fn):
+    """run ``fn`` on ``stream`` (where run_graphed pinned the parameters' AccumulateGrad nodes) and make the current stream wait for it"""
+    with torch.cuda.stream(stream):
+        out = fn()
+    torch.cuda.current_stream().wait_stream(stream)
+    return out
 
 
 def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None, backend_device=None, lr=LR, return_model=False):
@@ -785,5 +846,8 @@ if __name__ == "__main__":
     ap.add_argument("--images", type=int, default=2)
     ap.add_argument("--no-graph", action="store_true", help="eager steps only (the form profiled for profiles/*_step_kernels.md)")
     ap.add_argument("--stop-at", default=None, help="profiling aid: cut the step off after this section (implies --no-graph)")
+    ap.add_argument("--fed-loss", action="store_true", help="the criterion's federated loss (use_fed_loss, 50 classes per draw; synthetic class "
+                                                           "weights: Step.loss_part)")
     a_ = ap.parse_args()
-    print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at), indent=1))
+    print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at,
+                         **({"fed_loss": True} if a_.fed_loss else {})), indent=1))

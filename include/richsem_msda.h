@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define RICHSEM_MSDA_ABI_VERSION 8
+#define RICHSEM_MSDA_ABI_VERSION 9
 
 /* Return codes: 0 = success; negative = argument error detected on the host (nothing was
  * launched); positive = hipError_t reported by the runtime. */
@@ -313,6 +313,28 @@ int msda_focal_neg_sum_f32(const float *logits, const float *row_weight, int64_t
                            int *n_partial, msda_stream_t stream);
 int msda_focal_neg_grad_f32(const float *logits, const float *row_weight, int64_t rows, int C, float alpha, const float *gscale,
                             float *grad_logits, msda_stream_t stream);
+
+/* ---- the federated loss (ABI v9; reference models/richsem/fed_loss.py:15-25 through SetCriterion.loss_labels, richsem.py:930-961 with
+ * use_fed_loss): each loss_labels call takes the focal loss over a class subset only -- every class among the matched targets, topped up to
+ * num_sample_cats classes drawn without replacement with probability proportional to a class weight (image_count ** 0.5, set_cats) -- with a
+ * fresh draw per call.  Here the draw runs on the device with fixed shapes, so it can be captured into a graph and replayed.
+ * msda_fed_class_mask_f32: labels (n_labels) int64 (the matched targets' classes, shared by every group; repeats and n_labels = 0 allowed,
+ *   classes outside [0, C) ignored), class_weight (C) float32 (weight <= 0: never drawn), uniform (groups, C) float32 in [0, 1) (the caller's
+ *   RNG; one independent draw per group) -> mask (groups, C) float32: 1 for every appeared class and for m = max(num_sample_cats - a, 0)
+ *   more (a = distinct appeared classes), 0 elsewhere; n_chosen (groups) int32 = a + min(m, eligible).  The m classes of group g are those
+ *   with the smallest keys -log1p(-u) / w (the exponential race: the distribution of m sequential weighted draws without replacement, that is
+ *   of torch.multinomial(w, m, replacement=False)), ties to the lower class index.  Where fewer than m classes are eligible (weight > 0, not
+ *   appeared) every eligible class is taken -- torch.multinomial raises there instead; n_chosen says so.  C <= 4096, one workgroup per group.
+ * msda_focal_neg_sum_masked_f32 / msda_focal_neg_grad_masked_f32: msda_focal_neg_sum_f32 / _grad_f32 with row r counting class c only
+ *   where class_mask[row_group[r]][c] != 0 (row_group (rows) int32; class_mask (groups, C) float32, a 0 / 1 selector; a row whose group lies
+ *   outside [0, groups) counts nothing).  The gradient is written at every element and is exactly 0 where the mask is 0; an all-ones mask
+ *   gives the bits of the unmasked functions. */
+int msda_fed_class_mask_f32(const int64_t *labels, int64_t n_labels, const float *class_weight, const float *uniform, int groups, int C,
+                            int num_sample_cats, float *mask, int32_t *n_chosen, msda_stream_t stream);
+int msda_focal_neg_sum_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
+                                  int64_t rows, int C, float alpha, double *partial, int max_partial, int *n_partial, msda_stream_t stream);
+int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
+                                   int64_t rows, int C, float alpha, const float *gscale, float *grad_logits, msda_stream_t stream);
 
 /* The criterion's per-pair tails, one launch each (K pairs, float32): loss[0] <- the weighted sum, grad <- its gradient w.r.t. the
  * predictions (multiply by the incoming scalar gradient).  msda_box_pair_loss_f32: sum_k w[k] (c_l1 |p_k - t_k|_1 + c_giou (1 - GIoU(p_k,

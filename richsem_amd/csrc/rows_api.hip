@@ -227,6 +227,8 @@ __global__ __launch_bounds__(256) void focal_neg_grad_kernel(const float *__rest
     }
 }
 
+#include "msda_fed.h"      // (the federated loss: class sampler + the masked form of the two kernels above, which it shares focal_neg with)
+
 // ---- the criterion's per-pair tails as one kernel each (verdict item 3: "one kernel for the stacked focal + L1 + GIoU tails") -------------
 // Box loss of K matched pairs (reference SetCriterion.loss_boxes, models/richsem/richsem.py:1162-1188 with util/box_ops.py:9-64 on the
 // diagonal):   sum_k w[k] * ( c_l1 * |p_k - t_k|_1 + c_giou * (1 - GIoU(xyxy(p_k), xyxy(t_k))) ),   p, t = (cx, cy, w, h)
@@ -343,6 +345,47 @@ int msda_focal_neg_grad_f32(const float *logits, const float *row_weight, int64_
     const int grid = (int)std::min<int64_t>(rows, 8192);
     hipLaunchKernelGGL(focal_neg_grad_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
                        1.f - alpha, gscale, grad_logits);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : (int)e;
+}
+
+/* msda_fed_class_mask_f32: per group g, mask[g][c] = 1 for the classes among labels and for m = max(num_sample_cats - appeared, 0) more
+ * drawn without replacement with probability proportional to class_weight (the exponential race, msda_fed.h), 0 elsewhere;
+ * n_chosen[g] = appeared + min(m, eligible).  msda_focal_neg_{sum,grad}_masked_f32: msda_focal_neg_{sum,grad}_f32 with the classes of row r
+ * restricted to class_mask[row_group[r]]. */
+int msda_fed_class_mask_f32(const int64_t *labels, int64_t n_labels, const float *class_weight, const float *uniform, int groups, int C,
+                            int num_sample_cats, float *mask, int32_t *n_chosen, msda_stream_t stream)
+{
+    if (!class_weight || !uniform || !mask || !n_chosen || (n_labels > 0 && !labels)) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (n_labels < 0 || groups < 1 || C < 1 || C > msda::kFedMaxClasses || num_sample_cats < 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    int P2 = 1;
+    while (P2 < C) P2 <<= 1;
+    const int threads = std::min(msda::kFedThreads, std::max(64, P2 / 2));
+    hipLaunchKernelGGL(msda::fed_class_mask_kernel, dim3(groups), dim3(threads), sizeof(unsigned long long) * P2, static_cast<hipStream_t>(stream),
+                       labels, (long long)n_labels, class_weight, uniform, C, P2, num_sample_cats, mask, n_chosen);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : (int)e;
+}
+int msda_focal_neg_sum_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
+                                  int64_t rows, int C, float alpha, double *partial, int max_partial, int *n_partial, msda_stream_t stream)
+{
+    if (!logits || !row_weight || !row_group || !class_mask || !partial || !n_partial) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows < 1 || C < 1 || groups < 1 || max_partial < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    const int grid = (int)std::min<int64_t>(std::min<int64_t>(rows, 4096), max_partial);
+    *n_partial = grid;
+    hipLaunchKernelGGL(msda::focal_neg_sum_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
+                       class_mask, groups, (long long)rows, C, 1.f - alpha, partial);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : (int)e;
+}
+int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
+                                   int64_t rows, int C, float alpha, const float *gscale, float *grad_logits, msda_stream_t stream)
+{
+    if (!logits || !row_weight || !row_group || !class_mask || !gscale || !grad_logits) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows < 1 || C < 1 || groups < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    const int grid = (int)std::min<int64_t>(rows, 8192);
+    hipLaunchKernelGGL(msda::focal_neg_grad_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
+                       class_mask, groups, (long long)rows, C, 1.f - alpha, gscale, grad_logits);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MSDA_OK : (int)e;
 }
