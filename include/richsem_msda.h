@@ -220,7 +220,9 @@ int msda_backward_cpu(const void *value, const int64_t *spatial_shapes, const in
  * kernels accumulate grad_value with atomics, they do so in an fp32 scratch buffer owned by the
  * library (one per device and stream, allocated on first use -- not while the stream is being
  * captured -- and reused); decoder-shaped calls need no scratch.
- * value / out / grad_out / grad_value must be 8-byte aligned for the fast paths (2 bytes minimum). */
+ * value / out / grad_out / grad_value must be 8-byte aligned for the fast paths (2 bytes minimum).
+ * Kernels are selected by the code that serves the f32 / f64 entry points; where bf16 storage is treated differently is listed
+ * in one place, the comment block "kernel selection" of csrc/msda_api.hip. */
 int msda_forward_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
                       const float *sampling_loc, const float *attn_weight,
                       int N, int S, int M, int D, int L, int Lq, int P, int im2col_step,

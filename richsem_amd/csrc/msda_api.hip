@@ -54,11 +54,16 @@ extern "C" __attribute__((visibility("hidden"))) int msda_note_error(int code, c
 
 namespace {
 
-int hip_fail(hipError_t e, const char *what)
+int hip_fail(hipError_t e, const char *what, const char *tag = "")
 {
-    snprintf(g_err, sizeof(g_err), "%s: %s (hipError %d)", what, hipGetErrorString(e), (int)e);
+    snprintf(g_err, sizeof(g_err), "%s%s: %s (hipError %d)", what, tag, hipGetErrorString(e), (int)e);
     return (int)e;
 }
+
+struct Problem {
+    int N, S, M, D, L, Lq, P;
+    std::vector<int64_t> shapes, lsi;  // host mirrors
+};
 
 std::atomic<int> g_fwd_variant{0}, g_bwd_variant{0}, g_bwd_cpl{0}, g_levelsum{1}, g_fwd_prep_fused{1}, g_bwd_split{1};
 thread_local int g_tl_fwd_variant = -1;      // >= 0: the forward variant of THIS call (set by a caller inside the library that has already chosen)
@@ -78,9 +83,7 @@ std::atomic<int> g_prof_filter{0};      // 0: every call is bracketed; else only
 struct ProfileScope {
     ProfileSlot *slot = nullptr;
     hipStream_t stream;
-    ProfileScope(int kind, int variant, int dtype_bytes, int N, int S, int M, int D, int L, int Lq, int P,
-                 hipStream_t st)
-        : stream(st)
+    ProfileScope(int kind, int variant, int dtype_bytes, const Problem &pb, hipStream_t st) : stream(st)
     {
         if (!g_prof_on.load(std::memory_order_relaxed)) return;
         // (an event pair is two more packets on the stream -- ~4 us of a call's time on MI355X: a caller that times a whole step brackets
@@ -90,7 +93,7 @@ struct ProfileScope {
         std::lock_guard<std::mutex> lock(g_prof_mutex);
         if (g_prof_used >= (int)g_prof_slots.size()) return;
         slot = &g_prof_slots[g_prof_used++];
-        slot->rec = msda_profile_record{kind, variant, dtype_bytes, N, S, M, D, L, Lq, P, 0.f};
+        slot->rec = msda_profile_record{kind, variant, dtype_bytes, pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, 0.f};
         (void)hipEventRecord(slot->start, stream);
     }
     // the call turned out not to run this variant: give the slot back (only the newest slot can be returned)
@@ -242,10 +245,38 @@ void monitor_finish_probe(Monitor *mo, double points, hipStream_t stream, bool l
     mo->mu.unlock();
 }
 
-struct Problem {
-    int N, S, M, D, L, Lq, P;
-    std::vector<int64_t> shapes, lsi;  // host mirrors
+// The forward variant a call runs where a window kernel applies: what was asked for, or in automatic mode (0) the monitor's choice
+// together with the probe the window kernel is to count into.
+struct FwdChoice {
+    int variant;
+    Monitor *mo = nullptr;
+    unsigned *probe = nullptr;
 };
+FwdChoice choose_window_fwd(int asked, const Problem &pb, const void *loc, hipStream_t stream)
+{
+    FwdChoice ch{asked};
+    if (asked == 0) {
+        ch.mo = monitor_for_current_device();
+        ch.variant = monitor_choose_fwd(ch.mo, problem_key(pb.N, pb.S, pb.M, pb.L, pb.P, pb.shapes.data(), loc), stream, &ch.probe);
+    }
+    return ch;
+}
+
+// One launch of a window forward kernel (profile variant 2; 6 with the location / softmax arithmetic fused in): bracket it, launch,
+// hand the probe back to the monitor, map the error.  launch(probe) returns the hipError_t of the launch.
+template <typename Launch>
+int run_window_fwd(const FwdChoice &ch, int prof_variant, int dtype_bytes, const Problem &pb, hipStream_t stream, const char *what,
+                   const char *tag, Launch launch)
+{
+    hipError_t e;
+    {
+        ProfileScope prof(0, prof_variant, dtype_bytes, pb, stream);
+        e = launch(ch.probe);
+    }
+    if (ch.probe) monitor_finish_probe(ch.mo, 2.0 * pb.N * pb.Lq * pb.M * pb.L * pb.P, stream, e == hipSuccess);
+    if (e != hipSuccess) return hip_fail(e, what, tag);
+    return MSDA_OK;
+}
 
 bool is_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
@@ -303,19 +334,22 @@ int floor_log2(int x)
     return r;
 }
 
-// Channels per lane for the direct kernels: the widest access (<= 16 B) that D and every data
+// Channels per lane for the direct kernels: the widest access of at most max_channels elements of TV that D and every data
 // pointer allow.
-template <typename T>
-int pick_channels_per_lane(int D, std::initializer_list<const void *> ptrs)
+template <typename TV>
+int pick_channels(int D, int max_channels, std::initializer_list<const void *> ptrs)
 {
-    int c = (int)(16 / sizeof(T));
+    int c = max_channels;
     for (; c > 1; c >>= 1) {
         bool ok = D % c == 0;
-        for (const void *p : ptrs) ok = ok && is_aligned(p, sizeof(T) * c);
+        for (const void *p : ptrs) ok = ok && is_aligned(p, sizeof(TV) * c);
         if (ok) break;
     }
     return c;
 }
+// the direct kernels' widest: 16 B of f32 / f64, four channels (8 B) of bf16
+template <typename TV>
+constexpr int kMaxChannels = sizeof(TV) == 8 ? 2 : 4;
 
 msda::DirectGeom direct_geom(const Problem &pb, int C)
 {
@@ -341,52 +375,40 @@ msda::DirectGeom direct_geom(const Problem &pb, int C)
     return g;
 }
 
-// fp32 only: whole-level LDS sums of grad_value (msda_levelsum.h); `taken` = bit mask of the levels it produced
-template <typename T>
-hipError_t launch_levelsum(const Problem &, const T *, const T *, const T *, T *, hipStream_t, unsigned &taken)
-{
-    taken = 0;
-    return hipSuccess;
-}
-template <>
-hipError_t launch_levelsum<float>(const Problem &pb, const float *loc, const float *aw, const float *grad_out,
-                                  float *grad_value, hipStream_t stream, unsigned &taken)
-{
-    msda::LevelSumGeom lg;
-    size_t lds = 0;
-    taken = msda::plan_levelsum(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data(), lg, lds);
-    if (!taken) return hipSuccess;
-    // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
-    // for element alignment only)
-    const bool vec = pb.P == 4 && is_aligned(loc, 16) && is_aligned(aw, 16);
-    lg.dbg = msda::tiled_options().dbg & 7;
-    auto kern = vec ? &msda::bwd_levelsum_kernel<true> : &msda::bwd_levelsum_kernel<false>;
-    hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(msda::levelsum_grid(lg)), dim3(msda::kLsThreads), lds, stream, loc, aw, grad_out, grad_value,
-                       lg);
-    return hipGetLastError();
-}
-
-// the levels launch_levelsum would take for this problem (host-only)
-template <typename T>
-unsigned levelsum_levels(const Problem &)
-{
-    return 0;
-}
-template <>
-unsigned levelsum_levels<float>(const Problem &pb)
-{
-    msda::LevelSumGeom lg;
-    size_t lds = 0;
-    return msda::plan_levelsum(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data(), lg, lds);
-}
-
 int direct_grid(const msda::DirectGeom &g)
 {
     const int pairs = g.N * g.M;
     return msda::kXcds * ((pairs + msda::kXcds - 1) / msda::kXcds) * g.ntiles;
 }
+
+// bit mask of all L levels
+inline unsigned all_levels_mask(int L) { return L >= 32 ? ~0u : (1u << L) - 1; }
+
+// do the levels tile [0, S) in order, without gap or overlap?  (check_problem only bounds them)
+bool levels_tile(const Problem &pb)
+{
+    bool tile = true;
+    for (int64_t l = 0, pre = 0; l < pb.L; ++l) {
+        tile = tile && pb.lsi[l] == pre;
+        pre += pb.shapes[2 * l] * pb.shapes[2 * l + 1];
+    }
+    return tile;
+}
+
+// The direct kernels (msda_direct.h) are instantiated with 1, 2 and -- for 4-byte compute types -- 4 channels per lane: calls
+// launch(std::integral_constant<int, CC>) for the C picked (pick_channels never gives an 8-byte type more than 2).
+template <typename T, typename Launch>
+void with_channels(int C, Launch launch)
+{
+    switch (C) {
+        case 4: launch(std::integral_constant<int, (sizeof(T) == 4 ? 4 : 2)>{}); break;
+        case 2: launch(std::integral_constant<int, 2>{}); break;
+        default: launch(std::integral_constant<int, 1>{}); break;
+    }
+}
+
+// large calls: more waves per SIMD, shallower per-wave pipeline (see fwd_direct_kernel)
+inline bool many_items(const Problem &pb) { return (int64_t)pb.N * pb.Lq * pb.M >= 65536; }
 
 // ---- library-owned device memory, per (device, stream): calls on one stream are ordered, so they can share it; calls on
 // different streams cannot.  Nothing is allocated while the stream is being captured.
@@ -578,30 +600,6 @@ hipError_t launch_bwd_band(const Problem &pb, const TV *value, const float *loc,
     return hipGetLastError();
 }
 
-template <typename T>
-hipError_t try_bwd_band(const Problem &, const T *, const T *, const T *, const T *, T *, T *, T *, hipStream_t)
-{
-    return hipErrorNotSupported;
-}
-template <>
-hipError_t try_bwd_band<float>(const Problem &pb, const float *value, const float *loc, const float *aw, const float *grad_out,
-                               float *grad_value, float *grad_loc, float *grad_aw, hipStream_t stream)
-{
-    return launch_bwd_band<float>(pb, value, loc, aw, grad_out, grad_value, grad_value, grad_loc, grad_aw, stream);
-}
-
-template <typename T>
-hipError_t try_bwd_rps(const Problem &, const T *, const T *, const T *, const T *, T *, T *, T *, hipStream_t)
-{
-    return hipErrorNotSupported;
-}
-template <>
-hipError_t try_bwd_rps<float>(const Problem &pb, const float *value, const float *loc, const float *aw, const float *grad_out,
-                              float *grad_value, float *grad_loc, float *grad_aw, hipStream_t stream)
-{
-    return launch_bwd_rps<float>(pb, value, loc, aw, grad_out, grad_value, grad_value, grad_loc, grad_aw, stream);
-}
-
 // The split kernels (msda_direct.h: fwd_split_kernel / bwd_split_kernel) apply at D = 32 with 16-byte (fp32) / 8-byte (bf16) rows, L*P a
 // multiple of 4 up to 32; they are the automatic choice for calls of fewer than 65536 (query, head) items.
 inline bool split_fits(const Problem &pb, int C) { return pb.D == 32 && C == 4 && (pb.L * pb.P) % msda::kSplitGroups == 0 && pb.L * pb.P / msda::kSplitGroups <= msda::kSplitMaxPts; }
@@ -634,169 +632,7 @@ hipError_t launch_bwd_split(const Problem &pb, const TV *value, const int64_t *s
     return hipGetLastError();
 }
 
-template <typename T>
-int forward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, const T *loc, const T *aw, int N, int S,
-                 int M, int D, int L, int Lq, int P, int im2col_step, T *out, const int64_t *shapes_host,
-                 const int64_t *lsi_host, msda_stream_t stream_)
-{
-    g_err[0] = 0;
-    if (!value || !shapes || !lsi || !loc || !aw || !out) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Problem pb{N, S, M, D, L, Lq, P, {}, {}};
-    if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, sizeof(T)) || !is_aligned(out, sizeof(T)) || !is_aligned(aw, sizeof(T)) ||
-        !is_aligned(loc, 2 * sizeof(T)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs 2*sizeof(T))");
-
-    int variant = g_tl_fwd_variant >= 0 ? g_tl_fwd_variant : g_fwd_variant.load();
-    if (variant != 1 && msda::tiled_fwd_applicable<T>(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(),
-                                                     pb.lsi.data(), value, out)) {
-        unsigned *probe = nullptr;
-        Monitor *mo = nullptr;
-        if (variant == 0) {   // automatic: follow the locality monitor
-            mo = monitor_for_current_device();
-            variant = monitor_choose_fwd(mo, problem_key(N, S, M, L, P, pb.shapes.data(), loc), stream, &probe);
-        }
-        if (variant == 2) {
-            hipError_t e;
-            {
-                ProfileScope prof(0, 2, (int)sizeof(T), N, S, M, D, L, Lq, P, stream);
-                e = msda::launch_fwd_tiled<T>(value, shapes, lsi, loc, aw, out, pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P,
-                                              pb.shapes.data(), pb.lsi.data(), probe, stream);
-            }
-            if (probe) monitor_finish_probe(mo, 2.0 * N * Lq * M * L * P, stream, e == hipSuccess);
-            if (e != hipSuccess) return hip_fail(e, "launch of the tiled forward kernel");
-            return MSDA_OK;
-        }
-    }
-
-    const int C = pick_channels_per_lane<T>(D, {value, out});
-    msda::DirectGeom g = direct_geom(pb, C);
-    g.head_major = (msda::tiled_options().dbg & 128) ? 1 : 0;      // (measured experiment: value read as (N, M, S, D))
-    // small fp32 calls at D = 32 (decoder-shaped): 32 lanes per item, all of a lane's gathers in flight at once (fwd_split_kernel);
-    // fwd_variant 3 forces it wherever it applies, 1 keeps the 8-lane kernel
-    if constexpr (std::is_same<T, float>::value) {
-        if (split_fits(pb, C) && !g.head_major && (variant == 3 || (variant != 1 && split_small(pb)))) {
-            ProfileScope prof(0, 3, (int)sizeof(T), N, S, M, D, L, Lq, P, stream);
-            const hipError_t e = launch_fwd_split<float>(pb, value, shapes, lsi, loc, aw, out, g, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch of the split forward kernel");
-            return MSDA_OK;
-        }
-    }
-    const size_t lds = msda::direct_lds_bytes<T>(g);
-    if (lds > 64 * 1024) return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L);
-    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
-    ProfileScope prof(0, 1, (int)sizeof(T), N, S, M, D, L, Lq, P, stream);
-    // large calls: more waves per SIMD, shallower per-wave pipeline (see fwd_direct_kernel)
-    const bool many = (int64_t)N * Lq * M >= 65536;
-#define MSDA_LAUNCH_FWD(CC)                                                                                              \
-    if (many) hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 6>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g); \
-    else hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 4>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g)
-    switch (C) {
-        case 4: MSDA_LAUNCH_FWD((sizeof(T) == 4 ? 4 : 2)); break;
-        case 2: MSDA_LAUNCH_FWD(2); break;
-        default: MSDA_LAUNCH_FWD(1); break;
-    }
-#undef MSDA_LAUNCH_FWD
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the direct forward kernel");
-    return MSDA_OK;
-}
-
-template <typename T>
-int backward_impl(const T *value, const int64_t *shapes, const int64_t *lsi, const T *loc, const T *aw,
-                  const T *grad_out, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step, T *grad_value,
-                  T *grad_loc, T *grad_aw, const int64_t *shapes_host, const int64_t *lsi_host, msda_stream_t stream_)
-{
-    g_err[0] = 0;
-    if (!value || !shapes || !lsi || !loc || !aw || !grad_out || !grad_value || !grad_loc || !grad_aw)
-        return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Problem pb{N, S, M, D, L, Lq, P, {}, {}};
-    if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, sizeof(T)) || !is_aligned(grad_out, sizeof(T)) || !is_aligned(aw, sizeof(T)) ||
-        !is_aligned(grad_value, sizeof(T)) || !is_aligned(grad_aw, sizeof(T)) || !is_aligned(loc, 2 * sizeof(T)) ||
-        !is_aligned(grad_loc, 2 * sizeof(T)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc / grad_sampling_loc need 2*sizeof(T))");
-
-    // grad_value is accumulated into (the reference gets it from at::zeros_like, ms_deform_attn_cuda.cu:121)
-    hipError_t e = hipSuccess;
-    auto zero_grad_value = [&]() { return hipMemsetAsync(grad_value, 0, sizeof(T) * (size_t)N * S * M * D, stream); };
-
-    // Kernel choice: the routed pixel-stationary kernels (msda_rps.h: no float atomics, no zero-fill, cost independent of where
-    // the points fall) for encoder-shaped fp32 calls at D = 32 (bwd_variant 4 forces them for any Lq, 1 forces the direct path);
-    // everything else -- other D, f64, decoder shapes -- runs the level-sum + direct kernels below.
-    const int variant = g_bwd_variant.load();
-    if (variant == 4 || (variant == 0 && Lq == S)) {
-        ProfileScope prof(1, 4, (int)sizeof(T), N, S, M, D, L, Lq, P, stream);
-        e = try_bwd_rps<T>(pb, value, loc, aw, grad_out, grad_value, grad_loc, grad_aw, stream);
-        if (e == hipSuccess) return MSDA_OK;
-        prof.cancel();
-        if (e != hipErrorNotSupported) return hip_fail(e, "launch of the routed backward kernels");
-        e = hipSuccess;
-    }
-
-    // bwd_variant 5: the row-band kernel (msda_band.h) -- grad_value, grad_sampling_loc and grad_attn_weight in ONE launch, no zero-fill of
-    // grad_value.  A measured option, not the automatic choice: 101-123 us on the decoder call Dd against 88 us for the level-sum + direct
-    // kernels below (profiles/r05_dd_backward.md).
-    if (variant == 5) {
-        ProfileScope prof(1, 5, (int)sizeof(T), N, S, M, D, L, Lq, P, stream);
-        e = try_bwd_band<T>(pb, value, loc, aw, grad_out, grad_value, grad_loc, grad_aw, stream);
-        if (e == hipSuccess) return MSDA_OK;
-        prof.cancel();
-        if (e != hipErrorNotSupported) return hip_fail(e, "launch of the row-band backward kernel");
-        e = hipSuccess;
-    }
-
-    // Levels summed in LDS by their own kernel (msda_levelsum.h) are taken away from the atomics below; when that is ALL
-    // levels (decoder-shaped calls) grad_value is written, not accumulated: no zero-fill, no atomics.
-    unsigned ls_levels = 0;
-    const unsigned all_levels = L >= 32 ? ~0u : (1u << L) - 1;
-    // (its plain per-level stores need the levels to tile [0, S) without overlap; check_problem only bounds them)
-    bool levels_tile = true;
-    for (int64_t l = 0, pre = 0; l < L; ++l) {
-        levels_tile = levels_tile && pb.lsi[l] == pre;
-        pre += pb.shapes[2 * l] * pb.shapes[2 * l + 1];
-    }
-    if (g_levelsum.load() && levels_tile) ls_levels = levelsum_levels<T>(pb);
-    if (ls_levels != all_levels && (e = zero_grad_value()) != hipSuccess) return hip_fail(e, "zero-fill of grad_value");
-    // Float atomics run at full rate only as >= 128-B row segments (one dword per lane): with 32 or more
-    // channels put ONE channel on a lane, so that a wave-instruction adds two whole 128-B rows.
-    int C = pick_channels_per_lane<T>(D, {value, grad_out});
-    if (g_bwd_cpl.load() > 0) C = g_bwd_cpl.load() <= C ? g_bwd_cpl.load() : C;
-    else if (D * (int)sizeof(T) >= 128 && ls_levels != all_levels) C = 1;
-    msda::DirectGeom g = direct_geom(pb, C);
-    const size_t lds = msda::direct_lds_bytes<T>(g);
-    if (lds > 64 * 1024) return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L);
-    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
-    ProfileScope prof(1, 1, (int)sizeof(T), N, S, M, D, L, Lq, P, stream);
-    if (ls_levels) {
-        // (forking this kernel onto a second stream beside the direct kernel was tried: the cross-stream fork / join costs
-        // more than the overlap gains on a 90 us call -- 113 vs 96 us)
-        e = launch_levelsum<T>(pb, loc, aw, grad_out, grad_value, stream, g.gv_skip);
-        if (e != hipSuccess) return hip_fail(e, "launch of the level-sum backward kernel");
-    }
-    if constexpr (std::is_same<T, float>::value) {
-        // grad_value is complete: the location / weight gradients of a small call come from the split kernel (bwd_split = 0 keeps the 8-lane one)
-        if (g.gv_skip == all_levels && g_bwd_split.load() && split_fits(pb, C) && split_small(pb)) {
-            e = launch_bwd_split<float>(pb, value, shapes, lsi, loc, aw, grad_out, grad_loc, grad_aw, g, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch of the split backward kernel");
-            return MSDA_OK;
-        }
-    }
-    switch (C) {
-        case 4: hipLaunchKernelGGL((msda::bwd_direct_kernel<T, (sizeof(T) == 4 ? 4 : 2)>), grid, block, lds, stream, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, g); break;
-        case 2: hipLaunchKernelGGL((msda::bwd_direct_kernel<T, 2>), grid, block, lds, stream, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, g); break;
-        default: hipLaunchKernelGGL((msda::bwd_direct_kernel<T, 1>), grid, block, lds, stream, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, g); break;
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the direct backward kernel");
-    return MSDA_OK;
-}
-
-// ---- bf16 storage (value / out / grad_out / grad_value), fp32 compute ----------------------------------------------------------
-// New capability: the reference dispatches float / double only (ms_deform_attn_cuda.cu:64,134).  Sampling locations,
-// attention weights and their gradients stay fp32; every sum is formed in fp32 (or f64 LDS windows) and rounded to bf16 once.
+// ---- bf16 storage (value / out / grad_out / grad_value), fp32 compute: the fp32 scratch image of grad_value and its one rounding -------
 bool bf16_scratch(hipStream_t stream, size_t n_floats, float **out)
 {
     int dev = 0;
@@ -828,182 +664,231 @@ __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restr
         dst[i] = msda::to_storage<msda::bf16_t, float>(src[i]);
 }
 
-int pick_channels_bf16(int D, std::initializer_list<const void *> ptrs)
-{
-    int c = 4;
-    for (; c > 1; c >>= 1) {
-        bool ok = D % c == 0;
-        for (const void *p : ptrs) ok = ok && is_aligned(p, 2 * (size_t)c);
-        if (ok) break;
-    }
-    return c;
-}
+// ---- kernel selection: msda_forward_* / msda_backward_* ------------------------------------------------------------------------------
+// forward_impl / backward_impl serve every element type: T is the type of sampling_loc / attn_weight and their gradients (float or
+// double), TV the storage type of value / out / grad_out / grad_value (T, or msda::bf16_t beside T = float -- a capability the reference
+// does not have: it dispatches float / double only, ms_deform_attn_cuda.cu:64,134; every sum is formed in fp32 or f64 LDS windows and
+// rounded to bf16 once).  The order in which the paths are tried is the same for all; what differs between the instances is listed
+// here and marked kBf16 / is_same<T, float> below.  Each line is today's behaviour; whether it is wanted is a question of its own.
+//
+//                                     f32 / f64 storage                             bf16 storage
+//   pointer alignment demanded        sizeof(T); 2*sizeof(T) for loc / grad_loc     the same rule: 2 B data, 4 B weights, 8 B loc / grad_loc
+//   window forward eligible           f32 only; value, out 16-B aligned; plan ok    value, out 8-B aligned; plan ok  (both: rows of four)
+//   channels per lane                 widest <= 16 B that D and the pointers allow  widest <= 4 channels (8 B)
+//   tile_debug bit 128 (head-major)   honoured; keeps the call off the split kernel ignored
+//   split forward / backward          f32 only                                      yes
+//   "too many levels" (forward)       checked after the split kernel was considered before it  (a call the split kernel takes has L <= 32)
+//   routed / band backward entered    bwd_variant 4, or 0 with Lq == S (band: 5);   the same variants, and only with value / grad_out / grad_value
+//                                     f32 only                                      8-B aligned, D = 32 and the fp32 scratch to be had (band: a
+//                                                                                   scratch only if its plan has atomic levels)
+//   ... a launch error there          the profile record is given back              the profile record stays
+//   level-sum backward                f32: any subset of levels, the rest by        only when it takes ALL levels; else fp32 scratch + zero-fill +
+//                                     atomics after a zero-fill of grad_value;      direct kernel + one rounding pass
+//                                     sets lg.dbg
+//   bwd_direct_cpl option             honoured                                      ignored
+//   direct backward adds grad_value   into grad_value                               into the fp32 scratch (null when level-sum took everything)
+//   no scratch during stream capture  n/a                                           MSDA_ERR_BAD_DIMS
+//   error texts                       as written                                    + " (bf16)"; "... needs 8 bytes"; "LDS limit"
+int too_many_levels(int L) { return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L); }
 
-int forward_bf16_impl(const msda::bf16_t *value, const int64_t *shapes, const int64_t *lsi, const float *loc, const float *aw,
-                      int N, int S, int M, int D, int L, int Lq, int P, int im2col_step, msda::bf16_t *out,
-                      const int64_t *shapes_host, const int64_t *lsi_host, msda_stream_t stream_)
+template <typename T, typename TV = T>
+int forward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, const T *loc, const T *aw, int N, int S,
+                 int M, int D, int L, int Lq, int P, int im2col_step, TV *out, const int64_t *shapes_host,
+                 const int64_t *lsi_host, msda_stream_t stream_)
 {
+    constexpr bool kBf16 = std::is_same<TV, msda::bf16_t>::value;
+    constexpr const char *kTag = kBf16 ? " (bf16)" : "";
     g_err[0] = 0;
     if (!value || !shapes || !lsi || !loc || !aw || !out) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
     if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, 2) || !is_aligned(out, 2) || !is_aligned(aw, 4) || !is_aligned(loc, 8) || !is_aligned(shapes, 8) ||
-        !is_aligned(lsi, 8))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs 8 bytes)");
+    if (!is_aligned(value, sizeof(TV)) || !is_aligned(out, sizeof(TV)) || !is_aligned(aw, sizeof(T)) ||
+        !is_aligned(loc, 2 * sizeof(T)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
+        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs %s)", kBf16 ? "8 bytes" : "2*sizeof(T)");
 
     int variant = g_tl_fwd_variant >= 0 ? g_tl_fwd_variant : g_fwd_variant.load();
-    if (variant != 1 && is_aligned(value, 8) && is_aligned(out, 8) &&
-        msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
-        unsigned *probe = nullptr;
-        Monitor *mo = nullptr;
-        if (variant == 0) {
-            mo = monitor_for_current_device();
-            variant = monitor_choose_fwd(mo, problem_key(N, S, M, L, P, pb.shapes.data(), loc), stream, &probe);
+    if constexpr (std::is_same<T, float>::value) {      // the LDS-window kernel (msda_tiled.h): fp32 compute, rows read four channels at a time
+        if (variant != 1 && is_aligned(value, 4 * sizeof(TV)) && is_aligned(out, 4 * sizeof(TV)) &&
+            msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
+            const FwdChoice ch = choose_window_fwd(variant, pb, loc, stream);      // automatic: follow the locality monitor
+            variant = ch.variant;
+            if (variant == 2)
+                return run_window_fwd(ch, 2, (int)sizeof(TV), pb, stream, "launch of the tiled forward kernel", kTag, [&](unsigned *probe) {
+                    return msda::launch_fwd_tiled_tv<TV>(value, loc, aw, out, N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), probe, stream);
+                });
         }
-        if (variant == 2) {
-            hipError_t e;
-            {
-                ProfileScope prof(0, 2, 2, N, S, M, D, L, Lq, P, stream);
-                e = msda::launch_fwd_tiled_tv<msda::bf16_t>(value, loc, aw, out, N, S, M, D, L, Lq, P, pb.shapes.data(),
-                                                           pb.lsi.data(), probe, stream);
-            }
-            if (probe) monitor_finish_probe(mo, 2.0 * N * Lq * M * L * P, stream, e == hipSuccess);
-            if (e != hipSuccess) return hip_fail(e, "launch of the tiled forward kernel (bf16)");
+    }
+
+    const int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, out});
+    msda::DirectGeom g = direct_geom(pb, C);
+    if constexpr (!kBf16) g.head_major = (msda::tiled_options().dbg & 128) ? 1 : 0;      // (measured experiment: value read as (N, M, S, D))
+    const size_t lds = msda::direct_lds_bytes<T>(g);
+    if (kBf16 && lds > 64 * 1024) return too_many_levels(L);
+    // small calls at D = 32 (decoder-shaped): 32 lanes per item, all of a lane's gathers in flight at once (fwd_split_kernel);
+    // fwd_variant 3 forces it wherever it applies, 1 keeps the 8-lane kernel
+    if constexpr (std::is_same<T, float>::value) {
+        if (split_fits(pb, C) && !g.head_major && (variant == 3 || (variant != 1 && split_small(pb)))) {
+            ProfileScope prof(0, 3, (int)sizeof(TV), pb, stream);
+            const hipError_t e = launch_fwd_split<TV>(pb, value, shapes, lsi, loc, aw, out, g, stream);
+            if (e != hipSuccess) return hip_fail(e, "launch of the split forward kernel", kTag);
             return MSDA_OK;
         }
     }
-    const int C = pick_channels_bf16(D, {value, out});
-    const msda::DirectGeom g = direct_geom(pb, C);
-    const size_t lds = msda::direct_lds_bytes<float>(g);
-    if (lds > 64 * 1024) return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L);
+    if (lds > 64 * 1024) return too_many_levels(L);
     const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
-    if (split_fits(pb, C) && (variant == 3 || (variant != 1 && split_small(pb)))) {
-        ProfileScope prof(0, 3, 2, N, S, M, D, L, Lq, P, stream);
-        const hipError_t e = launch_fwd_split<msda::bf16_t>(pb, value, shapes, lsi, loc, aw, out, g, stream);
-        if (e != hipSuccess) return hip_fail(e, "launch of the split forward kernel (bf16)");
-        return MSDA_OK;
-    }
-    ProfileScope prof(0, 1, 2, N, S, M, D, L, Lq, P, stream);
-    const bool many = (int64_t)N * Lq * M >= 65536;
-#define MSDA_LAUNCH_FWD(CC)                                                                                                          \
-    if (many) hipLaunchKernelGGL((msda::fwd_direct_kernel<float, CC, 6, msda::bf16_t>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g); \
-    else hipLaunchKernelGGL((msda::fwd_direct_kernel<float, CC, 4, msda::bf16_t>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g)
-    switch (C) {
-        case 4: MSDA_LAUNCH_FWD(4); break;
-        case 2: MSDA_LAUNCH_FWD(2); break;
-        default: MSDA_LAUNCH_FWD(1); break;
-    }
-#undef MSDA_LAUNCH_FWD
+    ProfileScope prof(0, 1, (int)sizeof(TV), pb, stream);
+    with_channels<T>(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value;
+        if (many_items(pb)) hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 6, TV>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g);
+        else hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 4, TV>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g);
+    });
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the direct forward kernel (bf16)");
+    if (e != hipSuccess) return hip_fail(e, "launch of the direct forward kernel", kTag);
     return MSDA_OK;
 }
 
-int backward_bf16_impl(const msda::bf16_t *value, const int64_t *shapes, const int64_t *lsi, const float *loc, const float *aw,
-                       const msda::bf16_t *grad_out, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step,
-                       msda::bf16_t *grad_value, float *grad_loc, float *grad_aw, const int64_t *shapes_host,
-                       const int64_t *lsi_host, msda_stream_t stream_)
+// One attempt at a backward kernel that may answer hipErrorNotSupported -- its plan does not apply, or no workspace can be had right
+// now --, upon which the call goes on to the next path: returns kNextPath then, else the call's return code.
+constexpr int kNextPath = 1 << 30;
+template <typename Launch>
+int try_bwd(int prof_variant, int dtype_bytes, bool cancel_on_error, const Problem &pb, hipStream_t stream, const char *what,
+            const char *tag, Launch launch)
 {
+    hipError_t e;
+    {
+        ProfileScope prof(1, prof_variant, dtype_bytes, pb, stream);
+        e = launch();
+        if (e == hipErrorNotSupported || (cancel_on_error && e != hipSuccess)) prof.cancel();
+    }
+    if (e == hipSuccess) return MSDA_OK;
+    return e == hipErrorNotSupported ? kNextPath : hip_fail(e, what, tag);
+}
+
+template <typename T, typename TV = T>
+int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, const T *loc, const T *aw,
+                  const TV *grad_out, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step, TV *grad_value,
+                  T *grad_loc, T *grad_aw, const int64_t *shapes_host, const int64_t *lsi_host, msda_stream_t stream_)
+{
+    constexpr bool kBf16 = std::is_same<TV, msda::bf16_t>::value;
+    constexpr const char *kTag = kBf16 ? " (bf16)" : "";
     g_err[0] = 0;
     if (!value || !shapes || !lsi || !loc || !aw || !grad_out || !grad_value || !grad_loc || !grad_aw)
         return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
     if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, 2) || !is_aligned(grad_out, 2) || !is_aligned(grad_value, 2) || !is_aligned(aw, 4) ||
-        !is_aligned(grad_aw, 4) || !is_aligned(loc, 8) || !is_aligned(grad_loc, 8) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc / grad_sampling_loc need 8 bytes)");
+    if (!is_aligned(value, sizeof(TV)) || !is_aligned(grad_out, sizeof(TV)) || !is_aligned(grad_value, sizeof(TV)) ||
+        !is_aligned(aw, sizeof(T)) || !is_aligned(grad_aw, sizeof(T)) || !is_aligned(loc, 2 * sizeof(T)) ||
+        !is_aligned(grad_loc, 2 * sizeof(T)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
+        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc / grad_sampling_loc need %s)", kBf16 ? "8 bytes" : "2*sizeof(T)");
     const size_t n_value = (size_t)N * S * M * D;
     hipError_t e = hipSuccess;
-    auto finish_from_scratch = [&](float *gv32) {   // one rounding of the fp32 sums
-        const size_t n4 = is_aligned(grad_value, 8) ? n_value / 4 : 0;
-        hipLaunchKernelGGL(round_to_bf16_kernel, dim3(2048), dim3(256), 0, stream, gv32, grad_value, n4, n_value);
-        return hipGetLastError();
-    };
 
-    int variant = g_bwd_variant.load();
-    if (variant != 1 && is_aligned(value, 8) && is_aligned(grad_out, 8) && is_aligned(grad_value, 8)) {
-        // automatic: encoder-shaped calls take the routed kernels (as in fp32; the rows they request per point are half as wide);
-        // (5: the row-band kernel, a measured option -- see backward_impl)
+    // Kernel choice: the routed pixel-stationary kernels (msda_rps.h: no float atomics, no zero-fill, cost independent of where
+    // the points fall) for encoder-shaped fp32-compute calls at D = 32 (bwd_variant 4 forces them for any Lq, 1 forces the direct
+    // path); everything else -- other D, f64, decoder shapes -- runs the level-sum + direct kernels below.
+    // bwd_variant 5: the row-band kernel (msda_band.h) -- grad_value, grad_sampling_loc and grad_attn_weight in ONE launch, no zero-fill of
+    // grad_value.  A measured option, not the automatic choice: 101-123 us on the decoder call Dd against 88 us for the level-sum + direct
+    // kernels below (profiles/r05_dd_backward.md).
+    // Both take grad_value twice: the tensor, and an fp32 image for the levels several workgroups add to -- grad_value itself, or for bf16
+    // the library's scratch (zeroed by the kernels, rounded once at the end); plain bf16 stores serve the levels a workgroup owns alone.
+    if constexpr (std::is_same<T, float>::value) {
+        int variant = g_bwd_variant.load();
         if (variant == 0) variant = Lq == S ? 4 : 1;
-        float *gv32 = nullptr;
-        if (variant == 5 && D == msda::kBandD) {
-            const msda::BandPlan bp = msda::plan_band(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data());
-            if (bp.ok && (!bp.atomic_levels || bf16_scratch(stream, n_value, &gv32))) {
-                {
-                    ProfileScope prof(1, 5, 2, N, S, M, D, L, Lq, P, stream);
-                    e = launch_bwd_band<msda::bf16_t>(pb, value, loc, aw, grad_out, grad_value, gv32, grad_loc, grad_aw, stream);
-                    if (e == hipErrorNotSupported) prof.cancel();
-                }
-                if (e == hipSuccess) return MSDA_OK;
-                if (e != hipErrorNotSupported) return hip_fail(e, "launch of the row-band backward kernel (bf16)");
-            }
-            gv32 = nullptr;
+        const bool rows = !kBf16 || (is_aligned(value, 8) && is_aligned(grad_out, 8) && is_aligned(grad_value, 8));
+        float *acc = nullptr;
+        if constexpr (!kBf16) acc = grad_value;
+        if (variant == 4 && rows && (!kBf16 || (D == msda::kRpsD && bf16_scratch(stream, n_value, &acc)))) {
+            const int rc = try_bwd(4, (int)sizeof(TV), !kBf16, pb, stream, "launch of the routed backward kernels", kTag, [&]() {
+                return launch_bwd_rps<TV>(pb, value, loc, aw, grad_out, grad_value, acc, grad_loc, grad_aw, stream);
+            });
+            if (rc != kNextPath) return rc;
         }
-        if (variant == 4 && D == msda::kRpsD && bf16_scratch(stream, n_value, &gv32)) {
-            // routed kernels: plain bf16 stores for the levels a workgroup owns alone; the levels shared by several workgroups are
-            // accumulated in the fp32 scratch (zeroed by the route pass) and rounded once
-            {
-                ProfileScope prof(1, 4, 2, N, S, M, D, L, Lq, P, stream);
-                e = launch_bwd_rps<msda::bf16_t>(pb, value, loc, aw, grad_out, grad_value, gv32, grad_loc, grad_aw, stream);
-                if (e == hipErrorNotSupported) prof.cancel();
+        if (variant == 5 && rows && (!kBf16 || D == msda::kBandD)) {
+            bool go = true;
+            if constexpr (kBf16) {
+                const msda::BandPlan bp = msda::plan_band(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data());
+                go = bp.ok && (!bp.atomic_levels || bf16_scratch(stream, n_value, &acc));
             }
-            if (e == hipSuccess) return MSDA_OK;
-            if (e != hipErrorNotSupported) return hip_fail(e, "launch of the routed backward kernels (bf16)");
+            if (go) {
+                const int rc = try_bwd(5, (int)sizeof(TV), !kBf16, pb, stream, "launch of the row-band backward kernel", kTag, [&]() {
+                    return launch_bwd_band<TV>(pb, value, loc, aw, grad_out, grad_value, acc, grad_loc, grad_aw, stream);
+                });
+                if (rc != kNextPath) return rc;
+            }
         }
     }
 
-    // direct path.  All levels summed in f64 LDS windows (msda_levelsum.h) when the plan allows: no atomics, no scratch,
-    // the window is rounded to bf16 at its one store.  Otherwise every corner goes to an fp32 scratch buffer with row atomics.
-    bool levels_tile = true;
-    for (int64_t l = 0, pre = 0; l < L; ++l) {
-        levels_tile = levels_tile && pb.lsi[l] == pre;
-        pre += pb.shapes[2 * l] * pb.shapes[2 * l + 1];
-    }
-    const unsigned all_levels = L >= 32 ? ~0u : (1u << L) - 1;
+    // Direct path.  Levels summed in f64 LDS windows by their own kernel (msda_levelsum.h; fp32 compute only) are taken away from the
+    // atomics below; when that is ALL levels (decoder-shaped calls) grad_value is written, not accumulated: no zero-fill, no atomics, and
+    // for bf16 no scratch (the window is rounded at its one store).  bf16 takes all levels or none: otherwise every corner goes to the
+    // fp32 scratch with row atomics.
+    const unsigned all_levels = all_levels_mask(L);
+    unsigned ls_levels = 0;
     msda::LevelSumGeom lg;
     size_t ls_lds = 0;
-    unsigned ls_levels = 0;
-    if (g_levelsum.load() && levels_tile)
-        ls_levels = msda::plan_levelsum(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), lg, ls_lds);
-    const bool by_levelsum = ls_levels == all_levels;
-    float *gv32 = nullptr;
-    if (!by_levelsum) {
-        if (!bf16_scratch(stream, n_value, &gv32))
-            return fail(MSDA_ERR_BAD_DIMS, "bf16 backward of this shape needs an fp32 scratch buffer, which cannot be allocated "
-                                           "while the stream is being captured: run the call once outside the capture");
-        if ((e = hipMemsetAsync(gv32, 0, sizeof(float) * n_value, stream)) != hipSuccess) return hip_fail(e, "zero-fill of the fp32 scratch");
+    if constexpr (std::is_same<T, float>::value) {
+        // (its plain per-level stores need the levels to tile [0, S) without overlap; check_problem only bounds them)
+        if (g_levelsum.load() && levels_tile(pb))
+            ls_levels = msda::plan_levelsum(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), lg, ls_lds);
+        if (kBf16 && ls_levels != all_levels) ls_levels = 0;
     }
-    int C = pick_channels_bf16(D, {value, grad_out});
-    if (!by_levelsum && D * 4 >= 128) C = 1;   // row atomics: one channel per lane (see backward_impl)
+    // what the direct kernel accumulates grad_value into (the reference gets it from at::zeros_like, ms_deform_attn_cuda.cu:121)
+    T *acc = nullptr;
+    if constexpr (!kBf16) acc = grad_value;
+    if (ls_levels != all_levels) {
+        if constexpr (kBf16) {
+            if (!bf16_scratch(stream, n_value, &acc))
+                return fail(MSDA_ERR_BAD_DIMS, "bf16 backward of this shape needs an fp32 scratch buffer, which cannot be allocated "
+                                               "while the stream is being captured: run the call once outside the capture");
+        }
+        if ((e = hipMemsetAsync(acc, 0, sizeof(T) * n_value, stream)) != hipSuccess)
+            return hip_fail(e, kBf16 ? "zero-fill of the fp32 scratch" : "zero-fill of grad_value");
+    }
+    // Float atomics run at full rate only as >= 128-B row segments (one dword per lane): with 32 or more
+    // channels put ONE channel on a lane, so that a wave-instruction adds two whole 128-B rows.
+    int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, grad_out});
+    const int cpl = kBf16 ? 0 : g_bwd_cpl.load();
+    if (cpl > 0) C = cpl <= C ? cpl : C;
+    else if (D * (int)sizeof(T) >= 128 && ls_levels != all_levels) C = 1;
     msda::DirectGeom g = direct_geom(pb, C);
-    const size_t lds = msda::direct_lds_bytes<float>(g);
-    if (lds > 64 * 1024) return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L);
-    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
-    ProfileScope prof(1, 1, 2, N, S, M, D, L, Lq, P, stream);
-    if (by_levelsum) {
-        const bool vec = P == 4 && is_aligned(loc, 16) && is_aligned(aw, 16);
-        auto kern = vec ? &msda::bwd_levelsum_kernel<true, msda::bf16_t> : &msda::bwd_levelsum_kernel<false, msda::bf16_t>;
-        if ((e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), ls_lds)) != hipSuccess) return hip_fail(e, "LDS limit");
-        hipLaunchKernelGGL(kern, dim3(msda::levelsum_grid(lg)), dim3(msda::kLsThreads), ls_lds, stream, loc, aw, grad_out, grad_value, lg);
-        if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the level-sum backward kernel (bf16)");
-        g.gv_skip = all_levels;
-        if (g_bwd_split.load() && split_fits(pb, C) && split_small(pb)) {
-            e = launch_bwd_split<msda::bf16_t>(pb, value, shapes, lsi, loc, aw, grad_out, grad_loc, grad_aw, g, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch of the split backward kernel (bf16)");
+    const size_t lds = msda::direct_lds_bytes<T>(g);
+    if (lds > 64 * 1024) return too_many_levels(L);
+    ProfileScope prof(1, 1, (int)sizeof(TV), pb, stream);
+    if constexpr (std::is_same<T, float>::value) {
+        // (forking the level-sum kernel onto a second stream beside the direct kernel was tried: the cross-stream fork / join costs
+        // more than the overlap gains on a 90 us call -- 113 vs 96 us)
+        if (ls_levels) {
+            // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
+            // for element alignment only)
+            const bool vec = P == 4 && is_aligned(loc, 16) && is_aligned(aw, 16);
+            if constexpr (!kBf16) lg.dbg = msda::tiled_options().dbg & 7;
+            auto kern = vec ? &msda::bwd_levelsum_kernel<true, TV> : &msda::bwd_levelsum_kernel<false, TV>;
+            if ((e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), ls_lds)) != hipSuccess)
+                return hip_fail(e, kBf16 ? "LDS limit" : "launch of the level-sum backward kernel");
+            hipLaunchKernelGGL(kern, dim3(msda::levelsum_grid(lg)), dim3(msda::kLsThreads), ls_lds, stream, loc, aw, grad_out, grad_value, lg);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the level-sum backward kernel", kTag);
+            g.gv_skip = ls_levels;
+        }
+        // grad_value is complete: the location / weight gradients of a small call come from the split kernel (bwd_split = 0 keeps the 8-lane one)
+        if (g.gv_skip == all_levels && g_bwd_split.load() && split_fits(pb, C) && split_small(pb)) {
+            e = launch_bwd_split<TV>(pb, value, shapes, lsi, loc, aw, grad_out, grad_loc, grad_aw, g, stream);
+            if (e != hipSuccess) return hip_fail(e, "launch of the split backward kernel", kTag);
             return MSDA_OK;
         }
     }
-    switch (C) {
-        case 4: hipLaunchKernelGGL((msda::bwd_direct_kernel<float, 4, msda::bf16_t>), grid, block, lds, stream, value, shapes, lsi, loc, aw, grad_out, gv32, grad_loc, grad_aw, g); break;
-        case 2: hipLaunchKernelGGL((msda::bwd_direct_kernel<float, 2, msda::bf16_t>), grid, block, lds, stream, value, shapes, lsi, loc, aw, grad_out, gv32, grad_loc, grad_aw, g); break;
-        default: hipLaunchKernelGGL((msda::bwd_direct_kernel<float, 1, msda::bf16_t>), grid, block, lds, stream, value, shapes, lsi, loc, aw, grad_out, gv32, grad_loc, grad_aw, g); break;
-    }
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the direct backward kernel (bf16)");
-    if (!by_levelsum) {
-        e = finish_from_scratch(gv32);
-        if (e != hipSuccess) return hip_fail(e, "rounding grad_value to bf16");
+    with_channels<T>(C, [&](auto cc) {
+        hipLaunchKernelGGL((msda::bwd_direct_kernel<T, decltype(cc)::value, TV>), dim3(direct_grid(g)), dim3(msda::kDirectThreads), lds, stream,
+                           value, shapes, lsi, loc, aw, grad_out, acc, grad_loc, grad_aw, g);
+    });
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the direct backward kernel", kTag);
+    if constexpr (kBf16) {
+        if (ls_levels != all_levels) {      // one rounding of the fp32 sums
+            const size_t n4 = is_aligned(grad_value, 8) ? n_value / 4 : 0;
+            hipLaunchKernelGGL(round_to_bf16_kernel, dim3(2048), dim3(256), 0, stream, acc, grad_value, n4, n_value);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "rounding grad_value to bf16");
+        }
     }
     return MSDA_OK;
 }
@@ -1134,33 +1019,19 @@ int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi
             const bool aligned = is_aligned(value, row_align) && is_aligned(out, row_align) && is_aligned(offsets, 2 * sizeof(TP)) && off_stride % 2 == 0 &&
                                  is_aligned(logits, sizeof(TP)) && is_aligned(ref, 8) && is_aligned(loc, 8) && is_aligned(aw, 4);
             if (aligned && msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
-                int variant = g_fwd_variant.load();
-                unsigned *probe = nullptr;
-                Monitor *mo = nullptr;
-                if (variant == 0) {
-                    mo = monitor_for_current_device();
-                    variant = monitor_choose_fwd(mo, problem_key(N, S, M, L, P, pb.shapes.data(), loc), stream, &probe);
-                }
-                if (variant == 2) {
+                const FwdChoice ch = choose_window_fwd(g_fwd_variant.load(), pb, loc, stream);
+                if (ch.variant == 2) {
                     const msda::TiledPrepSrc src{offsets, logits, (long long)off_stride, (long long)log_stride, ref, ref_dim, loc, aw};
-                    hipError_t e;
-                    {
-                        ProfileScope prof(0, 6, (int)sizeof(TV), N, S, M, D, L, Lq, P, stream);
-                        e = msda::launch_fwd_tiled_prep<TV, TP>(value, src, out, N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), probe, stream);
-                    }
-                    if (probe) monitor_finish_probe(mo, 2.0 * N * Lq * M * L * P, stream, e == hipSuccess);
-                    if (e != hipSuccess) return hip_fail(e, "launch of the fused location / softmax / window-gather kernel");
-                    return MSDA_OK;
+                    return run_window_fwd(ch, 6, (int)sizeof(TV), pb, stream, "launch of the fused location / softmax / window-gather kernel", "",
+                                          [&](unsigned *probe) {
+                        return msda::launch_fwd_tiled_prep<TV, TP>(value, src, out, N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), probe, stream);
+                    });
                 }
                 // the monitor chose the direct kernel: location / softmax kernel, then the direct forward (the choice is not asked for again)
                 if (int rc = prep_forward_impl<T, TP>(offsets, off_stride, logits, log_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P, loc, aw, stream_))
                     return rc;
                 g_tl_fwd_variant = 1;
-                int rc;
-                if constexpr (std::is_same<TV, msda::bf16_t>::value)
-                    rc = forward_bf16_impl(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
-                else
-                    rc = forward_impl<T>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
+                const int rc = forward_impl<T, TV>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
                 g_tl_fwd_variant = -1;
                 return rc;
             }
@@ -1169,39 +1040,71 @@ int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi
     if (!fused) {
         if (int rc = prep_forward_impl<T, TP>(offsets, off_stride, logits, log_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P, loc, aw, stream_))
             return rc;
-        if constexpr (std::is_same<TV, msda::bf16_t>::value)
-            return forward_bf16_impl(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
-        else
-            return forward_impl<T>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
+        return forward_impl<T, TV>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
     }
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
     if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
     if (!is_aligned(value, sizeof(TV)) || !is_aligned(out, sizeof(TV)) || !is_aligned(aw, sizeof(T)) || !is_aligned(loc, 2 * sizeof(T)) ||
         !is_aligned(ref, sizeof(T)) || !is_aligned(offsets, sizeof(TP)) || !is_aligned(logits, sizeof(TP)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
         return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs 2*sizeof(T))");
-    int C;
-    if constexpr (std::is_same<TV, msda::bf16_t>::value) C = pick_channels_bf16(D, {value, out});
-    else C = pick_channels_per_lane<T>(D, {value, out});
+    const int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, out});
     const msda::DirectGeom g = direct_geom(pb, C);
     const size_t lds = msda::direct_lds_bytes<T>(g);
-    if (lds > 64 * 1024) return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L);
-    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
+    if (lds > 64 * 1024) return too_many_levels(L);
     const msda::PrepSrc<TP> src{offsets, logits, off_stride, log_stride, ref_dim};
-    ProfileScope prof(0, 5, (int)sizeof(TV), N, S, M, D, L, Lq, P, stream);
-    const bool many = (int64_t)N * Lq * M >= 65536;
-#define MSDA_LAUNCH_FWDP(CC)                                                                                                                    \
-    if (many) hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 6, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g); \
-    else hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 4, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g)
-    switch (C) {
-        case 4: MSDA_LAUNCH_FWDP((sizeof(T) == 4 ? 4 : 2)); break;
-        case 2: MSDA_LAUNCH_FWDP(2); break;
-        default: MSDA_LAUNCH_FWDP(1); break;
-    }
-#undef MSDA_LAUNCH_FWDP
+    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
+    ProfileScope prof(0, 5, (int)sizeof(TV), pb, stream);
+    with_channels<T>(C, [&](auto cc) {
+        constexpr int CC = decltype(cc)::value;
+        if (many_items(pb)) hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 6, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g);
+        else hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 4, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g);
+    });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch of the fused location / softmax / gather kernel");
     return MSDA_OK;
 }
+
+// The options: one table read by msda_set_option and msda_get_option.  A value is accepted when it lies in [lo, hi] and, where `values`
+// is not 0, bit `value` of it is set.  hi < lo: the option cannot be set; !readable: it cannot be read.
+namespace {
+struct Option {
+    const char *key;
+    std::atomic<int> *at;
+    int lo, hi;
+    unsigned values;
+    bool readable;
+};
+const Option *find_option(const char *key)
+{
+    static const Option table[] = {
+        {"fwd_variant", &g_fwd_variant, 0, 3, 0, true},
+        {"fwd_prep_fused", &g_fwd_prep_fused, 0, 2, 0, true},      // 1: decoder-shaped calls; 2: + encoder-shaped
+        {"bwd_variant", &g_bwd_variant, 0, 5, 1u << 0 | 1u << 1 | 1u << 4 | 1u << 5, true},
+        {"band_lds_kb", &msda::band_options().lds_kb, 16, 150, 0, true},
+        {"band_hits", &msda::band_options().hits, 32, 65536, 0, true},
+        {"rps_tile", &msda::rps_options().tile, 4, 16, 0, true},
+        {"rps_max_chunks", &msda::rps_options().max_chunks, 1, 4096, 0, true},
+        {"rps_route_wgs", &msda::rps_options().route_wgs, 1, 64, 0, true},
+        {"rps_seg_shift", &msda::rps_options().seg_shift, 3, 11, 0, true},
+        {"rps_order", &msda::rps_options().order, 0, 1, 0, true},
+        {"bwd_direct_cpl", &g_bwd_cpl, 0, 4, 1u << 0 | 1u << 1 | 1u << 2 | 1u << 4, true},
+        {"tile_region", &msda::tiled_options().region_px, 4, 64, 0, true},
+        {"tile_margin", &msda::tiled_options().margin, 0, 32, 0, true},
+        {"tile_debug", &msda::tiled_options().dbg, 0, 65535, 0, false},
+        {"tile_persist", &msda::tiled_options().persist, 0, 65536, 0, true},
+        {"bwd_levelsum", &g_levelsum, 0, 1, 0, true},
+        {"bwd_split", &g_bwd_split, 0, 1, 0, true},
+        {"profile_filter", &g_prof_filter, 0, 47, 0, true},
+        {"levelsum_lds_kb", &msda::levelsum_lds_kb(), 8, 150, 0, true},
+        {"tile_grow", &msda::tiled_options().grow, 0, 1, 0, true},
+        {"locality_monitor", &g_monitor_on, 0, 1, 0, true},
+        {"locality_share_ppm", &g_last_share_ppm, 0, -1, 0, true},   // read-only
+    };
+    for (const Option &o : table)
+        if (key && !strcmp(key, o.key)) return &o;
+    return nullptr;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1222,64 +1125,28 @@ const char *msda_last_error(void) { return g_err; }
 
 int msda_set_option(const char *key, int value)
 {
-    if (key && !strcmp(key, "fwd_variant") && value >= 0 && value <= 3) { g_fwd_variant = value; return MSDA_OK; }
-    if (key && !strcmp(key, "fwd_prep_fused") && value >= 0 && value <= 2) { g_fwd_prep_fused = value; return MSDA_OK; }      // 1: decoder-shaped calls; 2: + encoder-shaped
-    if (key && !strcmp(key, "bwd_variant") && (value == 0 || value == 1 || value == 4 || value == 5)) { g_bwd_variant = value; return MSDA_OK; }
-    if (key && !strcmp(key, "band_lds_kb") && value >= 16 && value <= 150) { msda::band_options().lds_kb = value; return MSDA_OK; }
-    if (key && !strcmp(key, "band_hits") && value >= 32 && value <= 65536) { msda::band_options().hits = value; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_tile") && value >= 4 && value <= 16) { msda::rps_options().tile = value; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_max_chunks") && value >= 1 && value <= 4096) { msda::rps_options().max_chunks = value; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_route_wgs") && value >= 1 && value <= 64) { msda::rps_options().route_wgs = value; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_seg_shift") && value >= 3 && value <= 11) { msda::rps_options().seg_shift = value; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_order") && value >= 0 && value <= 1) { msda::rps_options().order = value; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_direct_cpl") && (value == 0 || value == 1 || value == 2 || value == 4)) { g_bwd_cpl = value; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_region") && value >= 4 && value <= 64) { msda::tiled_options().region_px = value; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_margin") && value >= 0 && value <= 32) { msda::tiled_options().margin = value; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_debug") && value >= 0 && value <= 65535) { msda::tiled_options().dbg = value; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_persist") && value >= 0 && value <= 65536) { msda::tiled_options().persist = value; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_levelsum") && (value == 0 || value == 1)) { g_levelsum = value; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_split") && (value == 0 || value == 1)) { g_bwd_split = value; return MSDA_OK; }
-    if (key && !strcmp(key, "profile_filter") && value >= 0 && value <= 47) { g_prof_filter = value; return MSDA_OK; }
-    if (key && !strcmp(key, "levelsum_lds_kb") && value >= 8 && value <= 150) { msda::levelsum_lds_kb() = value; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_grow") && (value == 0 || value == 1)) { msda::tiled_options().grow = value; return MSDA_OK; }
-    if (key && !strcmp(key, "locality_monitor") && (value == 0 || value == 1)) {
-        g_monitor_on = value;
+    const Option *o = find_option(key);
+    if (!o || value < o->lo || value > o->hi || (o->values && !(o->values >> value & 1)))
+        return fail(MSDA_ERR_BAD_OPTION, "unknown option or value: %s=%d", key ? key : "(null)", value);
+    *o->at = value;
+    if (o->at == &g_monitor_on) {
         for (Monitor &mo : g_monitors) {   // switching it (either way) forgets what was learnt
             std::lock_guard<std::mutex> lock(mo.mu);
             mo.table.clear();
             for (ProbeSlot &ps : mo.slot) ps.pending = false;   // (probes still in flight belong to what is being forgotten)
         }
         g_last_share_ppm = -1;
-        return MSDA_OK;
     }
-    return fail(MSDA_ERR_BAD_OPTION, "unknown option or value: %s=%d", key ? key : "(null)", value);
+    return MSDA_OK;
 }
 
 int msda_get_option(const char *key, int *value)
 {
     if (!value) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (key && !strcmp(key, "fwd_variant")) { *value = g_fwd_variant; return MSDA_OK; }
-    if (key && !strcmp(key, "fwd_prep_fused")) { *value = g_fwd_prep_fused; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_variant")) { *value = g_bwd_variant; return MSDA_OK; }
-    if (key && !strcmp(key, "band_lds_kb")) { *value = msda::band_options().lds_kb; return MSDA_OK; }
-    if (key && !strcmp(key, "band_hits")) { *value = msda::band_options().hits; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_direct_cpl")) { *value = g_bwd_cpl; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_tile")) { *value = msda::rps_options().tile; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_max_chunks")) { *value = msda::rps_options().max_chunks; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_route_wgs")) { *value = msda::rps_options().route_wgs; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_seg_shift")) { *value = msda::rps_options().seg_shift; return MSDA_OK; }
-    if (key && !strcmp(key, "rps_order")) { *value = msda::rps_options().order; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_region")) { *value = msda::tiled_options().region_px; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_margin")) { *value = msda::tiled_options().margin; return MSDA_OK; }
-    if (key && !strcmp(key, "tile_persist")) { *value = msda::tiled_options().persist; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_levelsum")) { *value = g_levelsum; return MSDA_OK; }
-    if (key && !strcmp(key, "bwd_split")) { *value = g_bwd_split; return MSDA_OK; }
-    if (key && !strcmp(key, "profile_filter")) { *value = g_prof_filter; return MSDA_OK; }
-    if (key && !strcmp(key, "levelsum_lds_kb")) { *value = msda::levelsum_lds_kb(); return MSDA_OK; }
-    if (key && !strcmp(key, "tile_grow")) { *value = msda::tiled_options().grow; return MSDA_OK; }
-    if (key && !strcmp(key, "locality_monitor")) { *value = g_monitor_on; return MSDA_OK; }
-    if (key && !strcmp(key, "locality_share_ppm")) { *value = g_last_share_ppm; return MSDA_OK; }   // read-only
-    return fail(MSDA_ERR_BAD_OPTION, "unknown option: %s", key ? key : "(null)");
+    const Option *o = find_option(key);
+    if (!o || !o->readable) return fail(MSDA_ERR_BAD_OPTION, "unknown option: %s", key ? key : "(null)");
+    *value = *o->at;
+    return MSDA_OK;
 }
 
 int msda_tiled_plan(int N, int S, int M, int D, int L, int Lq, int P, const int64_t *shapes_host,
@@ -1425,7 +1292,7 @@ int msda_forward_bf16(const uint16_t *value, const int64_t *spatial_shapes, cons
                       int im2col_step, uint16_t *out, const int64_t *shapes_host, const int64_t *level_start_host,
                       msda_stream_t stream)
 {
-    return forward_bf16_impl(reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, sampling_loc,
+    return forward_impl<float, msda::bf16_t>(reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, sampling_loc,
                              attn_weight, N, S, M, D, L, Lq, P, im2col_step, reinterpret_cast<msda::bf16_t *>(out), shapes_host,
                              level_start_host, stream);
 }
@@ -1436,7 +1303,7 @@ int msda_backward_bf16(const uint16_t *value, const int64_t *spatial_shapes, con
                        float *grad_attn_weight, const int64_t *shapes_host, const int64_t *level_start_host,
                        msda_stream_t stream)
 {
-    return backward_bf16_impl(reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, sampling_loc,
+    return backward_impl<float, msda::bf16_t>(reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, sampling_loc,
                               attn_weight, reinterpret_cast<const msda::bf16_t *>(grad_out), N, S, M, D, L, Lq, P, im2col_step,
                               reinterpret_cast<msda::bf16_t *>(grad_value), grad_sampling_loc, grad_attn_weight, shapes_host,
                               level_start_host, stream);

@@ -933,19 +933,6 @@ inline TiledPlan plan_gather(int N, int S, int M, int D, int L, int Lq, int P, c
     if (pl.ok && pl.lds_bytes < fix) pl.lds_bytes = fix;
     return pl;
 }
-template <typename T>
-bool tiled_fwd_applicable(int, int, int, int, int, int, int, const int64_t *, const int64_t *, const T *, const T *)
-{
-    return false;
-}
-template <>
-inline bool tiled_fwd_applicable<float>(int N, int S, int M, int D, int L, int Lq, int P, const int64_t *shapes,
-                                        const int64_t *lsi, const float *value, const float *out)
-{
-    if ((reinterpret_cast<uintptr_t>(value) | reinterpret_cast<uintptr_t>(out)) & 15) return false;
-    return plan_gather(N, S, M, D, L, Lq, P, shapes, lsi).ok;
-}
-
 // Persistent grid size: at most `cap` workgroups, a multiple of 8 (XCD affinity), and with cap/8 coprime to the number of
 // sub-items per region -- otherwise a workgroup's stride through the item list would always land on the same kind of
 // sub-item (e.g. always the three-level phase) and the work would be badly balanced.
@@ -1011,21 +998,6 @@ inline hipError_t launch_fwd_tiled_prep(const TV *value, const TiledPrepSrc &src
     const int grid = persistent_grid(pl.grid * (kTD / kFwdGC), tiled_options().persist, kTD / kFwdGC);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), pl.lds_bytes, stream, value, (const float *)nullptr, (const float *)nullptr, out, pl.g, src);
     return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_fwd_tiled(const T *, const int64_t *, const int64_t *, const T *, const T *, T *, int, int, int, int,
-                            int, int, int, const int64_t *, const int64_t *, unsigned *, hipStream_t)
-{
-    return hipErrorNotSupported;
-}
-template <>
-inline hipError_t launch_fwd_tiled<float>(const float *value, const int64_t *, const int64_t *, const float *loc,
-                                          const float *aw, float *out, int N, int S, int M, int D, int L, int Lq, int P,
-                                          const int64_t *shapes_h, const int64_t *lsi_h, unsigned *general_points,
-                                          hipStream_t stream)
-{
-    return launch_fwd_tiled_tv<float>(value, loc, aw, out, N, S, M, D, L, Lq, P, shapes_h, lsi_h, general_points, stream);
 }
 
 }  // namespace msda

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-kernel register / scratch / LDS / occupancy table from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
 
-    hipcc <flags of richsem_amd/_build.py> -Rpass-analysis=kernel-resource-usage -o /dev/null csrc/msda_api.hip 2> usage.txt
+    hipcc <flags of richsem_amd/_build.py> --cuda-device-only -c -Rpass-analysis=kernel-resource-usage -o /dev/null \\
+        richsem_amd/csrc/msda_api.hip 2> usage.txt
     python tools/resource_table.py usage.txt > profiles/r02_resources.md
 """
 import re
