@@ -31,7 +31,8 @@ from richsem_amd.clip_resnet import ModifiedResNetTeacher
 from richsem_amd.dn import prepare_dn_layout
 from richsem_amd.fed_loss import FedClassSampler, MaskedFocalNegativeSum, class_weights_from_image_counts
 from richsem_amd.functions.linear import Lin256Function, VersionCache, pack_linear256
-from richsem_amd.matcher import BoxPairLoss, FocalNegativeSum, FocalPositiveSum, HungarianMatcher
+from richsem_amd.matcher import (BoxPairLoss, CostPlan, FocalNegativeSum, FocalPositiveSum, HungarianMatcher, LateStatus,
+                                 pairs_from_query_of_target)
 from richsem_amd.modules import (MLP, refine_boxes, DeformableTransformerDecoderLayer, DeformableTransformerEncoderLayer, TransformerDecoder,
                                  clip_box_targets, get_reference_points, inverse_sigmoid)
 from richsem_amd.two_stage import ClassScorer
@@ -101,7 +102,7 @@ class Step(nn.Module):
     """the rows with their (synthetic) parameters; ``forward`` = model forward + criterion, returns the loss and section times"""
 
     def __init__(self, n_img=2, height=800, width=1333, boxes_per_image=12, seed=0, dev="cuda", fed_loss=False, fed_num_sample_cats=50,
-                 class_image_counts=None):
+                 class_image_counts=None, device_matcher=False, keep_match_outputs=False):
         super().__init__()
         torch.manual_seed(seed)
         self.n_img, self.H, self.Wimg, self.K = n_img, height, width, boxes_per_image
@@ -149,6 +150,15 @@ class Step(nn.Module):
             counts = synthetic_image_counts(NUM_CLASSES) if class_image_counts is None else class_image_counts
             self.fed_sampler = FedClassSampler(fed_num_sample_cats, class_weights_from_image_counts(counts, NUM_CLASSES))
         self.last_fed_mask = None
+        # the Hungarian assignment on the device (msda_lsap_*, richsem_amd/matcher.py) instead of scipy on the host: opt-in.  The step then
+        # has no host wait between its first and last kernel and captures whole (run_graphed(device_matcher=True)); the solver's status is
+        # read one step late (matcher.LateStatus), the way AsyncLossLog reads the losses
+        self.device_matcher = bool(device_matcher)
+        self.cost_plan = None
+        self.late_status = LateStatus()
+        self.last_qot = self.last_status = None
+        self.keep_match_outputs = bool(keep_match_outputs)      # (tests: the logits / boxes the solver saw stay referenced as last_match_outputs)
+        self.last_match_outputs = None
 
     # synthetic LVIS-shaped batch
     def batch(self, seed=0):
@@ -204,6 +214,10 @@ class Step(nn.Module):
         self.scorer.prepare(self.dino_visual_proj.weight, self.text_embed, self.logit_scale)      # (its operand follows the weight's updates)
         self.static = st
         self._targets = targets
+        if self.device_matcher:      # (host -> device copies: here, not in the step)
+            if max(st["known_num"]) > NUM_QUERIES:
+                raise ValueError(f"device_matcher: an image with {max(st['known_num'])} targets against {NUM_QUERIES} queries")
+            self.cost_plan = CostPlan(targets, dev, torch.float32)
         return st
 
     def forward(self, images, mask, targets, indices=None, topk=None):
@@ -305,7 +319,9 @@ class Step(nn.Module):
         if self._model_only:      # (model_part: the step up to the matcher, as tensors)
             return logits, coords, interm["pred_logits"], interm["pred_boxes"], clip_logits, t_logits
         # ---- matcher (matcher.py:30-78, one host copy for the 7 outputs) -------------------------------------------------------------------
-        if indices is None:
+        if indices is None and self.device_matcher:
+            indices = self.match_device(logits, coords, interm["pred_logits"], interm["pred_boxes"], targets)
+        elif indices is None:
             indices = self.match(logits, coords, interm["pred_logits"], interm["pred_boxes"], targets)
         packed = indices if (isinstance(indices, tuple) and torch.is_tensor(indices[0])) else self.pack_indices(indices, targets)
         if packed is not indices:
@@ -369,6 +385,20 @@ class Step(nn.Module):
 
     def match(self, logits, coords, il, ib, targets):
         return self.matcher.match_many(self._match_outputs(logits, coords, il, ib), targets)
+
+    @torch.no_grad()
+    def match_device(self, logits, coords, il, ib, targets):
+        """the assignment of the 6 + 1 outputs solved on the device, as the packed tensors :meth:`pack_indices` builds from the host's: cost
+        blocks -> ``msda_lsap_*`` -> index tensors, all enqueued, nothing read back (``last_qot`` (7, targets) / ``last_status`` (7, images)
+        keep the solver's result; outside a capture the status goes to ``late_status``, which raises one step late)"""
+        outs = [{"pred_logits": o["pred_logits"].float(), "pred_boxes": o["pred_boxes"].float()} for o in self._match_outputs(logits, coords, il, ib)]
+        self.last_qot, self.last_status = self.matcher.match_many_device(outs, self.cost_plan)
+        if self.keep_match_outputs:
+            self.last_match_outputs = outs
+        if not torch.cuda.is_current_stream_capturing():
+            self.late_status.push(self.last_status)
+        labels, boxes = torch.cat([t["labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
+        return (labels, boxes) + pairs_from_query_of_target(self.last_qot, self.cost_plan, NUM_QUERIES)
 
     def match_begin(self, logits, coords, il, ib, targets):
         """the device half of :meth:`match` (cost blocks + copy to the host enqueued, nothing waits); :meth:`match_end` the host half"""
@@ -624,7 +654,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
     try:
         del model
         torch.cuda.empty_cache()
-        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts")}
+        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image")}
         out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
@@ -644,6 +674,17 @@ class _ModelPart(nn.Module):
         return self.step.model_part(images, self.step._mask, teacher=False)
 
 
+class _WholeStep(nn.Module):
+    """the whole step -- model, cost blocks, on-device assignment, teacher, criterion -- as one module of tensors (Step(device_matcher=True))"""
+
+    def __init__(self, step):
+        super().__init__()
+        self.step = step
+
+    def forward(self, images):
+        return self.step(images, self.step._mask, self.step._targets)
+
+
 class _LossPart(nn.Module):
     def __init__(self, step):
         super().__init__()
@@ -654,14 +695,18 @@ class _LossPart(nn.Module):
 
 
 def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, fed_seed=None,
-                **step_kwargs):
+                device_matcher=False, **step_kwargs):
     """The composed step as a trainer can run it WITHOUT freezing the matcher: the two device-only parts -- everything up to the matcher,
     and the criterion -- each captured once, forward and backward, with ``torch.cuda.make_graphed_callables`` (HIP graphs replayed by
     autograd), the Hungarian assignment between them live on the host every step.  Eagerly the step is bound by ~2900 kernel launches
     (ms above); this is the same work with three launches' worth of host time.  Returns the dict bench.py attaches as
     ``full_step.graphed_sections`` (``step_kwargs``: a smaller Step for the tests; ``return_model``: the trained Step and the graphed model
     part under "model" / "ga", ``images`` under "images", the training step under "step"; ``fed_seed``: Step.freeze_fed).  The packed / cast forms of the parameters are built INSIDE the captured graphs
-    (richsem_amd/param_cache.py): every replay re-packs from the current masters, the frozen teacher's graph included."""
+    (richsem_amd/param_cache.py): every replay re-packs from the current masters, the frozen teacher's graph included.
+    ``device_matcher``: the device-only form instead, see :func:`run_graphed_device`."""
+    if device_matcher:
+        return run_graphed_device(n_img, dev, steps=steps, warmup=warmup, optimizer=optimizer, noise_seed=noise_seed, return_grads=return_grads, lr=lr,
+                                  return_model=return_model, fed_seed=fed_seed, **step_kwargs)
     model = Step(n_img=n_img, dev=dev, **step_kwargs)
     model.timing = False
     images, mask, targets = model.batch()
@@ -751,6 +796,81 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
             **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
                 "indices": last["assign"], "topk": model.last_topk.clone()} if return_grads else {}),
             **({"model": model, "ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else {})}
+
+
+def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False,
+                       fed_seed=None, **step_kwargs):
+    """The training step with NO host wait between its first and last kernel: model, cost blocks, the Hungarian assignment
+    (``msda_lsap_*``), frozen teacher and criterion captured forward + backward as ONE ``torch.cuda.make_graphed_callables`` callable, then
+    gradient clipping + fused AdamW.  The assignment is live: every replay solves it for that replay's model outputs.  The solver's status
+    is copied to pinned memory after the replay and read one step late (a non-zero entry raises ValueError then).  Returns what
+    :func:`run_graphed` returns; with ``return_model`` also "query_of_target" / "status": the static tensors every replay rewrites."""
+    model = Step(n_img=n_img, dev=dev, device_matcher=True, **step_kwargs)
+    model.timing = False
+    images, mask, targets = model.batch()
+    model.prepare(mask, targets)
+    model._mask = mask
+    if noise_seed is not None:
+        model.freeze_noise(noise_seed)
+    if fed_seed is not None:
+        model.freeze_fed(fed_seed)
+    whole = _WholeStep(model)
+    side = torch.cuda.Stream()      # one stream for the warm-up, the capture and the training steps: see run_graphed
+    side.wait_stream(torch.cuda.current_stream())
+    saved_capture_stream = torch.cuda.graph.default_capture_stream
+    torch.cuda.graph.default_capture_stream = side
+    try:
+        with torch.cuda.stream(side):
+            pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (alive to the end)
+            whole(images).backward()      # (eager once: workspaces of this stream, caches, the solver's LDS attribute)
+            for p in model.parameters():
+                p.grad = None
+            torch.cuda.synchronize()
+            model.late_status.flush()
+            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)      # (the private warm-up stream: see run_graphed)
+            try:
+                with quiet_gc():
+                    gw = torch.cuda.make_graphed_callables(whole, (images,), num_warmup_iters=3, allow_unused_input=True)
+            finally:
+                torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(True)
+            torch.cuda.synchronize()
+            model.late_status.flush()      # (the warm-up iterations ran eagerly and pushed theirs)
+            params = [p for p in model.parameters() if p.requires_grad]
+            opt = make_optimizer(params, lr) if optimizer else None
+
+            def step(batch_images=images):
+                for p in params:
+                    p.grad = None
+                loss = gw(batch_images)
+                loss.backward()
+                model.late_status.push(model.last_status)      # (raises for the PREVIOUS step's status)
+                if opt is not None:
+                    optimizer_step(opt, params)
+                return loss
+
+            for _ in range(warmup):
+                step()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                loss = step()
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) / steps * 1e3
+            model.late_status.flush()
+    finally:
+        torch.cuda.graph.default_capture_stream = saved_capture_stream
+    torch.cuda.current_stream().wait_stream(side)
+    return {"what": "the same training step with the Hungarian assignment solved on the device (msda_lsap_*): model, cost blocks, assignment, "
+                    "frozen teacher and criterion captured forward + backward as ONE graphed callable, no host wait between the step's first "
+                    "and last kernel; the solver's status is read one step late"
+                    + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"),
+            "optimizer": "AdamW(fused) + clip_grad_norm_(0.1)" if optimizer else None,
+            "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
+            "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
+            **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
+                "topk": model.last_topk.clone()} if return_grads else {}),
+            **({"model": model, "ga": gw, "images": images, "step": lambda *a: _on_stream(side, lambda: step(*a)),
+                "query_of_target": model.last_qot, "status": model.last_status} if return_model else {})}
 
 
 def _on_stream(stream, fn):
@@ -848,6 +968,21 @@ if __name__ == "__main__":
     ap.add_argument("--stop-at", default=None, help="profiling aid: cut the step off after this section (implies --no-graph)")
     ap.add_argument("--fed-loss", action="store_true", help="the criterion's federated loss (use_fed_loss, 50 classes per draw; synthetic class "
                                                            "weights: Step.loss_part)")
+    ap.add_argument("--boxes-per-image", type=int, default=12, help="targets per synthetic image (default 12)")
+    ap.add_argument("--device-matcher", action="store_true", help="time the graphed training step in both forms: the Hungarian assignment on the "
+                                                                  "host between two captured parts (twice, to show its spread) and on the device "
+                                                                  "inside one captured step")
     a_ = ap.parse_args()
+    if a_.device_matcher:
+        kw = dict(steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}))
+        res = {"boxes_per_image": a_.boxes_per_image}
+        for name, dm in (("host_matcher", False), ("host_matcher_again", False), ("device_matcher", True)):
+            r = run_graphed(a_.images, torch.device("cuda", 0), device_matcher=dm, **kw)
+            res[name] = {k: r[k] for k in ("ms", "img_per_s", "loss")}
+            torch.cuda.empty_cache()
+            print(json.dumps({name: res[name]}), file=sys.stderr, flush=True)
+        print(json.dumps(res, indent=1))
+        sys.exit(0)
     print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at,
-                         **({"fed_loss": True} if a_.fed_loss else {})), indent=1))
+                         **({"fed_loss": True} if a_.fed_loss else {}), **({"boxes_per_image": a_.boxes_per_image} if a_.boxes_per_image != 12 else {})),
+                     indent=1))

@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define RICHSEM_MSDA_ABI_VERSION 9
+#define RICHSEM_MSDA_ABI_VERSION 10
 
 /* Return codes: 0 = success; negative = argument error detected on the host (nothing was
  * launched); positive = hipError_t reported by the runtime. */
@@ -537,6 +537,38 @@ int msda_matcher_cost_f32(const float *logits, const float *boxes, const int64_t
 int msda_matcher_cost_f64(const double *logits, const double *boxes, const int64_t *tgt_ids, const double *tgt_boxes,
                           const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
                           double w_giou, double alpha, double *cost, msda_stream_t stream);
+/* The same entries with every block stored TARGET-major: entry (q, t) of image b at element Q * tgt_offsets[b] + t * Q + q.  The layout
+ * msda_lsap_* scans with unit stride (target_major = 1); the value of every entry is msda_matcher_cost_*'s. */
+int msda_matcher_cost_tm_f32(const float *logits, const float *boxes, const int64_t *tgt_ids, const float *tgt_boxes,
+                             const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
+                             double w_giou, double alpha, float *cost, msda_stream_t stream);
+int msda_matcher_cost_tm_f64(const double *logits, const double *boxes, const int64_t *tgt_ids, const double *tgt_boxes,
+                             const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
+                             double w_giou, double alpha, double *cost, msda_stream_t stream);
+
+/* ---- the Hungarian assignment on the device (csrc/msda_lsap.h; what the reference asks scipy.optimize.linear_sum_assignment for on
+ * the host, models/richsem/matcher.py:76-78) ------------------------------------------------------------------------------------
+ * Exact linear sum assignment of n_out * B cost blocks in ONE launch: shortest augmenting paths with dual variables (Jonker-Volgenant
+ * as in Crouse 2016, the algorithm of scipy's rectangular_lsap), float64 arithmetic whatever the cost type, one wave per block.
+ *   cost             n_out consecutive buffers of Q * n_targets elements, each as msda_matcher_cost_* (target_major = 0) or
+ *                    msda_matcher_cost_tm_* (target_major = 1) writes it: image b's Q x T_b block at element Q * tgt_offsets[b]
+ *   tgt_offsets      (B + 1) int64 ON THE DEVICE, tgt_offsets[B] == n_targets.  The block sizes are read from it by the kernel: the
+ *                    launch depends on n_out, B, Q and n_targets only, so a captured launch stays valid when the per-image counts change
+ *                    under the same total
+ *   query_of_target  (n_out, n_targets) int64: the query assigned to target t of output o, -1 for a target left without one (T_b > Q:
+ *                    exactly Q targets of the block are assigned) and for every target of a block that was not solved
+ *   status           (n_out, B) int32: 0 solved; 1 the block holds a non-finite cost (found by a scan before the solve; scipy raises
+ *                    there); 2 no augmenting path of finite length (finite costs whose float64 sums overflow); 3 tgt_offsets does not
+ *                    describe a block inside n_targets (nothing read or written for it)
+ *   workspace        msda_lsap_workspace_bytes() bytes, 4-byte aligned; may be NULL when that is 0 (every size supported today keeps its
+ *                    state in LDS and needs none)
+ * Limits: Q <= 4096 and n_targets <= 4096, MSDA_ERR_TOO_LARGE beyond (from both entry points, nothing launched).  Among assignments of
+ * equal total cost the choice is the kernel's own, not scipy's.  No allocation, no synchronisation. */
+int msda_lsap_workspace_bytes(int n_out, int B, int Q, int64_t n_targets, int64_t *bytes);
+int msda_lsap_f32(const float *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
+                  int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream);
+int msda_lsap_f64(const double *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
+                  int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream);
 
 /* ---- feed-forward block of the transformer layers on the matrix cores ----------
  *     out = LayerNorm(x + W2 . relu(W1 . x + b1) + b2)

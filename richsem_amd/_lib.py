@@ -17,7 +17,7 @@ ERR_NAMES = {
     -8: "MSDA_ERR_NOT_ON_CPU",
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 def raw_stream(dev=None):
@@ -66,7 +66,8 @@ SYMBOLS = [
     "msda_dn_indices_i64", "msda_dn_attn_mask_u8", "msda_topk_f32", "msda_sine_embed_bf16", "msda_narrow_linear_backward_bf16", "msda_box_refine_forward", "msda_box_refine_backward", "msda_box_refine_backward_ref", "msda_box_pair_loss_f32", "msda_focal_pos_sum_f32", "msda_roi_align_forward_f32", "msda_roi_align_forward_f64",
     "msda_ffn_pack_w2_bf16", "msda_ffn_forward_bf16", "msda_ffn_debug_stamps", "msda_ffn_forward_train_bf16", "msda_ffn_ln_backward_bf16", "msda_add_layernorm_forward_bf16", "msda_lin256_pack_bf16", "msda_lin256_forward_bf16", "msda_lin256_pack_f32", "msda_lin256_forward_f32", "msda_lin256_forward_stacked_bf16",
     "msda_attn_workspace_bytes", "msda_attn_forward_bf16", "msda_attn_backward_bf16",
-    "msda_matcher_cost_f32", "msda_matcher_cost_f64", "msda_focal_neg_sum_f32", "msda_focal_neg_grad_f32", "msda_fed_class_mask_f32", "msda_focal_neg_sum_masked_f32", "msda_focal_neg_grad_masked_f32",
+    "msda_matcher_cost_f32", "msda_matcher_cost_f64", "msda_matcher_cost_tm_f32", "msda_matcher_cost_tm_f64",
+    "msda_lsap_workspace_bytes", "msda_lsap_f32", "msda_lsap_f64", "msda_focal_neg_sum_f32", "msda_focal_neg_grad_f32", "msda_fed_class_mask_f32", "msda_focal_neg_sum_masked_f32", "msda_focal_neg_grad_masked_f32",
     "msda_attnpool_core_f32", "msda_attnpool_core_f64",
     "msda_cls_packed_elems", "msda_cls_pack", "msda_cls_max_scores",
     "msda_conv_set_tiling", "msda_conv_set_ring", "msda_conv_dgrad_fused_bf16", "msda_conv_packed_elems", "msda_conv_pack_weight", "msda_conv_forward_bf16", "msda_conv_dgrad_bf16", "msda_conv_forward_workspace_bytes", "msda_conv_forward_ws_bf16", "msda_conv_dgrad_workspace_bytes", "msda_conv_dgrad_ws_bf16", "msda_pool_nhwc_bf16", "msda_groupnorm8_nhwc_bf16", "msda_groupnorm8_backward_nhwc_bf16", "msda_conv_wgrad_workspace_bytes", "msda_conv_wgrad_bf16", "msda_conv_set_wgrad_ring", "msda_conv_wgrad_group_workspace_bytes", "msda_conv_wgrad_group_bf16",
@@ -143,9 +144,15 @@ def load():
         f.argtypes = [vp, vp] + [ci] * 7 + [ctypes.c_double, ci, ci, vp, vp]
         f.restype = ci
     for sfx in ("f32", "f64"):
-        f = getattr(L, "msda_matcher_cost_" + sfx)
-        f.argtypes = [vp] * 5 + [ci] * 3 + [i64] + [ctypes.c_double] * 4 + [vp, vp]
+        for name in ("msda_matcher_cost_", "msda_matcher_cost_tm_"):
+            f = getattr(L, name + sfx)
+            f.argtypes = [vp] * 5 + [ci] * 3 + [i64] + [ctypes.c_double] * 4 + [vp, vp]
+            f.restype = ci
+        f = getattr(L, "msda_lsap_" + sfx)
+        f.argtypes = [vp, ci, vp, ci, ci, ci, i64, vp, vp, vp, vp]
         f.restype = ci
+    L.msda_lsap_workspace_bytes.argtypes = [ci, ci, ci, i64, ctypes.POINTER(i64)]
+    L.msda_lsap_workspace_bytes.restype = ci
     L.msda_focal_neg_sum_f32.argtypes = [vp, vp, i64, ci, ctypes.c_float, vp, ci, ctypes.POINTER(ci), vp]
     L.msda_focal_neg_sum_f32.restype = ci
     L.msda_focal_neg_grad_f32.argtypes = [vp, vp, i64, ci, ctypes.c_float, vp, vp, vp]

@@ -36,8 +36,9 @@ __device__ __forceinline__ double matcher_exp<double>(double x) { return exp(x);
 
 // logits (B, Q, C); boxes (B, Q, 4) cxcywh; tgt_ids (Ttot) int64; tgt_boxes (Ttot, 4) cxcywh; tgt_offsets (B + 1) int64 prefix
 // of the per-image target counts; cost: Q * Ttot elements.  A label outside [0, C) gives NaN in its column (the reference
-// raises an index error there).
-template <typename T>
+// raises an index error there).  TM: the same entries with every block stored target-major (entry (q, t) at t * Q + q inside the block), the
+// layout the on-device solver (msda_lsap.h) scans with unit stride; the arithmetic per entry is the same.
+template <typename T, bool TM = false>
 __global__ __launch_bounds__(256) void matcher_cost_kernel(const T *__restrict__ logits, const T *__restrict__ boxes,
                                                            const int64_t *__restrict__ tgt_ids, const T *__restrict__ tgt_boxes,
                                                            const int64_t *__restrict__ tgt_offsets, int B, int Q, int C, T w_class,
@@ -50,7 +51,14 @@ __global__ __launch_bounds__(256) void matcher_cost_kernel(const T *__restrict__
         const int64_t t0 = tgt_offsets[b];
         const int Tb = (int)(tgt_offsets[b + 1] - t0);
         const int64_t r = i - (int64_t)Q * t0;
-        const int q = (int)(r / Tb), t = (int)(r - (int64_t)q * Tb);
+        int q, t;
+        if (TM) {
+            t = (int)(r / Q);
+            q = (int)(r - (int64_t)t * Q);
+        } else {
+            q = (int)(r / Tb);
+            t = (int)(r - (int64_t)q * Tb);
+        }
         const int64_t label = tgt_ids[t0 + t];
         const T *ob = boxes + ((int64_t)b * Q + q) * 4, *tb = tgt_boxes + (t0 + t) * 4;
         T cc;

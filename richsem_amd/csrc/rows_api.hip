@@ -12,10 +12,11 @@
 extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
 #include "msda_attnpool.h"
 #include "msda_matcher.h"
+#include "msda_lsap.h"
 
 namespace {
 
-template <typename T>
+template <typename T, bool TM = false>
 int matcher_cost_impl(const T *logits, const T *boxes, const int64_t *tgt_ids, const T *tgt_boxes, const int64_t *tgt_offsets, int B,
                       int Q, int C, int64_t n_targets, double w_class, double w_bbox, double w_giou, double alpha, T *cost,
                       msda_stream_t stream)
@@ -27,8 +28,46 @@ int matcher_cost_impl(const T *logits, const T *boxes, const int64_t *tgt_ids, c
     if (total == 0) return MSDA_OK;
     if (total >= ((int64_t)1 << 40)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 16384);
-    hipLaunchKernelGGL(msda::matcher_cost_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, boxes, tgt_ids,
+    hipLaunchKernelGGL((msda::matcher_cost_kernel<T, TM>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, boxes, tgt_ids,
                        tgt_boxes, tgt_offsets, B, Q, C, (T)w_class, (T)w_bbox, (T)w_giou, (T)alpha, cost);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : (int)e;
+}
+
+// the LDS a launch of the solver needs, or a negative error: the host knows Q and the total number of targets only
+int lsap_sizes(int n_out, int B, int Q, int64_t n_targets, int *cols_cap, int *rows_cap, size_t *lds)
+{
+    if (n_out < 1 || B < 1 || Q < 0 || n_targets < 0) return MSDA_ERR_BAD_DIMS;
+    if (Q > msda::kLsapMaxDim || n_targets > msda::kLsapMaxDim || (int64_t)n_out * B >= ((int64_t)1 << 30)) return MSDA_ERR_TOO_LARGE;
+    *cols_cap = std::max(Q, (int)n_targets);
+    *rows_cap = std::min(Q, (int)n_targets);
+    *lds = msda::lsap_lds_bytes(*cols_cap, *rows_cap);
+    return MSDA_OK;
+}
+
+template <typename T>
+int lsap_impl(const T *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
+              int64_t *query_of_target, int32_t *status, msda_stream_t stream)
+{
+    if (!tgt_offsets || !status || (n_targets > 0 && (!query_of_target || (Q > 0 && !cost)))) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    int cols_cap = 0, rows_cap = 0;
+    size_t lds = 0;
+    const int rc = lsap_sizes(n_out, B, Q, n_targets, &cols_cap, &rows_cap, &lds);
+    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    if (lds > 64 * 1024) {      // beyond the default limit of dynamic LDS: raised once per device (the attribute is per kernel and device)
+        static bool raised[64] = {};
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return (int)e;
+        if (dev < 0 || dev >= 64 || !raised[dev]) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(msda::lsap_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)msda::lsap_lds_bytes(msda::kLsapMaxDim, msda::kLsapMaxDim));
+            if (e != hipSuccess) return (int)e;
+            if (dev >= 0 && dev < 64) raised[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL(msda::lsap_kernel<T>, dim3(n_out * B), dim3(64), lds, static_cast<hipStream_t>(stream), cost, target_major, tgt_offsets, B, Q,
+                       n_targets, cols_cap, rows_cap, query_of_target, status);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MSDA_OK : (int)e;
 }
@@ -514,6 +553,44 @@ int msda_matcher_cost_f64(const double *logits, const double *boxes, const int64
 {
     return matcher_cost_impl<double>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
                                      cost, stream);
+}
+
+int msda_matcher_cost_tm_f32(const float *logits, const float *boxes, const int64_t *tgt_ids, const float *tgt_boxes,
+                             const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
+                             double w_giou, double alpha, float *cost, msda_stream_t stream)
+{
+    return matcher_cost_impl<float, true>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
+                                          cost, stream);
+}
+int msda_matcher_cost_tm_f64(const double *logits, const double *boxes, const int64_t *tgt_ids, const double *tgt_boxes,
+                             const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
+                             double w_giou, double alpha, double *cost, msda_stream_t stream)
+{
+    return matcher_cost_impl<double, true>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
+                                           cost, stream);
+}
+
+int msda_lsap_workspace_bytes(int n_out, int B, int Q, int64_t n_targets, int64_t *bytes)
+{
+    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    int cols_cap = 0, rows_cap = 0;
+    size_t lds = 0;
+    const int rc = lsap_sizes(n_out, B, Q, n_targets, &cols_cap, &rows_cap, &lds);
+    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    *bytes = 0;      // every supported size keeps its state in LDS
+    return MSDA_OK;
+}
+int msda_lsap_f32(const float *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
+                  int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream)
+{
+    (void)workspace;
+    return lsap_impl<float>(cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
+}
+int msda_lsap_f64(const double *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
+                  int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream)
+{
+    (void)workspace;
+    return lsap_impl<double>(cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,11 @@ asynchronous copy and ONE event wait.  The assignment itself stays scipy's ``lin
 :func:`global_num_boxes` / :class:`AsyncLossLog` remove the two remaining per-step device round trips of the criterion and the
 engine (richsem.py:1143-1147, engine.py:84-91): the box count is known on the host and reduced there, the reduced loss dictionary
 for the log is read one step late.
+
+``HungarianMatcher(solver="device")`` / :meth:`HungarianMatcher.match_many_device` solve the assignment on the device instead
+(``msda_lsap_*``, csrc/msda_lsap.h): opt-in, the default stays the host path above.  With a :class:`CostPlan` built beforehand the device
+form neither waits nor copies anything to the host, so the whole training step can be one captured graph (bench_step.py
+``device_matcher``); :func:`pairs_from_query_of_target` turns its result into the criterion's index tensors.
 """
 import ctypes
 
@@ -31,6 +36,8 @@ class CostPlan:
     boxes (matcher.py:55-57)."""
 
     def __init__(self, targets, device, dtype):
+        self.device, self.dtype = torch.device(device), dtype
+        self.num_queries = None      # (set by match_many_device: the query count the last solve ran with)
         self.sizes = [int(v["boxes"].shape[0]) for v in targets]
         self.offsets = [0]
         for s in self.sizes:
@@ -44,10 +51,31 @@ class CostPlan:
             self.tgt_ids = torch.zeros(0, dtype=torch.int64, device=device)
             self.tgt_boxes = torch.zeros(0, 4, dtype=dtype, device=device)
 
+    @torch.no_grad()
+    def update_(self, targets):
+        """write another batch's labels, boxes and offsets into the device buffers this plan already has -- the same number of images and
+        the same TOTAL number of targets (the per-image counts may change), anything else raises -- so that a graph captured with this plan
+        solves the next batch on its next replay.  Host -> device copies on the current stream: call it between replays, not in a capture."""
+        sizes = [int(v["boxes"].shape[0]) for v in targets]
+        if len(sizes) != len(self.sizes):
+            raise ValueError(f"CostPlan.update_: {len(sizes)} images, the plan was built for {len(self.sizes)}")
+        if sum(sizes) != self.total:
+            raise ValueError(f"CostPlan.update_: {sum(sizes)} targets in all, the plan was built for {self.total}")
+        offsets = [0]
+        for n in sizes:
+            offsets.append(offsets[-1] + n)
+        self.sizes, self.offsets = sizes, offsets
+        self.offsets_dev.copy_(torch.tensor(offsets, dtype=torch.int64), non_blocking=True)
+        if self.total:
+            self.tgt_ids.copy_(torch.cat([v["labels"] for v in targets]).to(torch.int64), non_blocking=True)
+            self.tgt_boxes.copy_(torch.cat([v["boxes"] for v in targets]).to(self.dtype), non_blocking=True)
+        return self
 
-def cost_blocks(pred_logits, pred_boxes, plan, cost_class, cost_bbox, cost_giou, focal_alpha, out=None):
+
+def cost_blocks(pred_logits, pred_boxes, plan, cost_class, cost_bbox, cost_giou, focal_alpha, out=None, target_major=False):
     """Diagonal cost blocks of one decoder output on the device: a flat tensor of nq * plan.total elements, image b's (nq x T_b)
-    block starting at nq * plan.offsets[b].  ``out``: slice of a larger buffer to write into."""
+    block starting at nq * plan.offsets[b].  ``out``: slice of a larger buffer to write into.  ``target_major``: every block stored
+    (T_b x nq) instead -- the same values in the layout the device solver scans with unit stride (``msda_matcher_cost_tm_*``)."""
     if not pred_logits.is_cuda:
         raise RuntimeError("Not implemented on the CPU")
     dt = pred_logits.dtype
@@ -61,7 +89,7 @@ def cost_blocks(pred_logits, pred_boxes, plan, cost_class, cost_bbox, cost_giou,
         out = torch.empty(n, dtype=dt, device=logits.device)
     assert out.numel() == n and out.dtype == dt and out.is_contiguous()
     if n:
-        fn = getattr(_lib.load(), "msda_matcher_cost_" + ("f32" if dt == torch.float32 else "f64"))
+        fn = getattr(_lib.load(), ("msda_matcher_cost_tm_" if target_major else "msda_matcher_cost_") + ("f32" if dt == torch.float32 else "f64"))
         with _lib.on_device(logits.device):
             _lib.check(fn(logits.data_ptr(), boxes.data_ptr(), plan.tgt_ids.data_ptr(), plan.tgt_boxes.data_ptr(),
                           plan.offsets_dev.data_ptr(), bs, nq, C, plan.total, float(cost_class), float(cost_bbox), float(cost_giou),
@@ -78,11 +106,73 @@ def _assign(host, nq, plan):
     return res
 
 
-class HungarianMatcher(nn.Module):
-    """Same signature and result as the reference's class (matcher.py:8-78)."""
+LSAP_MAX_DIM = 4096      # msda_lsap_*: queries per output, and targets per batch (csrc/msda_lsap.h kLsapMaxDim)
 
-    def __init__(self, cost_class: float = 1, cost_bbox: float = 1, cost_giou: float = 1, focal_alpha=0.25):
+
+def lsap_supported(nq, total):
+    """whether the device solver takes ``nq`` queries against ``total`` targets in the batch (beyond: MSDA_ERR_TOO_LARGE, the host solves)"""
+    return nq <= LSAP_MAX_DIM and total <= LSAP_MAX_DIM
+
+
+def solve_blocks(cost, plan, n_out, nq, target_major=False):
+    """``msda_lsap_*`` on ``n_out`` consecutive cost buffers of nq * plan.total elements (float32 / float64, as :func:`cost_blocks` writes
+    them) -> (query_of_target (n_out, plan.total) int64, status (n_out, images) int32), see include/richsem_msda.h.  One launch; the
+    per-image counts are read from ``plan.offsets_dev`` by the kernel.  Nothing waits."""
+    if not cost.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    if cost.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError(f"lsap: float32 / float64 costs, got {cost.dtype}")
+    B = len(plan.sizes)
+    assert cost.is_contiguous() and cost.numel() == n_out * nq * plan.total
+    qot = torch.empty((n_out, plan.total), dtype=torch.int64, device=cost.device)
+    status = torch.empty((n_out, B), dtype=torch.int32, device=cost.device)
+    L = _lib.load()
+    nbytes = ctypes.c_int64(0)
+    _lib.check(L.msda_lsap_workspace_bytes(n_out, B, nq, plan.total, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=cost.device) if nbytes.value else None
+    fn = L.msda_lsap_f32 if cost.dtype == torch.float32 else L.msda_lsap_f64
+    with _lib.on_device(cost.device):
+        _lib.check(fn(cost.data_ptr(), int(bool(target_major)), plan.offsets_dev.data_ptr(), n_out, B, nq, plan.total, qot.data_ptr(),
+                      status.data_ptr(), ws.data_ptr() if ws is not None else None, _stream(cost.device)))
+    return qot, status
+
+
+def pairs_from_query_of_target(query_of_target, plan, num_queries=None):
+    """The criterion's index tensors from the device solver's result, as ``Step.pack_indices`` (bench_step.py) lays them out: with
+    ``query_of_target`` (n_out, total) of n_out - 1 decoder outputs followed by the two-stage output -> three (4, K) int64 tensors of rows
+    (layer, image, query, target): the decoder outputs' pairs (K = (n_out - 1) * total), the two-stage output's and the last decoder
+    layer's (K = total, layer 0).  Pure torch on the tensors' device (CPU tensors work too), nothing read back: a target's image comes from
+    ``plan.offsets_dev`` (which follows :meth:`CostPlan.update_`), a query left at -1 by an unsolved block is clamped to 0 -- the solver's
+    status, read late, is what reports it.  Pairs come in target order (the host path: query order); the pair SET is the same.
+    Every image must have at most ``num_queries`` targets (default: what the plan was last solved with), since the criterion's tensors hold
+    one pair per target: checked on the host from ``plan.sizes``."""
+    nq = plan.num_queries if num_queries is None else num_queries
+    if nq is not None and plan.sizes and max(plan.sizes) > nq:
+        raise ValueError(f"pairs_from_query_of_target: an image with {max(plan.sizes)} targets against {nq} queries leaves targets unmatched")
+    n_out, total = query_of_target.shape
+    assert total == plan.total and n_out >= 2
+    dev = query_of_target.device
+    tj = torch.arange(total, dtype=torch.int64, device=dev)
+    bi = torch.bucketize(tj, plan.offsets_dev[1:].to(dev), right=True)
+    si = query_of_target.clamp(min=0)
+
+    def rows(first, last):
+        n = last - first
+        li = torch.arange(n, dtype=torch.int64, device=dev)[:, None].expand(n, total)
+        return torch.stack((li.reshape(-1), bi.repeat(n), si[first:last].reshape(-1), tj.repeat(n)))
+    return rows(0, n_out - 1), rows(n_out - 1, n_out), rows(n_out - 2, n_out - 1)
+
+
+class HungarianMatcher(nn.Module):
+    """Same signature and result as the reference's class (matcher.py:8-78).  ``solver``: "host" (default) -- scipy's
+    ``linear_sum_assignment`` on cost blocks copied to the host; "device" -- the same assignment from ``msda_lsap_*`` on the GPU (equal to
+    scipy's wherever the optimum is unique; any optimal assignment where costs tie), read back for the reference's list format."""
+
+    def __init__(self, cost_class: float = 1, cost_bbox: float = 1, cost_giou: float = 1, focal_alpha=0.25, solver="host"):
         super().__init__()
+        if solver not in ("host", "device"):
+            raise ValueError(f'HungarianMatcher: solver must be "host" or "device", got {solver!r}')
+        self.solver = solver
         self.cost_class, self.cost_bbox, self.cost_giou = cost_class, cost_bbox, cost_giou
         assert cost_class != 0 or cost_bbox != 0 or cost_giou != 0, "all costs cant be 0"
         self.focal_alpha = focal_alpha
@@ -98,7 +188,57 @@ class HungarianMatcher(nn.Module):
         """Match several decoder outputs (each a dict with "pred_logits" (bs, nq_o, C) and "pred_boxes" (bs, nq_o, 4)) against the
         same targets: one cost kernel per output into one device buffer, one copy to the host, one wait.  Returns a list (per
         output) of the reference's per-image index pairs."""
+        if self.solver == "device":
+            first = outputs_list[0]["pred_logits"]
+            plan = CostPlan(targets, first.device, first.dtype)
+            if all(lsap_supported(o["pred_logits"].shape[1], plan.total) for o in outputs_list):
+                return self._lists_from_device(*self.match_many_device(outputs_list, plan), plan)
+            # (beyond the kernel's limits -- MSDA_ERR_TOO_LARGE -- the host path solves, as documented)
         return self.match_many_end(self.match_many_begin(outputs_list, targets))
+
+    @torch.no_grad()
+    def match_many_device(self, outputs_list, plan, target_major=True):
+        """Match several decoder outputs against the targets of ``plan`` (a :class:`CostPlan` built BEFOREHAND: its constructor copies host
+        data to the device) entirely on the device: cost kernels into one buffer, then one ``msda_lsap_*`` launch per run of outputs with
+        the same query count (one launch when all have it).  -> (query_of_target (n_out, plan.total) int64: the query matched to each
+        target, -1 where none; status (n_out, images) int32: 0 solved, non-zero see include/richsem_msda.h).  Nothing waits and nothing
+        reaches the host: safe inside ``torch.cuda.graph`` / ``make_graphed_callables`` after one eager call; ``plan.update_`` feeds a
+        captured call its next batch."""
+        first = outputs_list[0]["pred_logits"]
+        nqs = [o["pred_logits"].shape[1] for o in outputs_list]
+        dev_buf = torch.empty(sum(nq * plan.total for nq in nqs), dtype=first.dtype, device=first.device)
+        at, runs = 0, []
+        for o, nq in zip(outputs_list, nqs):
+            cost_blocks(o["pred_logits"], o["pred_boxes"], plan, self.cost_class, self.cost_bbox, self.cost_giou, self.focal_alpha,
+                        out=dev_buf[at: at + nq * plan.total], target_major=target_major)
+            if runs and runs[-1][1] == nq:
+                runs[-1][2] += 1
+            else:
+                runs.append([at, nq, 1])
+            at += nq * plan.total
+        parts = [solve_blocks(dev_buf[a: a + n * nq * plan.total], plan, n, nq, target_major) for a, nq, n in runs]
+        plan.num_queries = min(nqs)
+        if len(parts) == 1:
+            return parts[0]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    @staticmethod
+    def _lists_from_device(query_of_target, status, plan):
+        """the reference's format from the solver's result (reads it back: one wait); a block that was not solved raises as scipy does"""
+        st, qot = status.cpu(), query_of_target.cpu()
+        if bool((st != 0).any()):
+            o, b = (st != 0).nonzero()[0].tolist()
+            raise ValueError(f"matrix contains invalid numeric entries (output {o}, image {b}: solver status {int(st[o, b])})")
+        res = []
+        for row in qot:
+            per_image = []
+            for b in range(len(plan.sizes)):
+                q = row[plan.offsets[b]: plan.offsets[b + 1]]
+                j = (q >= 0).nonzero()[:, 0]
+                i, order = q[j].sort()
+                per_image.append((i, j[order]))
+            res.append(per_image)
+        return res
 
     @torch.no_grad()
     def match_many_begin(self, outputs_list, targets):
@@ -190,6 +330,42 @@ class AsyncLossLog:
 
     def flush(self):
         return self._finish()
+
+
+class LateStatus:
+    """The device solver's status (``match_many_device``) without a wait: ``push`` copies this step's status tensor to pinned memory behind
+    an event and checks the PREVIOUS step's -- a non-zero entry raises ValueError (scipy raises for the same inputs, at once) --, ``flush``
+    checks the last one.  The read is one step late, as :class:`AsyncLossLog`'s."""
+
+    def __init__(self):
+        self._pending = None
+
+    def _finish(self):
+        if self._pending is None:
+            return
+        host, event = self._pending
+        self._pending = None
+        if event is not None:
+            event.synchronize()
+        if bool((host != 0).any()):
+            o, b = (host != 0).nonzero()[0].tolist()
+            raise ValueError(f"matrix contains invalid numeric entries (the previous step's assignment: output {o}, image {b}, solver status "
+                             f"{int(host[o, b])})")
+
+    @torch.no_grad()
+    def push(self, status):
+        self._finish()
+        if status.is_cuda:
+            host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
+            host.copy_(status, non_blocking=True)
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(status.device))
+        else:
+            host, event = status.clone(), None
+        self._pending = (host, event)
+
+    def flush(self):
+        self._finish()
 
 
 class FocalNegativeSum(torch.autograd.Function):
