@@ -124,7 +124,6 @@ const char *msda_last_error(void);
  *   "profile_filter"  which calls msda_profile_enable brackets with its event pair: 0 (default) = every call; (kind + 1) * 16 + variant =
  *                     only those (kind 0 forward / 1 backward, variant as in msda_profile_record) -- an event pair costs a call ~4 us
  *   "tile_persist"    persistent workgroups walking the work items (default 512 = 2 per CU; 0 = one workgroup per item)
- *   "tile_debug"      diagnostic bits (stage-stamp kernel selection)
  * Unknown key or value out of range -> MSDA_ERR_BAD_OPTION.  Options change speed, never results. */
 int msda_set_option(const char *key, int value);
 int msda_get_option(const char *key, int *value);

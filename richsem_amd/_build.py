@@ -18,7 +18,7 @@ def _headers():
     import glob
     return sorted(glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(_PKG, "..", "include", "*.h")))
 HIPCC_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function"] + \
-    os.environ.get("RICHSEM_HIPCC_EXTRA", "").split()      # (diagnostic builds: -DRPS_ROUTE_ABLATION, -DCONV_RING_ABLATE=...)
+    os.environ.get("RICHSEM_HIPCC_EXTRA", "").split()      # (diagnostic builds: -Rpass-analysis=..., --save-temps)
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 STAMP = os.path.join(LIB_DIR, "build_flags.txt")      # the hipcc flags the library on disk was built with (part of the staleness key)
 

@@ -82,8 +82,8 @@ class ProfileRecord(ctypes.Structure):
 
 
 def lib_path():
-    """the product library -- or, for diagnostic runs only, the library RICHSEM_MSDA_LIB names (ablation builds are loaded from where they
-    were built: nothing ever overwrites the product .so)"""
+    """the product library -- or, for diagnostic runs only, the library RICHSEM_MSDA_LIB names (a library built elsewhere is loaded from where it
+    was built: nothing ever overwrites the product .so)"""
     return os.environ.get("RICHSEM_MSDA_LIB") or _build.LIB_PATH
 
 

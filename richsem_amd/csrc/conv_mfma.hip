@@ -428,16 +428,13 @@ struct RingRequest {
                                             const uint16_t *zero)
     {
         unsigned char *wdst = wring + (slot * WFR + wave * WPW) * 1024;
-#ifndef CONV_RING_ABLATE      // diagnostic builds (wrong results): 1 = no weight requests, 2 = no activation requests, 3 = neither
-#define CONV_RING_ABLATE 0
-#endif
 #pragma unroll
-        for (int i = 0; i < ((CONV_RING_ABLATE & 1) ? 0 : WPW); ++i)
+        for (int i = 0; i < WPW; ++i)
             __builtin_amdgcn_global_load_lds(wsrc[i], reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(wdst + i * 1024)),
                                              16, 0, 0);
         unsigned char *adst = aring + ((wave * R + slot) * AFR) * 1024;
 #pragma unroll
-        for (int h = 0; h < ((CONV_RING_ABLATE & 2) ? 0 : KT); ++h)
+        for (int h = 0; h < KT; ++h)
 #pragma unroll
             for (int t3 = 0; t3 < PT; ++t3)
                 __builtin_amdgcn_global_load_lds(asrc[t3] ? asrc[t3] + 64 * cb + 8 * h : zero,
@@ -535,7 +532,7 @@ void conv_ring_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict
     const unsigned wbase = (unsigned)(uintptr_t)wring + lane * 16, abase = (unsigned)(uintptr_t)aring + (wave * R * AFR) * 1024 + lane * 16;
     int slot = 0;
     for (int s = 0; s < S; ++s) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CONV_RING_ABLATE ? 0 : (R - 2) * NPI) : "memory");      // iteration s has landed (this wave's requests)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 2) * NPI) : "memory");      // iteration s has landed (this wave's requests)
         __builtin_amdgcn_s_barrier();                                              // ... everybody's; and slot (s - 1) % R is free
         rq.template request<R>(slot == 0 ? R - 1 : slot - 1, wave, S, cpb, x, g, img, hi0, wi0, q, wring, aring, zero);
         const unsigned wa = wbase + slot * (WFR * 1024), ba = abase + slot * (AFR * 1024);

@@ -217,14 +217,7 @@ __device__ __attribute__((aligned(16))) unsigned g_wgrad_zero_line[4];      // (
 constexpr int kRingStagePx = 32, kRingSlots = 4, kRingImage = kRingStagePx * 256, kRingSlotBytes = 2 * kRingImage;
 static_assert(kRingSlots * kRingSlotBytes == 2 * 2 * kImageBytes, "the ring is the old double buffer's LDS");
 
-#ifndef WGRAD_RING_ABLATE      // diagnostic builds (wrong results): 1 = no requests inside the loop, 2 = no products, 4 = no barrier, 8 = plain 8-byte reads, 16 = no MFMAs
-#define WGRAD_RING_ABLATE 0
-#endif
-#if WGRAD_RING_ABLATE & 8
-#define WG_TR_READ(dst, addr, byte_off) asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(byte_off))
-#else
 #define WG_TR_READ(dst, addr, byte_off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(byte_off))
-#endif
 #define WG_LDS_WAIT(n, a, b) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a), "+v"(b) : "n"(n))
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -289,7 +282,7 @@ __device__ __forceinline__ void wgrad_ring_products(f32x4 (&acc)[4][4], f32x4 (&
     WG_LDS_WAIT(NEWER, fa[A_][0], fa[A_][1]);                                                                                  \
     {                                                                                                                          \
         const bf16x8 a = WG_FRAG(fa[A_]);                                                                                      \
-        _Pragma("unroll") for (int b = 0; b < ((WGRAD_RING_ABLATE & 16) ? 1 : 4); ++b)                                         \
+        _Pragma("unroll") for (int b = 0; b < 4; ++b)                                                                          \
             acc[A_][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, WG_FRAG(fb[b]), acc[A_][b], 0, 0, 0);                      \
         if (BIAS && want_bias) bacc[A_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, ones, bacc[A_], 0, 0, 0);                 \
     }
@@ -299,11 +292,11 @@ __device__ __forceinline__ void wgrad_ring_products(f32x4 (&acc)[4][4], f32x4 (&
     // the matrix pipe's work instead of in front of it); the scheduling barriers keep the groups where they are written
     WG_ROW(0, 6)      // ... this wait: at most A tiles 1-3 (six reads) still in flight)
     __builtin_amdgcn_sched_barrier(0);
-    if (!(WGRAD_RING_ABLATE & 1)) rq.request_row(0, req_slot, g);
+    rq.request_row(0, req_slot, g);
     __builtin_amdgcn_sched_barrier(0);
     WG_ROW(1, 4)
     __builtin_amdgcn_sched_barrier(0);
-    if (!(WGRAD_RING_ABLATE & 1)) rq.request_row(1, req_slot, g);
+    rq.request_row(1, req_slot, g);
     __builtin_amdgcn_sched_barrier(0);
     WG_ROW(2, 2)
     __builtin_amdgcn_sched_barrier(0);
@@ -379,8 +372,7 @@ __device__ __forceinline__ void wgrad_block_ring(const uint16_t *__restrict__ dz
     int slot = 0;
     for (int st = 0; st < n_stage; ++st) {
         asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // this stage has landed (this wave's requests; two younger stages may be in flight)
-        if (!(WGRAD_RING_ABLATE & 4)) __builtin_amdgcn_s_barrier();      // ... everybody's; and the slot of stage st - 1 is free
-        if (WGRAD_RING_ABLATE & 2) { rq.request((slot + kRingSlots - 1) % kRingSlots, g); slot = (slot + 1) % kRingSlots; continue; }
+        __builtin_amdgcn_s_barrier();      // ... everybody's; and the slot of stage st - 1 is free
         wgrad_ring_products<BIAS>(acc, bacc, aa, ab, (unsigned)slot * kRingSlotBytes, want_bias, rq, (slot + kRingSlots - 1) % kRingSlots, g);      // (+ stage st + 3's requests)
         slot = (slot + 1) % kRingSlots;
     }

@@ -527,7 +527,6 @@ hipError_t launch_bwd_rps(const Problem &pb, const TV *value, const float *loc, 
     pl.g.entries = ws.rps_entries;
     pl.g.dummy = reinterpret_cast<float *>(ws.rps_entries + ws.rps_entries_cap);
     pl.g.stamps = msda::tiled_options().stamps;
-    pl.g.dbg = msda::tiled_options().dbg;
     auto kern = pl.g.stamps ? (pb.P == 4 ? &msda::rps_tile_kernel<true, TV, true> : &msda::rps_tile_kernel<false, TV, true>)
                             : (pb.P == 4 ? &msda::rps_tile_kernel<true, TV> : &msda::rps_tile_kernel<false, TV>);
     hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), sizeof(msda::RpsLds));
@@ -555,12 +554,6 @@ hipError_t launch_bwd_rps(const Problem &pb, const TV *value, const float *loc, 
                            grad_loc, grad_aw, pl.g);
     }
     const int grid = (cu_count() / msda::kXcds) * msda::kXcds;   // persistent: one workgroup per CU (its LDS is most of a CU's)
-#ifdef RPS_ROUTE_ABLATION
-    if (pl.g.dbg & 0x300) {      // diagnostic: route-pass ablations -- the records are not what the tile kernel expects; wrong results
-        rps_mark_dirty(stream);
-        return hipGetLastError();
-    }
-#endif
     hipLaunchKernelGGL(kern, dim3(grid > 0 ? grid : 8), dim3(msda::kRpsThreads), sizeof(msda::RpsLds), stream, value, grad_out,
                        grad_value, grad_acc, grad_loc, grad_aw, pl.g);
     if constexpr (!std::is_same<TV, float>::value)      // (every level has rows in the fp32 image: the tiles' shared first rows / columns at least)
@@ -578,7 +571,6 @@ hipError_t launch_bwd_band(const Problem &pb, const TV *value, const float *loc,
 {
     msda::BandPlan pl = msda::plan_band(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data());
     if (!pl.ok) return hipErrorNotSupported;
-    pl.g.dbg = msda::tiled_options().dbg & 63;
     pl.g.stamps = msda::tiled_options().stamps;
     if ((reinterpret_cast<uintptr_t>(grad_loc) | reinterpret_cast<uintptr_t>(loc)) & 7) return hipErrorNotSupported;
     constexpr uintptr_t row_align = sizeof(TV) * 4 - 1;   // 16 B (fp32) / 8 B (bf16) per lane access
@@ -675,7 +667,6 @@ __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restr
 //   pointer alignment demanded        sizeof(T); 2*sizeof(T) for loc / grad_loc     the same rule: 2 B data, 4 B weights, 8 B loc / grad_loc
 //   window forward eligible           f32 only; value, out 16-B aligned; plan ok    value, out 8-B aligned; plan ok  (both: rows of four)
 //   channels per lane                 widest <= 16 B that D and the pointers allow  widest <= 4 channels (8 B)
-//   tile_debug bit 128 (head-major)   honoured; keeps the call off the split kernel ignored
 //   split forward / backward          f32 only                                      yes
 //   "too many levels" (forward)       checked after the split kernel was considered before it  (a call the split kernel takes has L <= 32)
 //   routed / band backward entered    bwd_variant 4, or 0 with Lq == S (band: 5);   the same variants, and only with value / grad_out / grad_value
@@ -684,7 +675,6 @@ __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restr
 //   ... a launch error there          the profile record is given back              the profile record stays
 //   level-sum backward                f32: any subset of levels, the rest by        only when it takes ALL levels; else fp32 scratch + zero-fill +
 //                                     atomics after a zero-fill of grad_value;      direct kernel + one rounding pass
-//                                     sets lg.dbg
 //   bwd_direct_cpl option             honoured                                      ignored
 //   direct backward adds grad_value   into grad_value                               into the fp32 scratch (null when level-sum took everything)
 //   no scratch during stream capture  n/a                                           MSDA_ERR_BAD_DIMS
@@ -722,13 +712,12 @@ int forward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, con
 
     const int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, out});
     msda::DirectGeom g = direct_geom(pb, C);
-    if constexpr (!kBf16) g.head_major = (msda::tiled_options().dbg & 128) ? 1 : 0;      // (measured experiment: value read as (N, M, S, D))
     const size_t lds = msda::direct_lds_bytes<T>(g);
     if (kBf16 && lds > 64 * 1024) return too_many_levels(L);
     // small calls at D = 32 (decoder-shaped): 32 lanes per item, all of a lane's gathers in flight at once (fwd_split_kernel);
     // fwd_variant 3 forces it wherever it applies, 1 keeps the 8-lane kernel
     if constexpr (std::is_same<T, float>::value) {
-        if (split_fits(pb, C) && !g.head_major && (variant == 3 || (variant != 1 && split_small(pb)))) {
+        if (split_fits(pb, C) && (variant == 3 || (variant != 1 && split_small(pb)))) {
             ProfileScope prof(0, 3, (int)sizeof(TV), pb, stream);
             const hipError_t e = launch_fwd_split<TV>(pb, value, shapes, lsi, loc, aw, out, g, stream);
             if (e != hipSuccess) return hip_fail(e, "launch of the split forward kernel", kTag);
@@ -863,7 +852,6 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
             // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
             // for element alignment only)
             const bool vec = P == 4 && is_aligned(loc, 16) && is_aligned(aw, 16);
-            if constexpr (!kBf16) lg.dbg = msda::tiled_options().dbg & 7;
             auto kern = vec ? &msda::bwd_levelsum_kernel<true, TV> : &msda::bwd_levelsum_kernel<false, TV>;
             if ((e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), ls_lds)) != hipSuccess)
                 return hip_fail(e, kBf16 ? "LDS limit" : "launch of the level-sum backward kernel");
@@ -1065,40 +1053,38 @@ int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi
 }
 
 // The options: one table read by msda_set_option and msda_get_option.  A value is accepted when it lies in [lo, hi] and, where `values`
-// is not 0, bit `value` of it is set.  hi < lo: the option cannot be set; !readable: it cannot be read.
+// is not 0, bit `value` of it is set.  hi < lo: the option cannot be set.
 namespace {
 struct Option {
     const char *key;
     std::atomic<int> *at;
     int lo, hi;
     unsigned values;
-    bool readable;
 };
 const Option *find_option(const char *key)
 {
     static const Option table[] = {
-        {"fwd_variant", &g_fwd_variant, 0, 3, 0, true},
-        {"fwd_prep_fused", &g_fwd_prep_fused, 0, 2, 0, true},      // 1: decoder-shaped calls; 2: + encoder-shaped
-        {"bwd_variant", &g_bwd_variant, 0, 5, 1u << 0 | 1u << 1 | 1u << 4 | 1u << 5, true},
-        {"band_lds_kb", &msda::band_options().lds_kb, 16, 150, 0, true},
-        {"band_hits", &msda::band_options().hits, 32, 65536, 0, true},
-        {"rps_tile", &msda::rps_options().tile, 4, 16, 0, true},
-        {"rps_max_chunks", &msda::rps_options().max_chunks, 1, 4096, 0, true},
-        {"rps_route_wgs", &msda::rps_options().route_wgs, 1, 64, 0, true},
-        {"rps_seg_shift", &msda::rps_options().seg_shift, 3, 11, 0, true},
-        {"rps_order", &msda::rps_options().order, 0, 1, 0, true},
-        {"bwd_direct_cpl", &g_bwd_cpl, 0, 4, 1u << 0 | 1u << 1 | 1u << 2 | 1u << 4, true},
-        {"tile_region", &msda::tiled_options().region_px, 4, 64, 0, true},
-        {"tile_margin", &msda::tiled_options().margin, 0, 32, 0, true},
-        {"tile_debug", &msda::tiled_options().dbg, 0, 65535, 0, false},
-        {"tile_persist", &msda::tiled_options().persist, 0, 65536, 0, true},
-        {"bwd_levelsum", &g_levelsum, 0, 1, 0, true},
-        {"bwd_split", &g_bwd_split, 0, 1, 0, true},
-        {"profile_filter", &g_prof_filter, 0, 47, 0, true},
-        {"levelsum_lds_kb", &msda::levelsum_lds_kb(), 8, 150, 0, true},
-        {"tile_grow", &msda::tiled_options().grow, 0, 1, 0, true},
-        {"locality_monitor", &g_monitor_on, 0, 1, 0, true},
-        {"locality_share_ppm", &g_last_share_ppm, 0, -1, 0, true},   // read-only
+        {"fwd_variant", &g_fwd_variant, 0, 3, 0},
+        {"fwd_prep_fused", &g_fwd_prep_fused, 0, 2, 0},      // 1: decoder-shaped calls; 2: + encoder-shaped
+        {"bwd_variant", &g_bwd_variant, 0, 5, 1u << 0 | 1u << 1 | 1u << 4 | 1u << 5},
+        {"band_lds_kb", &msda::band_options().lds_kb, 16, 150, 0},
+        {"band_hits", &msda::band_options().hits, 32, 65536, 0},
+        {"rps_tile", &msda::rps_options().tile, 4, 16, 0},
+        {"rps_max_chunks", &msda::rps_options().max_chunks, 1, 4096, 0},
+        {"rps_route_wgs", &msda::rps_options().route_wgs, 1, 64, 0},
+        {"rps_seg_shift", &msda::rps_options().seg_shift, 3, 11, 0},
+        {"rps_order", &msda::rps_options().order, 0, 1, 0},
+        {"bwd_direct_cpl", &g_bwd_cpl, 0, 4, 1u << 0 | 1u << 1 | 1u << 2 | 1u << 4},
+        {"tile_region", &msda::tiled_options().region_px, 4, 64, 0},
+        {"tile_margin", &msda::tiled_options().margin, 0, 32, 0},
+        {"tile_persist", &msda::tiled_options().persist, 0, 65536, 0},
+        {"bwd_levelsum", &g_levelsum, 0, 1, 0},
+        {"bwd_split", &g_bwd_split, 0, 1, 0},
+        {"profile_filter", &g_prof_filter, 0, 47, 0},
+        {"levelsum_lds_kb", &msda::levelsum_lds_kb(), 8, 150, 0},
+        {"tile_grow", &msda::tiled_options().grow, 0, 1, 0},
+        {"locality_monitor", &g_monitor_on, 0, 1, 0},
+        {"locality_share_ppm", &g_last_share_ppm, 0, -1, 0},   // read-only
     };
     for (const Option &o : table)
         if (key && !strcmp(key, o.key)) return &o;
@@ -1144,7 +1130,7 @@ int msda_get_option(const char *key, int *value)
 {
     if (!value) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
     const Option *o = find_option(key);
-    if (!o || !o->readable) return fail(MSDA_ERR_BAD_OPTION, "unknown option: %s", key ? key : "(null)");
+    if (!o) return fail(MSDA_ERR_BAD_OPTION, "unknown option: %s", key ? key : "(null)");
     *value = *o->at;
     return MSDA_OK;
 }

@@ -49,7 +49,6 @@ inline BandOptions &band_options()
 struct BandGeom {
     int N, S, M, Lq, L, P;
     int nent;
-    int dbg;          // diagnostic (wrong results): 1 skip the reduce stage, 2 skip the scan, 4 skip zeroing and flush, 8 no value rows / dots
     unsigned long long *stamps;      // diagnostic runs only (msda_debug_stamps): per workgroup 8 words -- start, end of zero / scan / reduce / flush, entry, items
     int H[kBandMaxLevels], W[kBandMaxLevels], start[kBandMaxLevels];
     // entry e: rows [r0, r0 + nr) of level lev; slab `slab` of `nslab` (the level's points dealt over nslab workgroups by point index)
@@ -178,7 +177,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
 #pragma unroll
             for (int p = 0; p < 4; ++p) sxy[u][p] = *reinterpret_cast<const float2 *>(loc + 2u * (spt0[u] + (unsigned)min(p, snp[u] - 1)));
         }
-        if (c0 == i_lo && !(g.dbg & 4))
+        if (c0 == i_lo)
             for (int i = tid; i < npx * kBandStride; i += kBandThreads) win[i] = 0.0;
         if (tid == 0) *cnt = 0;
         __syncthreads();
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
 #pragma unroll
         for (int u = 0; u < kPer; ++u) {
             const int it = c0 + u * kBandThreads + tid;
-            const bool in_range = it < c0 + s_here && !(g.dbg & 2);
+            const bool in_range = it < c0 + s_here;
             const unsigned pt0 = spt0[u];
             const int np = snp[u];
             unsigned hitm = 0u, ownm = 0u;
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
         }
         __syncthreads();
         if (g.stamps) { st[2] = __builtin_amdgcn_s_memtime(); st_items += *cnt; }
-        const int n = (g.dbg & 1) ? 0 : *cnt;
+        const int n = *cnt;
         // ---- reduce: a group of eight lanes per listed item; the NEXT item's first loads (its entry, grad_out row, locations, weights) travel
         //      under this item's work -------------------------------------------------------------------------------------------------------------
         struct Head {
@@ -272,7 +271,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
                     lw[u] = w_im - wf;
                     row0[u] = (int)hf;
                     col0[u] = (int)wf;
-                    const bool own = (ownm >> p & 1u) && !(g.dbg & 8);
+                    const bool own = ownm >> p & 1u;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {      // (corners that do not count fetch the level's first row: a cache hit)
                         const int rr = row0[u] + (k >> 1), cc = col0[u] + (k & 1);
@@ -292,7 +291,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const int rr = row0[u] + (k >> 1), cc = col0[u] + (k & 1);
-                        if (rr >= r0 && rr < r0 + nr && rr <= H - 1 && cc >= 0 && cc <= W - 1 && !(g.dbg & 16)) {      // (rr >= r0 >= 0)
+                        if (rr >= r0 && rr < r0 + nr && rr <= H - 1 && cc >= 0 && cc <= W - 1) {      // (rr >= r0 >= 0)
                             double *dst = win + (size_t)((rr - r0) * W + cc) * kBandStride + j;      // slot 8 * i + j <- channel 4 * j + i
                             atomicAdd(dst, (double)(wgt[k] * ga.x));
                             atomicAdd(dst + 8, (double)(wgt[k] * ga.y));
@@ -300,7 +299,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
                             atomicAdd(dst + 24, (double)(wgt[k] * ga.w));
                         }
                     }
-                    if ((ownm >> p & 1u) && !(g.dbg & 32)) {      // (uniform over the group)
+                    if (ownm >> p & 1u) {      // (uniform over the group)
                         float d[4];
 #pragma unroll
                         for (int k = 0; k < 4; ++k)
@@ -318,13 +317,12 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
         __syncthreads();
     }
     if (i_lo >= i_hi) {      // (a slab past the level's last item: nothing to add, but the window is still flushed)
-        if (!(g.dbg & 4)) for (int i = tid; i < npx * kBandStride; i += kBandThreads) win[i] = 0.0;
+        for (int i = tid; i < npx * kBandStride; i += kBandThreads) win[i] = 0.0;
         __syncthreads();
     }
     if (g.stamps) st[3] = __builtin_amdgcn_s_memtime();
 
     // ---- flush: a pixel's 128-B row per lane group --------------------------------------------------------------------------------------------------
-    if (g.dbg & 4) return;
     const int64_t base = (lvl_base + r0 * W) * g.M * kBandD + (int64_t)m * kBandD + c4;
     if (nslab == 1) {
         for (int px = grp; px < npx; px += kGroups) {

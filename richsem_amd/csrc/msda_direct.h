@@ -32,7 +32,6 @@ struct DirectGeom {
     int qtile, ntiles;     // queries per block, tiles per (b,m) pair
     int pbatch;            // sampling points staged in LDS per pass: min(L*P, kPointBatch)
     unsigned gv_skip;      // backward: bit l set = grad_value of level l is produced elsewhere (msda_levelsum.h)
-    int head_major;        // forward, measured experiment (round 4): value is (N, M, S, D) instead of the reference's (N, S, M, D)
 };
 
 constexpr int kDirectThreads = 256;
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(kDirectThreads, OCC) void fwd_direct_kernel(
     const int j = lane & (g.G - 1);               // lane within the group
     const int slot = wave * ipw + (lane >> g.logG);
     const int LP = g.L * g.P;
-    const int row_elems = g.head_major ? g.D : g.M * g.D;
+    const int row_elems = g.M * g.D;
     PointRec<T> *my = recs + slot * (g.pbatch + 1);
 
     const int q_end = min((tile + 1) * g.qtile, g.Lq);
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(kDirectThreads, OCC) void fwd_direct_kernel(
                         PointRec<T> r;
                         T lh, lw;
                         resolve_point<T>(xy.v[0], xy.v[1], G_.H, G_.W,
-                                         g.head_major ? ((b * g.M + m) * g.S + G_.start) * g.D : (b * g.S + G_.start) * row_elems + m * g.D,
+                                         (b * g.S + G_.start) * row_elems + m * g.D,
                                          row_elems, r.o, lh, lw);
                         const T hh = (T)1 - lh, hw = (T)1 - lw;
                         r.f[0] = hh * hw * a;

@@ -30,7 +30,6 @@ inline std::atomic<int> &levelsum_lds_kb()   // window size: 150 KB = one workgr
 struct LevelSumGeom {
     int N, S, M, D, L, Lq, P;
     int nlev, nslices;   // entries, channel slices
-    int dbg;             // diagnostic (wrong results): 1 skip the walk, 2 skip the flush, 4 skip zeroing
     // entry = a band of rows [r0, r0 + nr) of level lev (the whole level when it fits LDS)
     int lev[kLsMaxLevels], H[kLsMaxLevels], W[kLsMaxLevels], start[kLsMaxLevels], r0[kLsMaxLevels], nr[kLsMaxLevels];
 };
@@ -115,13 +114,13 @@ __global__ __launch_bounds__(kLsThreads) void bwd_levelsum_kernel(const float *_
     const int ch = slice * kLsChan + j;
     const bool has_ch = ch < g.D;
 
-    if (!(g.dbg & 4)) for (int e = tid; e < npx * kLsChan; e += kLsThreads) win[e] = 0.0;
+    for (int e = tid; e < npx * kLsChan; e += kLsThreads) win[e] = 0.0;
     __syncthreads();
 
     const int LP = g.L * g.P;
     // query-major walk: a lane group takes a query and its P points of this level (kLsUnroll at a time, all loads first) -- no
     // index divisions in the loop, grad_out read once per query
-    for (int q = grp; q < ((g.dbg & 1) ? 0 : g.Lq); q += kGroups) {
+    for (int q = grp; q < g.Lq; q += kGroups) {
         const unsigned item = (unsigned)((b * g.Lq + q) * g.M + m);
         const unsigned pt0 = item * (unsigned)LP + (unsigned)(l * g.P);
         const float go = has_ch ? ld1(grad_out + item * (unsigned)g.D + ch) : 0.f;
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(kLsThreads) void bwd_levelsum_kernel(const float *_
 
     // every pixel of the slice, once: 16 B per lane group
     TV *dst = grad_value + ((int64_t)(b * g.S + g.start[li] + r0 * W) * g.M + m) * g.D + ch;
-    if (has_ch && !(g.dbg & 2))
+    if (has_ch)
         for (int px = grp; px < npx; px += kGroups) dst[(int64_t)px * g.M * g.D] = to_storage<TV, float>((float)win[px * kLsChan + j]);
 }
 

@@ -40,15 +40,11 @@
 
 namespace msda {
 
-#ifndef RPS_THREADS
-#define RPS_THREADS 768
-#define RPS_RPL 2
-#endif
-constexpr int kRpsThreads = RPS_THREADS;               // 12 waves = 3 per SIMD, 168 registers per lane (1024 threads at 128 registers spilled; 512 threads: same speed)
+constexpr int kRpsThreads = 768;               // 12 waves = 3 per SIMD, 168 registers per lane (1024 threads at 128 registers spilled; 512 threads: same speed)
 constexpr int kRpsWaves = kRpsThreads / 64;
 constexpr int kRpsMaxPx = 256;                  // pixel grid of a tile (tile + one row / column): bound by LDS (f64 sums + value rows)
 constexpr int kRpsPpq = (kRpsMaxPx + kRpsThreads / 4 - 1) / (kRpsThreads / 4);   // pixels per quad where a quad stands for a pixel
-constexpr int kRpsRpl = RPS_RPL;                      // records per lane and chunk
+constexpr int kRpsRpl = 2;                      // records per lane and chunk
 constexpr int kRpsChunk = kRpsRpl * kRpsThreads;   // sampling points per chunk
 constexpr int kRpsSumStride = 36;               // doubles per pixel of the f64 sums (see RpsLds)
 constexpr int kRpsSegShift = 3;                 // SMALLEST unit of the list walk: 1 << 3 = 8 points (the units' length is RpsOptions::seg_shift, default 4: <= 16 points)
@@ -103,8 +99,6 @@ struct RpsGeom {
     float *dummy;                   // kRpsDummyBytes of scratch: where the lanes that have nothing to store send their stores
                                     // (every store instruction is then issued unconditionally: see rps_tile_kernel)
     unsigned long long *stamps;     // diagnostic runs only (msda_debug_stamps)
-    int dbg;                        // diagnostic: bits 4..6 = 1 + level -> only that level's tiles do any work (wrong results); bit 3: walk units in list order (A/B of the length classes);
-                                    // bits 8..9, builds with -DRPS_ROUTE_ABLATION only: route-pass ablations (the tile kernel is not launched): 256 no record stores, 512 4-byte records
 };
 
 // One sampling point in the list of its base pixel; overwritten by its four corner dots.  The walk is bound by instruction issue (round 5:
@@ -171,7 +165,7 @@ __device__ __forceinline__ int rps_wave_scan(int v)
 
 // Where a sampling position falls, per level, comes from two small tables in LDS (round 4) -- one entry per base row r = h_low + 1 in
 // [0, H] and one per base column c = w_low + 1 in [0, W] -- instead of ~35 vector instructions of tile arithmetic per point and level
-// (the route pass is bound by instruction issue: ~2400 instructions per wave and work item before, profiles/r04_route_ablation.md):
+// (the route pass is bound by instruction issue: ~2400 instructions per wave and work item before, profiles/r04_experiments.md):
 //   row entry     gr (bits 0..4) | inr << 6 | (ty * ntx * nslab) << 8
 //   column entry  gc (bits 0..4) | inc << 6 | (tx * nslab) << 8 | gw << 17
 // gr / gc: base-grid row / column inside the owner tile (the tile that holds the point's upper-left corner; row / column 0 of the grid is
@@ -220,10 +214,7 @@ static_assert(kRpsMaxUnits <= 512, "route pass: one thread per bin of a pair");
 // scalar registers the generic form spills go away (round 5: 1150 -> ~700 instructions per wave and work item).  kStamps: the diagnostic
 // stage stamps (msda_debug_stamps) are compiled into a second instance only.
 template <int kRpsRouteThreads, int kL = 0, int kP = 0, bool kStamps = false>
-#ifndef RPS_ROUTE_OCC
-#define RPS_ROUTE_OCC 4      // waves per SIMD the 8-wave form is compiled for (two workgroups per CU)
-#endif
-__global__ __launch_bounds__(kRpsRouteThreads, kRpsRouteThreads == 512 ? RPS_ROUTE_OCC : 4) void rps_route_kernel(const float *__restrict__ loc, const float *__restrict__ aw,
+__global__ __launch_bounds__(kRpsRouteThreads, 4) void rps_route_kernel(const float *__restrict__ loc, const float *__restrict__ aw,      // (4 waves per SIMD: two 8-wave workgroups per CU)
                                                                      float *__restrict__ grad_value, float *__restrict__ grad_loc,
                                                                      float *__restrict__ grad_aw, const RpsGeom g)
 {
@@ -456,10 +447,6 @@ __global__ __launch_bounds__(kRpsRouteThreads, kRpsRouteThreads == 512 ? RPS_ROU
             if (w != ~0u) {
                 const unsigned slot = min(slot0[l] + ((w >> 9) & 16383u), g.entries_cap - 1u);
                 const unsigned code = qp | (w >> 23) << kRpsQpBits | inmap[l] << 27 | 0x80000000u;
-#ifdef RPS_ROUTE_ABLATION      // (diagnostic build, profiles/r04_route_ablation.md: what the record stores cost)
-                if (g.dbg & 512) reinterpret_cast<unsigned *>(g.entries)[slot] = code;
-                else if (!(g.dbg & 256))
-#endif
                 g.entries[slot] = RpsRec{code, lh[l], lw[l], at[l]};
             }
         }
@@ -597,8 +584,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
         const unsigned unit = (unsigned)rps_uni((int)g.units[min(id, n_items - 1) / g.ppx]);
         const int pr = xq + kXcds * (min(id, n_items - 1) % g.ppx);
         const int pair = min(pr, pairs - 1);
-        // (diagnostic: dbg bits 4..6 = 1 + level -> only that level's units do any work)
-        it.live = id < n_items && pr < pairs && (((g.dbg >> 4) & 7) == 0 || ((g.dbg >> 4) & 7) == (int)(unit & 3) + 1);
+        it.live = id < n_items && pr < pairs;
         it.l = unit & 3;
         const int ty = (unit >> 2) & 63, tx = (unit >> 8) & 63;
         it.b = pair / g.M;
@@ -797,7 +783,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                     v = c | ((c + (1 << sh) - 1) >> sh) << 16;
                     n_full = c >> sh;
                     part = c & ((1 << sh) - 1);
-                    pslot = part ? ((g.dbg & 8) ? 0 : 3 - ((part - 1) >> (sh - 2))) : -1;   // (dbg 8: A/B, units in list order)
+                    pslot = part ? 3 - ((part - 1) >> (sh - 2)) : -1;
                     n0 = n_full + (pslot == 0 ? 1 : 0);      // this list's units of slot 0: its full ones, then a nearly full last one
                     incl = rps_wave_scan(v);
                     incl0 = rps_wave_scan(n0);
@@ -929,13 +915,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                     // of point e + 2 is being read (the chain entry -> row address -> row is what a walk waits for).  Only the
                     // row offset is read ahead; the weight's two words are read when the point is reduced (registers).
                     // (entries are addressed by BYTE offset into the chunk's entry array: one add per two points)
-#if defined(RPS_WALK_ABLATE) && RPS_WALK_ABLATE == 1      // (diagnostic: no row requests at all -- wrong results)
-#define RPS_ROW(OFF, ROW) asm volatile("" : "+v"(ROW.a.x), "+v"(ROW.a.y), "+v"(ROW.b.x), "+v"(ROW.b.y), "+v"(OFF));
-#elif defined(RPS_WALK_ABLATE) && RPS_WALK_ABLATE == 2    // (diagnostic: every request hits one of 64 rows -- wrong results)
-#define RPS_ROW(OFF, ROW) ROW.load(grad_out, ((OFF) & 0x1F80u) + lane_row);
-#else
 #define RPS_ROW(OFF, ROW) ROW.load(grad_out, (OFF) + lane_row);
-#endif
 #define RPS_OFF(EP) (*RPS_LDS(const unsigned, (EP) + 12u))
                     // (ep = LDS ADDRESS of the entry: the array's base is added once, behind an opaque asm -- derived from the symbol inside
                     // the loop, every address costs an extra add of the "+ 0" the LDS layout pass leaves behind)
@@ -987,13 +967,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                         if (ok) {
                             double *dst = S->sum + (my_p - (k < 2 ? gw : 0) - ((k & 1) ? 0 : 1)) * kRpsSumStride + j4;
 #pragma unroll
-#if defined(RPS_EPI_ABLATE) && RPS_EPI_ABLATE == 1      // (diagnostic: no f64 atomics -- wrong results; the sums are kept alive by one plain store)
-                            for (int m_ = 0; m_ < 1; ++m_) *reinterpret_cast<float *>(dst) = macc[0][k] + macc[1][k] + macc[2][k] + macc[3][k] + macc[4][k] + macc[5][k] + macc[6][k] + macc[7][k];
-#elif defined(RPS_EPI_ABLATE) && RPS_EPI_ABLATE == 2    // (diagnostic: plain f64 read-modify-write instead of atomics -- racy, wrong results)
-                            for (int m_ = 0; m_ < 8; ++m_) dst[4 * m_] += (double)macc[m_][k];
-#else
                             for (int m_ = 0; m_ < 8; ++m_) atomicAdd(dst + 4 * m_, (double)macc[m_][k]);
-#endif
                         }
                     }
                 }

@@ -62,7 +62,6 @@ struct TiledGeom {
     short cq0[kTL][kMaxGrid + 1], cw0[kTL][kMaxGrid], cwn[kTL][kMaxGrid];
     unsigned long long *stamps;   // diagnostic builds of a run only: per-workgroup s_memtime stamps (16 per workgroup), or null
     unsigned *stats;              // forward, optional: stats[0] += points that missed their window (locality monitor), or null
-    int dbg;               // diagnostic: bits 4..5 select the kernel that writes stage stamps (0 = all, 1 = scatter, 2 = gather)
 };
 
 // ---- region geometry (host and device) --------------------------------------------------------------
@@ -125,7 +124,6 @@ struct TiledOptions {
     std::atomic<int> persist{512};    // 0 = one workgroup per work item; n > 0 = at most n workgroups (n/2 for the 1024-thread kernels)
                                       // walking the items (2 x 256 CUs by default: no per-item launch ramp)
     std::atomic<int> grow{1};         // 1 = windows grow into the LDS their phase leaves unused (per-level margins)
-    std::atomic<int> dbg{0};
     std::atomic<unsigned long long *> stamps{nullptr};
     std::atomic<unsigned *> stats{nullptr};   // diagnostic override of the locality counter (msda_debug_stats)
 };
@@ -158,7 +156,6 @@ inline TiledPlan plan_tiled(int N, int S, int M, int D, int L, int Lq, int P, co
     TiledGeom &g = pl.g;
     g.N = N; g.S = S; g.M = M; g.Lq = Lq; g.L = L; g.P = P;
     g.margin = margin;
-    g.dbg = tiled_options().dbg;
     g.stamps = tiled_options().stamps;
     g.stats = tiled_options().stats;
     int Hmax = 0, Wmax = 0;
@@ -262,10 +259,9 @@ inline TiledPlan plan_tiled(int N, int S, int M, int D, int L, int Lq, int P, co
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Diagnostic only (g.stamps is null in normal runs): slot i of this workgroup's stamp row <- shader clock.
-template <int KERNEL>   // 1 = scatter, 2 = gather; dbg bits 4..5 select one kernel (0 = all)
 __device__ __forceinline__ void stamp(const TiledGeom &g, int i)
 {
-    if (g.stamps && threadIdx.x == 0 && (((g.dbg >> 4) & 3) == 0 || ((g.dbg >> 4) & 3) == KERNEL)) {
+    if (g.stamps && threadIdx.x == 0) {
         const unsigned long long wg = blockIdx.x + (unsigned long long)gridDim.x * (blockIdx.y + (unsigned long long)gridDim.y * blockIdx.z);
         g.stamps[wg * 16 + i] = __builtin_amdgcn_s_memtime();
     }
@@ -636,17 +632,15 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
     const int region = rs / nsub, sub = rs - region * nsub;
     const int b = pair / g.M, m = pair - b * g.M;
     const int gy = region / g.GX, gx = region - gy * g.GX;
-    stamp<2>(g, 0);
+    stamp(g, 0);
     const int nq = build_header(hdr, g, gy, gx);
-    stamp<2>(g, 1);
+    stamp(g, 1);
 
     const int tid = threadIdx.x;
     const int j = tid & (GL - 1), grp = tid / GL;
     const int fj = tid & (FL - 1), fgrp = tid / FL;
-    // value layout: the reference's (N, S, M, D) -- a pixel's row of one head every M * D elements -- or, as a measured experiment
-    // (round 4, dbg bit 7; SURVEY.md section 8f rank 1 "head-major value layout"), (N, M, S, D): rows of a head contiguous
-    const bool head_major = g.dbg & 128;
-    const int row_elems = head_major ? kTD : g.M * kTD;
+    // value layout: the reference's (N, S, M, D) -- a pixel's row of one head every M * D elements
+    const int row_elems = g.M * kTD;
     const int LP = g.L * g.P;
 
     bool live[kGatherQPG];
@@ -701,13 +695,9 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
             else load_level_ops(loc, aw, item, (unsigned)LP, (unsigned)(lb * g.P), g.P, j, nxt);
             // ---- stage this phase's windows: 64-B pixel half-rows, 16 B per lane -------------------------------------
             for (int l = lb; l < le; ++l) {
-#if defined(FWD_ABLATE) && FWD_ABLATE == 1      // (diagnostic: no window fills -- wrong results)
-                continue;
-#endif
                 const int wr0 = uni(hdr->r[l].wr0), wc0 = uni(hdr->r[l].wc0), nwc = uni(hdr->r[l].nwc);
                 const int npx = uni(hdr->r[l].nwr) * nwc, Wl = uni(hdr->W[l]), Hl = uni(hdr->H[l]);
-                const TV *src = value + (head_major ? ((int64_t)(b * g.M + m) * g.S + uni(hdr->start[l])) * kTD
-                                                    : ((int64_t)(b * g.S + uni(hdr->start[l])) * g.M + m) * kTD) + half * GC + 4 * fj;
+                const TV *src = value + ((int64_t)(b * g.S + uni(hdr->start[l])) * g.M + m) * kTD + half * GC + 4 * fj;
                 float *dst = win + (int64_t)uni(hdr->lds_px[l]) * GC + 4 * fj;
                 // kFillBatch independent loads in flight per lane before the first LDS store.  Straight-line code (round 4): the pixel index
                 // is clamped for the load AND for the store -- lanes past the window's end re-store its last pixel, the same value to the
@@ -716,28 +706,26 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
                 // (exact: (px + 0.5) / nwc is at least 0.5 / nwc away from an integer), not from a 20-instruction integer division.
                 const float inv_nwc = 1.0f / (float)nwc;
                 if constexpr (sizeof(TV) == 4 && FL == 4) {
-                    if (!(g.dbg & 256)) {
-                        // fp32 value (round 4): the window rows by LDS DMA: lane l of a wave writes 16 B at (base + 16 l) = pixel l / 4, quarter
-                        // l % 4 of the wave's 16 consecutive window pixels -- no staging registers, no LDS store instructions; lanes past
-                        // the window's end are masked off, pixels of the zero apron fetch a zero line.  114.2 -> 108.5 us at the init pattern,
-                        // 145.5 -> 140.5 us at sigma = 4 (tools/r04_dma_fill.py, same box; tile_debug bit 8 = the register-staged fill below,
-                        // which bf16 storage keeps: its rows are converted on the way)
-                        const int wave_px = (tid >> 6) * 16;
-                        for (int px0 = 0; px0 < npx; px0 += kFillGroups) {
-                            const int px = px0 + fgrp;
-                            if (px < npx) {
-                                const int rr = (int)(((float)px + 0.5f) * inv_nwc), cc = px - rr * nwc;
-                                const int row = wr0 + rr, col = wc0 + cc;
-                                const bool in = row >= 0 && row < Hl && col >= 0 && col < Wl;
-                                const float *sp = in ? reinterpret_cast<const float *>(src) + (int64_t)(row * Wl + col) * row_elems
-                                                     : reinterpret_cast<const float *>(g_tiled_zero_line);
-                                float *dp = win + (int64_t)(uni(hdr->lds_px[l]) + px0 + wave_px) * GC;
-                                __builtin_amdgcn_global_load_lds(sp, reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(dp)),
-                                                                 16, 0, 0);
-                            }
+                    // fp32 value (round 4): the window rows by LDS DMA: lane l of a wave writes 16 B at (base + 16 l) = pixel l / 4, quarter
+                    // l % 4 of the wave's 16 consecutive window pixels -- no staging registers, no LDS store instructions; lanes past
+                    // the window's end are masked off, pixels of the zero apron fetch a zero line.  114.2 -> 108.5 us at the init pattern,
+                    // 145.5 -> 140.5 us at sigma = 4 (same box; the register-staged fill below is what bf16 storage keeps:
+                    // its rows are converted on the way)
+                    const int wave_px = (tid >> 6) * 16;
+                    for (int px0 = 0; px0 < npx; px0 += kFillGroups) {
+                        const int px = px0 + fgrp;
+                        if (px < npx) {
+                            const int rr = (int)(((float)px + 0.5f) * inv_nwc), cc = px - rr * nwc;
+                            const int row = wr0 + rr, col = wc0 + cc;
+                            const bool in = row >= 0 && row < Hl && col >= 0 && col < Wl;
+                            const float *sp = in ? reinterpret_cast<const float *>(src) + (int64_t)(row * Wl + col) * row_elems
+                                                 : reinterpret_cast<const float *>(g_tiled_zero_line);
+                            float *dp = win + (int64_t)(uni(hdr->lds_px[l]) + px0 + wave_px) * GC;
+                            __builtin_amdgcn_global_load_lds(sp, reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(dp)),
+                                                             16, 0, 0);
                         }
-                        continue;
                     }
+                    continue;
                 }
                 for (int px0 = fgrp; px0 < npx; px0 += kFillBatch * kFillGroups) {
                     float4 v[kFillBatch];
@@ -758,15 +746,12 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
                         *reinterpret_cast<float4 *>(dst + pxs[u] * GC) = inm[u] ? v[u] : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
-            if (sizeof(TV) == 4 && FL == 4 && !(g.dbg & 256)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the DMA fill's requests have landed)
+            if (sizeof(TV) == 4 && FL == 4) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the DMA fill's requests have landed)
             __syncthreads();
-            stamp<2>(g, st++);
+            stamp(g, st++);
 
             // ---- gather -------------------------------------------------------------------------------------
             for (int l = lb; l < le; ++l) {
-#if defined(FWD_ABLATE) && FWD_ABLATE == 2      // (diagnostic: no gather -- wrong results)
-                continue;
-#endif
                 LevelOps<kGatherQPG> cur = nxt;
                 [[maybe_unused]] const LevelRaw<PREP ? kGatherQPG : 1, REF4> rcur = rnxt;
                 if (l + 1 < le) {
@@ -805,17 +790,22 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
                 lc.nwr = uni(hdr->r[l].nwr);
                 lc.nwc = uni(hdr->r[l].nwc);
                 lc.lds_base = uni(hdr->lds_px[l]) * GC;
-                lc.base_row = head_major ? ((b * g.M + m) * g.S + uni(hdr->start[l])) * kTD : (b * g.S + uni(hdr->start[l])) * row_elems + m * kTD;
+                lc.base_row = (b * g.S + uni(hdr->start[l])) * row_elems + m * kTD;
                 unsigned pt0[kGatherQPG];
 #pragma unroll
                 for (int k = 0; k < kGatherQPG; ++k) pt0[k] = item[k] * (unsigned)LP + (unsigned)(l * g.P);
                 gather_level<P4, GC, CPL, TV>(value, loc, aw, win, lc, row_elems, g.P, j, chan, pt0, live, cur, acc_lo, acc_hi, n_general, l,
                                               miss);
             }
+            // vmcnt(0), as a builtin so that the compiler's wait-count pass sees it (an asm one it does not): nothing is in flight here, but
+            // the gather loop leaves before the wait of its location prefetch, which the last level never issues, and the compiler, which
+            // cannot know that, otherwise protects the fill loop's header registers with a full drain per level -- the fills of a phase's
+            // levels then wait for one another (profiles/r08_debug_switch_removal.md: 112.6 -> 115 us per E call without this line)
+            __builtin_amdgcn_s_waitcnt(0x0F70);
             // the next fill overwrites the windows (last phase: the barrier below, which also tells whether any point of the
             // workgroup missed its window, takes this one's place)
             if (!defer || ph + 1 < ph_end) __syncthreads();
-            stamp<2>(g, st++);
+            stamp(g, st++);
         }
     }
 
@@ -886,7 +876,7 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
                     int o[4];
                     float lh, lw;
                     resolve_point<float>(xy.x, xy.y, hdr->H[lv], hdr->W[lv],
-                                         head_major ? ((b * g.M + m) * g.S + hdr->start[lv]) * kTD : (b * g.S + hdr->start[lv]) * row_elems + m * kTD,
+                                         (b * g.S + hdr->start[lv]) * row_elems + m * kTD,
                                          row_elems, o, lh, lw);
                     const float hh = 1.f - lh, hw = 1.f - lw;
                     const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -906,7 +896,7 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
                 }
         }
     }
-    stamp<2>(g, st++);
+    stamp(g, st++);
     {
         const int chan = sub * GC + 4 * j;
 #pragma unroll
@@ -915,7 +905,7 @@ __global__ __launch_bounds__(GC == 16 ? 512 : 1024, GC == 16 ? 4 : 1) void tiled
                 st4(out + item[k] * (unsigned)kTD + chan, make_float4(acc_lo[k].x, acc_lo[k].y, acc_hi[k].x, acc_hi[k].y));
     }
     __syncthreads();   // the next item rebuilds the header
-    stamp<2>(g, st++);
+    stamp(g, st++);
     }
     if (g.stats) {   // locality monitor: one atomic per wave (only when the host asked for the count)
         for (int o = kWave / 2; o > 0; o >>= 1) n_general += __shfl_xor(n_general, o, kWave);

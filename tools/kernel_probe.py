@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time single MSDeformAttn calls on the GPU under different library options (tuning aid).
 
-    python tools/kernel_probe.py --call E --loc init --reps 5 --set tile_margin=4 --set tile_debug=1
+    python tools/kernel_probe.py --call E --loc init --reps 5 --set tile_margin=4 --set tile_grow=0
 Prints one line per (kind, variant): average kernel time from the library's event log.
 """
 import argparse

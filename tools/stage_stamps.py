@@ -16,7 +16,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--call", default="E")
 ap.add_argument("--kernel", default="fwd")
 ap.add_argument("--loc", default="init")
-ap.add_argument("--which", type=int, default=0, help="1 = scatter only, 2 = gather only")
 ap.add_argument("--set", action="append", default=[], help="option=value")
 args = ap.parse_args()
 call = {"E": W.call_E, "Em": W.call_Em}[args.call](2)
@@ -38,12 +37,10 @@ def run():
 
 run()
 torch.cuda.synchronize()
-_lib.set_option('tile_debug', args.which << 4)
 lib.msda_debug_stamps(buf.data_ptr())
 run()   # for bwd both kernels write the same rows: the later one (gather) wins where grids overlap
 torch.cuda.synchronize()
 lib.msda_debug_stamps(None)
-_lib.set_option('tile_debug', 0)
 s = buf.view(nwg, 16).cpu()
 used = s[:, 0] != 0
 s = s[used].double()
