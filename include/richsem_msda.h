@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define RICHSEM_MSDA_ABI_VERSION 10
+#define RICHSEM_MSDA_ABI_VERSION 11
 
 /* Return codes: 0 = success; negative = argument error detected on the host (nothing was
  * launched); positive = hipError_t reported by the runtime. */
@@ -568,6 +568,36 @@ int msda_lsap_f32(const float *cost, int target_major, const int64_t *tgt_offset
                   int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream);
 int msda_lsap_f64(const double *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
                   int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream);
+
+/* ---- PostProcess on the device (csrc/msda_postproc.h; reference models/richsem/richsem.py:1309-1367) ----------------------------------
+ * msda_postprocess_select: per image the k largest of the Q * C logits, in descending order, with what PostProcess makes of them:
+ *   logits      (B, Q, C) f32, or bf16 when logits_is_bf16; boxes (B, Q, 4) f32 (cx, cy, w, h); sizes_hw (B, 2) f32 (height, width)
+ *   scores      (B, k) f32 = sigmoid(logit) of the winners (from the f32 value of the logit)
+ *   labels, query_idx (B, k) int64 = flat index % C, flat index / C
+ *   out_boxes   (B, k, 4) f32: the winner's query box, box_mode 0 as it is (cx, cy, w, h), 1 as (x1, y1, x2, y2) = (cx - 0.5 w, cy - 0.5 h,
+ *               cx + 0.5 w, cy + 0.5 h), 2 as (x1, y1, x2 - x1, y2 - y1); then times (width, height, width, height).  Every operation is
+ *               rounded to float32 on its own, so the boxes are bit-equal to the reference's float32 tensor arithmetic.
+ * The order is float comparison of the LOGITS with -0.0 == +0.0 and every NaN above +inf; equal logits are taken lowest flat index first,
+ * so the result is determined by the input (exact for every input: all-equal rows, any number of elements equal to the k-th largest).
+ * Limits: B >= 1, 1 <= k <= 1024, k <= Q * C (MSDA_ERR_BAD_DIMS), Q * C < 2^31, and B * max(6160, ceil((Q * C + 7) / 8192)) < 2^31 -- the
+ * call's workgroups and zeroed words, some 348 000 images -- (MSDA_ERR_TOO_LARGE); logits, boxes, out_boxes and workspace 16-byte aligned
+ * (MSDA_ERR_MISALIGNED).  workspace: msda_postprocess_workspace_bytes() bytes, contents irrelevant on entry
+ * (the call zeroes what it counts in, on `stream`); it must not be shared by calls that may run concurrently.
+ * msda_nms_f32: torchvision's nms of K <= 1024 boxes per image that are ALREADY in descending score order (as msda_postprocess_select
+ * writes them): box i, unless suppressed itself, suppresses every later box j with inter / (area_i + area_j - inter) > iou_threshold in
+ * float32, areas (x2 - x1) * (y2 - y1) (0 / 0 is NaN and suppresses nothing; a NaN coordinate suppresses nothing either for
+ * iou_threshold >= 0, as in torchvision, though by another route: the clamp of the intersection's sides at 0 drops a NaN here and
+ * propagates it there, and neither 0 nor NaN is above such a threshold); with labels (B, K) int64 only where the two labels are equal
+ * (batched_nms).  keep (B, K) uint8; kept_idx (B, K) int64: the kept positions in ascending order (= descending score), then -1;
+ * n_kept (B) int32.  boxes_xyxy 16-byte aligned.
+ * None of these allocates, synchronises or reads device memory on the host: they can be captured into a graph. */
+int msda_postprocess_workspace_bytes(int B, int Q, int C, int k, int64_t *bytes);
+int msda_postprocess_select(const void *logits, int logits_is_bf16, const float *boxes, const float *sizes_hw,
+                            int B, int Q, int C, int k, int box_mode,
+                            float *scores, int64_t *labels, float *out_boxes, int64_t *query_idx,
+                            void *workspace, msda_stream_t stream);
+int msda_nms_f32(const float *boxes_xyxy, const int64_t *labels_or_null, int B, int K, float iou_threshold,
+                 uint8_t *keep, int64_t *kept_idx, int32_t *n_kept, msda_stream_t stream);
 
 /* ---- feed-forward block of the transformer layers on the matrix cores ----------
  *     out = LayerNorm(x + W2 . relu(W1 . x + b1) + b2)

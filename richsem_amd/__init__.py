@@ -13,6 +13,13 @@ import sys
 __version__ = "0.1.0"
 
 
+def __getattr__(name):      # PostProcess is exported from the package without importing torch at `import richsem_amd`
+    if name == "PostProcess":
+        from .postprocess import PostProcess
+        return PostProcess
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def install_dropin():
     """Register the drop-in under the reference's extension name, so that the reference's own
     ``import MultiScaleDeformableAttention as MSDA`` (ops/functions/ms_deform_attn_func.py:18) resolves to it."""

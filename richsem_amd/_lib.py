@@ -17,7 +17,7 @@ ERR_NAMES = {
     -8: "MSDA_ERR_NOT_ON_CPU",
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def raw_stream(dev=None):
@@ -69,6 +69,7 @@ SYMBOLS = [
     "msda_matcher_cost_f32", "msda_matcher_cost_f64", "msda_matcher_cost_tm_f32", "msda_matcher_cost_tm_f64",
     "msda_lsap_workspace_bytes", "msda_lsap_f32", "msda_lsap_f64", "msda_focal_neg_sum_f32", "msda_focal_neg_grad_f32", "msda_fed_class_mask_f32", "msda_focal_neg_sum_masked_f32", "msda_focal_neg_grad_masked_f32",
     "msda_attnpool_core_f32", "msda_attnpool_core_f64",
+    "msda_postprocess_workspace_bytes", "msda_postprocess_select", "msda_nms_f32",
     "msda_cls_packed_elems", "msda_cls_pack", "msda_cls_max_scores",
     "msda_conv_set_tiling", "msda_conv_set_ring", "msda_conv_dgrad_fused_bf16", "msda_conv_packed_elems", "msda_conv_pack_weight", "msda_conv_forward_bf16", "msda_conv_dgrad_bf16", "msda_conv_forward_workspace_bytes", "msda_conv_forward_ws_bf16", "msda_conv_dgrad_workspace_bytes", "msda_conv_dgrad_ws_bf16", "msda_pool_nhwc_bf16", "msda_groupnorm8_nhwc_bf16", "msda_groupnorm8_backward_nhwc_bf16", "msda_conv_wgrad_workspace_bytes", "msda_conv_wgrad_bf16", "msda_conv_set_wgrad_ring", "msda_conv_wgrad_group_workspace_bytes", "msda_conv_wgrad_group_bf16",
 ]
@@ -167,6 +168,12 @@ def load():
         f = getattr(L, "msda_attnpool_core_" + sfx)
         f.argtypes = [vp] * 4 + [ci] * 5 + [vp, vp]
         f.restype = ci
+    L.msda_postprocess_workspace_bytes.argtypes = [ci] * 4 + [ctypes.POINTER(i64)]
+    L.msda_postprocess_workspace_bytes.restype = ci
+    L.msda_postprocess_select.argtypes = [vp, ci, vp, vp] + [ci] * 5 + [vp] * 6
+    L.msda_postprocess_select.restype = ci
+    L.msda_nms_f32.argtypes = [vp, vp, ci, ci, ctypes.c_float, vp, vp, vp, vp]
+    L.msda_nms_f32.restype = ci
     L.msda_cls_packed_elems.argtypes = [ci, ctypes.POINTER(i64)]
     L.msda_cls_packed_elems.restype = ci
     L.msda_cls_pack.argtypes = [vp, ci, vp, ci, vp, vp]

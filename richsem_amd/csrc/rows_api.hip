@@ -13,6 +13,7 @@ extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hi
 #include "msda_attnpool.h"
 #include "msda_matcher.h"
 #include "msda_lsap.h"
+#include "msda_postproc.h"
 
 namespace {
 
@@ -591,6 +592,102 @@ int msda_lsap_f64(const double *cost, int target_major, const int64_t *tgt_offse
 {
     (void)workspace;
     return lsap_impl<double>(cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
+}
+
+}  // extern "C"
+
+/* ---- PostProcess on the device (csrc/msda_postproc.h; reference models/richsem/richsem.py:1309-1367) ------------------------------------ */
+namespace {
+
+// the argument checks msda_postprocess_workspace_bytes and msda_postprocess_select share
+int postprocess_dims(int B, int Q, int C, int k)
+{
+    if (B < 1 || Q < 1 || C < 1 || k < 1 || k > msda::kPpMaxK) return MSDA_ERR_BAD_DIMS;
+    if ((int64_t)Q * C >= ((int64_t)1 << 31)) return MSDA_ERR_TOO_LARGE;
+    if (k > (int64_t)Q * C) return MSDA_ERR_BAD_DIMS;
+    // the grid (a workgroup per chunk and image) and the words zeroed per call are counted in 32 bits
+    const int64_t per_image = msda::pp_chunks((int64_t)Q * C) > msda::kPpZeroWords ? msda::pp_chunks((int64_t)Q * C) : msda::kPpZeroWords;
+    if ((int64_t)B * per_image >= ((int64_t)1 << 31)) return MSDA_ERR_TOO_LARGE;
+    return MSDA_OK;
+}
+
+template <bool BF16>
+void postprocess_launch(const void *logits, const float *boxes, const float *sizes_hw, int B, int Q, int C, int k, int box_mode, float *scores,
+                        int64_t *labels, float *out_boxes, int64_t *query_idx, unsigned *ws, hipStream_t st)
+{
+    const int n = Q * C, nchunks = msda::pp_chunks(n);
+    unsigned *cand = ws + (size_t)B * msda::kPpZeroWords, *chunk_eq = cand + (size_t)B * 2 * msda::kPpMaxK;
+    unsigned *eq_slots = chunk_eq + (size_t)B * nchunks;
+    const dim3 grid(nchunks * B), block(msda::kPpThreads);      // (image-major: no limit of a grid's y extent on B)
+    for (int round = 0; round < msda::kPpRounds; ++round)
+        hipLaunchKernelGGL(msda::pp_hist_kernel<BF16>, grid, block, 0, st, logits, n, k, nchunks, round, ws);
+    hipLaunchKernelGGL(msda::pp_compact_kernel<BF16>, grid, block, 0, st, logits, boxes, sizes_hw, Q, C, k, nchunks, box_mode, ws, cand, chunk_eq,
+                       eq_slots, scores, labels, out_boxes, query_idx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msda_postprocess_workspace_bytes(int B, int Q, int C, int k, int64_t *bytes)
+{
+    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    const int rc = postprocess_dims(B, Q, C, k);
+    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    const int64_t words = (int64_t)B * (msda::kPpZeroWords + 2 * msda::kPpMaxK +
+                                         (int64_t)(1 + msda::kPpEqSlots) * msda::pp_chunks((int64_t)Q * C));
+    *bytes = (words * 4 + 15) & ~(int64_t)15;
+    return MSDA_OK;
+}
+
+int msda_postprocess_select(const void *logits, int logits_is_bf16, const float *boxes, const float *sizes_hw, int B, int Q, int C, int k,
+                            int box_mode, float *scores, int64_t *labels, float *out_boxes, int64_t *query_idx, void *workspace,
+                            msda_stream_t stream)
+{
+    if (!logits || !boxes || !sizes_hw || !scores || !labels || !out_boxes || !query_idx || !workspace)
+        return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    const int rc = postprocess_dims(B, Q, C, k);
+    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    if (box_mode < 0 || box_mode > 2) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_boxes) |
+         reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // histograms, tickets and counters start every call at zero (a replayed graph or a second call on the same workspace starts clean)
+    const int zero_words = B * msda::kPpZeroWords;
+    hipLaunchKernelGGL(msda::pp_zero_kernel, dim3((zero_words + msda::kPpThreads - 1) / msda::kPpThreads), dim3(msda::kPpThreads), 0, st,
+                       static_cast<unsigned *>(workspace), zero_words);
+    if (logits_is_bf16)
+        postprocess_launch<true>(logits, boxes, sizes_hw, B, Q, C, k, box_mode, scores, labels, out_boxes, query_idx, static_cast<unsigned *>(workspace), st);
+    else
+        postprocess_launch<false>(logits, boxes, sizes_hw, B, Q, C, k, box_mode, scores, labels, out_boxes, query_idx, static_cast<unsigned *>(workspace), st);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : (int)e;
+}
+
+int msda_nms_f32(const float *boxes_xyxy, const int64_t *labels_or_null, int B, int K, float iou_threshold, uint8_t *keep, int64_t *kept_idx,
+                 int32_t *n_kept, msda_stream_t stream)
+{
+    if (!boxes_xyxy || !keep || !kept_idx || !n_kept) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (B < 1 || K < 1 || K > msda::kNmsMaxK) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (reinterpret_cast<uintptr_t>(boxes_xyxy) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    const size_t lds = msda::nms_lds_bytes(K);
+    if (lds > 64 * 1024) {      // beyond the default limit of dynamic LDS: raised once per device, as for the assignment solver
+        static bool raised[64] = {};
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return (int)e;
+        if (dev < 0 || dev >= 64 || !raised[dev]) {
+            e = hipFuncSetAttribute(reinterpret_cast<const void *>(msda::nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)msda::nms_lds_bytes(msda::kNmsMaxK));
+            if (e != hipSuccess) return (int)e;
+            if (dev >= 0 && dev < 64) raised[dev] = true;
+        }
+    }
+    hipLaunchKernelGGL(msda::nms_kernel, dim3(B), dim3(msda::kNmsMaxK), lds, static_cast<hipStream_t>(stream), boxes_xyxy, labels_or_null, K,
+                       iou_threshold, keep, kept_idx, n_kept);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : (int)e;
 }
 
 }  // extern "C"
