@@ -21,31 +21,20 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "mfma_common.h"
+#include "msda_host.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kHd = 32;            // head dimension
 constexpr int kQW = 16;            // queries (or keys) per wave
 constexpr int kWaves = 4;
 
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    const bf16x2_t p = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
-    return __builtin_bit_cast(unsigned, p);
-}
 __device__ __forceinline__ bf16x8 pack8(const float (&p)[8])
 {
     const unsigned u0 = pack_bf16(p[0], p[1]), u1 = pack_bf16(p[2], p[3]), u2 = pack_bf16(p[4], p[5]), u3 = pack_bf16(p[6], p[7]);
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     return __builtin_bit_cast(bf16x8, (u32x4){u0, u1, u2, u3});
 }
 __device__ __forceinline__ float xor16(float v) { return __shfl_xor(v, 16, 64); }
@@ -358,12 +347,6 @@ __global__ __launch_bounds__(kWaves * 64) void attn_bwd_q_kernel(
 }
 
 bool bad_ld(int ld, int H) { return ld < H * kHd || (ld & 7); }
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-int finish()
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
-}
 
 }  // namespace
 
@@ -379,9 +362,9 @@ int msda_attn_forward_bf16(const uint16_t *q, int ldq, const uint16_t *k, int ld
                            int nq, int bs, int batch_first, int heads, uint16_t *out, float *lse, void *workspace, msda_stream_t stream)
 {
     const Tok tk = batch_first ? Tok{1, nq} : Tok{bs, 1};
-    if (!q || !k || !v || !out || !lse || !workspace) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (nq <= 0 || bs <= 0 || heads <= 0 || bad_ld(ldq, heads) || bad_ld(ldk, heads) || bad_ld(ldv, heads)) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(out) || misaligned(lse) || misaligned(workspace)) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!q || !k || !v || !out || !lse || !workspace) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (nq <= 0 || bs <= 0 || heads <= 0 || bad_ld(ldq, heads) || bad_ld(ldk, heads) || bad_ld(ldv, heads)) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {q, k, v, out, lse, workspace})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nkb = (nq + 31) / 32, nqp = nkb * 32;
     uint16_t *vt = static_cast<uint16_t *>(workspace);
@@ -389,7 +372,7 @@ int msda_attn_forward_bf16(const uint16_t *q, int ldq, const uint16_t *k, int ld
     hipLaunchKernelGGL(attn_transpose_kernel, tgrid, dim3(256), 0, st, v, ldv, nq, nqp, tk.si, tk.sb, heads, vt);
     hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(kWaves * 64), 0, st, q, ldq, k, ldk, vt, mask_bits, nq, nkb, tk, heads,
                        1.4426950408889634f / sqrtf((float)kHd), out, lse);
-    return finish();
+    return msda::launched(__func__);
 }
 
 int msda_attn_backward_bf16(const uint16_t *q, int ldq, const uint16_t *k, int ldk, const uint16_t *v, int ldv, const uint16_t *out,
@@ -398,14 +381,12 @@ int msda_attn_backward_bf16(const uint16_t *q, int ldq, const uint16_t *k, int l
                             msda_stream_t stream)
 {
     const Tok tk = batch_first ? Tok{1, nq} : Tok{bs, 1};
-    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !workspace) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if ((mask_bits == nullptr) != (maskt_bits == nullptr)) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !workspace) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if ((mask_bits == nullptr) != (maskt_bits == nullptr)) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (nq <= 0 || bs <= 0 || heads <= 0 || bad_ld(ldq, heads) || bad_ld(ldk, heads) || bad_ld(ldv, heads) || bad_ld(lddq, heads) ||
         bad_ld(lddk, heads) || bad_ld(lddv, heads))
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if (misaligned(q) || misaligned(k) || misaligned(v) || misaligned(out) || misaligned(dout) || misaligned(dq) || misaligned(dk) ||
-        misaligned(dv) || misaligned(workspace) || misaligned(lse))
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {q, k, v, out, dout, dq, dk, dv, workspace, lse})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nkb = (nq + 31) / 32, nqp = nkb * 32;
     const size_t tsz = (size_t)bs * heads * kHd * nqp;
@@ -422,7 +403,7 @@ int msda_attn_backward_bf16(const uint16_t *q, int ldq, const uint16_t *k, int l
                        nkb, tk, heads, scale, scale2, dk, lddk, dv, lddv);
     hipLaunchKernelGGL(attn_bwd_q_kernel, grid, dim3(kWaves * 64), 0, st, q, ldq, k, ldk, v, ldv, dout, kt, lse, delta, mask_bits, nq, nkb,
                        tk, heads, scale, scale2, dq, lddq);
-    return finish();
+    return msda::launched(__func__);
 }
 
 }  // extern "C"

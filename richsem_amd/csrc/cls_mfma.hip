@@ -28,33 +28,17 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "mfma_common.h"
+#include "msda_host.h"
 
 namespace {
-
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int kD = 256;            // width of the encoder memory (8 k-steps of 32)
 constexpr int kTokWave = 48;
 constexpr int kWaves = 4;
 constexpr int kTokWg = kTokWave * kWaves;
-constexpr int kFragShorts = 512;   // one MFMA operand fragment: 64 lanes x 8 bf16
 constexpr int kTileShorts = 2 * 8 * kFragShorts;   // 16 rows x 256 k, hi + lo parts: 16 KB
 constexpr int kMaxClasses = 8192;
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)   // one v_cvt_pk_bf16_f32 (round to nearest even)
-{
-    const bf16x2_t p = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
-    return __builtin_bit_cast(unsigned, p);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 // [G (classes x 256); zero rows up to a multiple of 16; A (256 x 256)] fp32 -> packed[tile][part][k-step][lane][8] bf16, lane (r, q)
 // of a fragment = row 16 tile + r, k = 32 step + 8 q + 0..7; part 0 = bf16(v), part 1 = bf16(v - part 0).
@@ -208,8 +192,7 @@ int launch_scores(const void *x, const uint16_t *packed, int tokens, int classes
 {
     const int grid = (tokens + kTokWg - 1) / kTokWg;
     hipLaunchKernelGGL((cls_score_kernel<XF32, WPARTS>), dim3(grid), dim3(kWaves * 64), 0, stream, x, packed, tokens, classes, scale, scores);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched("msda_cls_max_scores");
 }
 
 }  // namespace
@@ -218,28 +201,27 @@ extern "C" {
 
 int msda_cls_packed_elems(int classes, int64_t *elems)
 {
-    if (!elems) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (classes < 1 || classes > kMaxClasses) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!elems) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (classes < 1 || classes > kMaxClasses) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     *elems = (int64_t)((classes + 15) / 16 + kD / 16) * kTileShorts;
     return MSDA_OK;
 }
 
 int msda_cls_pack(const float *G, int classes, const float *A, int d_model, uint16_t *packed, msda_stream_t stream)
 {
-    if (!G || !A || !packed) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (classes < 1 || classes > kMaxClasses || d_model != kD) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!G || !A || !packed) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (classes < 1 || classes > kMaxClasses || d_model != kD) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int n_tiles = (classes + 15) / 16 + kD / 16;
     hipLaunchKernelGGL(cls_pack_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), G, classes, A, packed, n_tiles);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 int msda_cls_max_scores(const void *x, int x_is_bf16, const uint16_t *packed, int tokens, int d_model, int classes, float scale, int parts,
                         float *scores, msda_stream_t stream)
 {
-    if (!x || !packed || !scores) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (tokens < 0 || d_model != kD || classes < 1 || classes > kMaxClasses || (parts != 1 && parts != 2)) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!x || !packed || !scores) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (tokens < 0 || d_model != kD || classes < 1 || classes > kMaxClasses || (parts != 1 && parts != 2)) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, packed})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     if (tokens == 0) return MSDA_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (x_is_bf16)

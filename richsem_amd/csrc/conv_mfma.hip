@@ -29,28 +29,12 @@
 #include <initializer_list>
 #include <type_traits>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "mfma_common.h"
+#include "msda_host.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int kWaves = 4;
-constexpr int kFragShorts = 512;
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    const bf16x2_t p = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
-    return __builtin_bit_cast(unsigned, p);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 struct ConvGeom {
     int N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad;
@@ -359,15 +343,12 @@ void conv_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict_
 // C_in % 64 == 0 (two k-steps per iteration), CO_TILES >= 2.  Geometry, packing and epilogue are conv_fwd_kernel's.
 __device__ __attribute__((aligned(16))) unsigned g_conv_zero_line[4];      // (device globals are zero-initialised)
 
-#define CONV_LDS_READ(dst, addr, byte_off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(byte_off))
-#define CONV_LDS_WAIT(n, a) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(n))
-
 // fragments I .. N - 1 of a slot (1 KB apart) -> dst[I .. N - 1]   (compile-time recursion: the offsets and counts are instruction immediates)
 template <int I, int N>
 __device__ __forceinline__ void ring_read(u32x4 *dst, unsigned addr)
 {
     if constexpr (I < N) {
-        CONV_LDS_READ(dst[I], addr, I * 1024);
+        MFMA_LDS_READ(dst[I], addr, I * 1024);
         ring_read<I + 1, N>(dst, addr);
     }
 }
@@ -381,12 +362,12 @@ __device__ __forceinline__ void ring_products(f32x4 (&acc)[PT][CO_TILES], u32x4 
     if constexpr (P_ < WFR) {
         constexpr int h = P_ / CO_TILES, t = P_ % CO_TILES;
         constexpr int newer = (WFR - 1 - P_) < 7 ? (WFR - 1 - P_) : 7;
-        CONV_LDS_WAIT(newer, fr[P_ & 7]);      // (the activation fragments were asked for before fragment 0)
+        MFMA_LDS_WAIT(newer, fr[P_ & 7]);      // (the activation fragments were asked for before fragment 0)
         const bf16x8 a = __builtin_bit_cast(bf16x8, fr[P_ & 7]);
 #pragma unroll
         for (int t3 = 0; t3 < PT; ++t3)
             acc[t3][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, bfr[h * PT + t3]), acc[t3][t], 0, 0, 0);
-        if constexpr (P_ + 8 < WFR) CONV_LDS_READ(fr[P_ & 7], wa, (P_ + 8) * 1024);
+        if constexpr (P_ + 8 < WFR) MFMA_LDS_READ(fr[P_ & 7], wa, (P_ + 8) * 1024);
         ring_products<P_ + 1, CO_TILES, PT>(acc, fr, bfr, wa);
     }
 }
@@ -794,6 +775,7 @@ struct ConvArgs {
     float *ksum = nullptr;      // zeroed (P, C_out) fp32 image for a k split, or nullptr
     int nz = 1;                 // k slices
     const uint16_t *mask = nullptr;      // input gradient through a ReLU: the forward's activation (result zeroed where it is not positive)
+    const char *entry = "";     // the exported function the launch belongs to (error text)
     int ring = 0;               // > 0: conv_ring_kernel with this many slots (C_in % 64 == 0, CO_TILES >= 2, PT <= 2, no k split)
 };
 
@@ -802,19 +784,15 @@ int launch_ring(const ConvArgs &a, const dim3 &grid)
 {
     constexpr int bytes = R * (2 * CO_TILES + kWaves * 2 * PT) * 1024;
     if constexpr (bytes <= 160 * 1024) {
-        static std::atomic<int> prepared{0};
-        if (bytes > 64 * 1024 && !prepared.load()) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(conv_ring_kernel<CO_TILES, PT, R>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            if (e != hipSuccess) return (int)e;
-            prepared = 1;
+        if (bytes > 64 * 1024) {
+            const hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(conv_ring_kernel<CO_TILES, PT, R>), bytes);
+            if (e != hipSuccess) return msda::hip_fail(e, a.entry);
         }
         hipLaunchKernelGGL((conv_ring_kernel<CO_TILES, PT, R>), grid, dim3(kWaves * 64), bytes, a.stream, a.x, a.wpk, a.scale, a.shift,
                            a.residual, a.out, a.g, a.relu, a.mask);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? MSDA_OK : (int)e;
+        return msda::launched(a.entry);
     } else {
-        return MSDA_ERR_BAD_OPTION;
+        return msda::arg_fail(MSDA_ERR_BAD_OPTION, a.entry);
     }
 }
 
@@ -851,8 +829,7 @@ int launch_conv(const ConvArgs &a)
         hipLaunchKernelGGL(conv_ksum_finish_kernel, dim3((unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0, a.stream,
                            a.ksum, a.scale, a.shift, a.residual, a.out, P, a.g.Cout, a.relu, a.mask);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(a.entry);
 }
 
 template <int CO_TILES, int MODE>
@@ -937,7 +914,7 @@ extern "C" {
 /* Tuning / tests: the operand rings of conv_ring_kernel: -1 never, 0 automatic, 3 / 4 / 6 slots wherever the kernel applies. */
 int msda_conv_set_ring(int slots)
 {
-    if (slots != -1 && slots != 0 && slots != 3 && slots != 4 && slots != 6) return msda_note_error(MSDA_ERR_BAD_OPTION, __func__);
+    if (slots != -1 && slots != 0 && slots != 3 && slots != 4 && slots != 6) return msda::arg_fail(MSDA_ERR_BAD_OPTION, __func__);
     g_ring = slots;
     return MSDA_OK;
 }
@@ -947,7 +924,7 @@ int msda_conv_set_tiling(int co_tiles, int pixel_tiles)
 {
     if ((co_tiles != 0 && co_tiles != 1 && co_tiles != 2 && co_tiles != 4 && co_tiles != 8 && co_tiles != 16) || pixel_tiles < 0 ||
         pixel_tiles > 3)
-        return msda_note_error(MSDA_ERR_BAD_OPTION, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_OPTION, __func__);
     g_force_ct = co_tiles;
     g_force_pt = pixel_tiles;
     return MSDA_OK;
@@ -955,36 +932,35 @@ int msda_conv_set_tiling(int co_tiles, int pixel_tiles)
 
 int msda_conv_packed_elems(int Cout, int Cin, int KH, int KW, int64_t *elems)
 {
-    if (!elems) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (Cout < 16 || Cout % 16 != 0 || Cin < 1 || KH < 1 || KW < 1 || KH > 16 || KW > 16) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!elems) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (Cout < 16 || Cout % 16 != 0 || Cin < 1 || KH < 1 || KW < 1 || KH > 16 || KW > 16) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int64_t K = (int64_t)KH * KW * Cin;
-    if (Cin % 32 != 0 && K > 512) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);      // few-channel inputs only (table of 512 entries)
+    if (Cin % 32 != 0 && K > 512) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);      // few-channel inputs only (table of 512 entries)
     *elems = (int64_t)Cout * ((K + 31) / 32 * 32);
     return MSDA_OK;
 }
 
 int msda_conv_pack_weight(const float *weight, int Cout, int Cin, int KH, int KW, uint16_t *packed, msda_stream_t stream)
 {
-    if (!weight || !packed) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!weight || !packed) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     int64_t n = 0;
     const int rc = msda_conv_packed_elems(Cout, Cin, KH, KW, &n);
     if (rc != MSDA_OK) return rc;
     hipLaunchKernelGGL(conv_pack_kernel, dim3(512), dim3(256), 0, static_cast<hipStream_t>(stream), weight, packed, Cout, Cin, KH, KW,
                        (int)(n / Cout));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* bytes of zeroed fp32 workspace with which msda_conv_forward_ws_bf16 splits the k loop of this problem (0: it does not) */
 int msda_conv_forward_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int64_t *bytes)
 {
-    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     int64_t n = 0;
     const int rc = msda_conv_packed_elems(Cout, Cin, KH, KW, &n);
     if (rc != MSDA_OK) return rc;
-    if (N < 1 || H < 1 || W < 1 || stride < 1 || pad < 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (N < 1 || H < 1 || W < 1 || stride < 1 || pad < 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho < 1 || Wo < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (Ho < 1 || Wo < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     int ct, pt;
     choose_tiling((long long)N * Ho * Wo, Cout, KH * KW * Cin, ct, pt);
     *bytes = choose_ksplit((long long)N * Ho * Wo, Cout, Cin, KH, KW, ct, pt) > 1 ? (int64_t)N * Ho * Wo * Cout * (int64_t)sizeof(float) : 0;
@@ -1005,18 +981,16 @@ int msda_conv_forward_ws_bf16(const uint16_t *x, const uint16_t *packed_weight, 
                               const uint16_t *residual, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int relu,
                               uint16_t *out, void *workspace, msda_stream_t stream)
 {
-    if (!x || !packed_weight || !scale || !shift || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!x || !packed_weight || !scale || !shift || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     int64_t n = 0;
     const int rc = msda_conv_packed_elems(Cout, Cin, KH, KW, &n);
     if (rc != MSDA_OK) return rc;
-    if (N < 1 || H < 1 || W < 1 || stride < 1 || pad < 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (N < 1 || H < 1 || W < 1 || stride < 1 || pad < 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho < 1 || Wo < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((long long)N * H * W * Cin >= (1ll << 40) || (long long)N * Ho * Wo * Cout >= (1ll << 40)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
+    if (Ho < 1 || Wo < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if ((long long)N * H * W * Cin >= (1ll << 40) || (long long)N * Ho * Wo * Cout >= (1ll << 40)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
     const bool small_c = Cin % 32 != 0;
-    if ((reinterpret_cast<uintptr_t>(packed_weight) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(residual) | (small_c ? 0 : reinterpret_cast<uintptr_t>(x))) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!msda::aligned(16, {packed_weight, scale, shift, out, residual, small_c ? nullptr : x})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     int ct, pt;
     choose_tiling((long long)N * Ho * Wo, Cout, KH * KW * Cin, ct, pt);
     const int fct = g_force_ct.load(), fpt = g_force_pt.load();
@@ -1024,8 +998,9 @@ int msda_conv_forward_ws_bf16(const uint16_t *x, const uint16_t *packed_weight, 
     if (fpt) pt = fpt;
     ConvArgs a{x, packed_weight, scale, shift, residual, out, ConvGeom{N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, 1}, relu,
                static_cast<hipStream_t>(stream)};
+    a.entry = __func__;
     if (workspace && !fct && !fpt) {
-        if (reinterpret_cast<uintptr_t>(workspace) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+        if (!msda::aligned(16, {workspace})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
         a.nz = choose_ksplit((long long)N * Ho * Wo, Cout, Cin, KH, KW, ct, pt);
         a.ksum = a.nz > 1 ? static_cast<float *>(workspace) : nullptr;
     }
@@ -1040,23 +1015,20 @@ int msda_conv_forward_ws_bf16(const uint16_t *x, const uint16_t *packed_weight, 
 int msda_groupnorm8_nhwc_bf16(const uint16_t *x, const float *gamma, const float *beta, float eps, int N, int HW, int C, double *stats,
                               float *out_f32, uint16_t *out_bf16, msda_stream_t stream)
 {
-    if (!x || !gamma || !beta || !stats || (!out_f32 && !out_bf16)) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (N < 1 || HW < 1 || C < 8 || C % 8 != 0 || C / 8 > 65535 || N > 65535) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |
-         reinterpret_cast<uintptr_t>(out_f32) | reinterpret_cast<uintptr_t>(out_bf16)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!x || !gamma || !beta || !stats || (!out_f32 && !out_bf16)) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (N < 1 || HW < 1 || C < 8 || C % 8 != 0 || C / 8 > 65535 || N > 65535) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, gamma, beta, out_f32, out_bf16})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int groups = C / 8;
-    hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * 2 * N * groups, st);
-    if (e != hipSuccess) return (int)e;
+    const hipError_t e = hipMemsetAsync(stats, 0, sizeof(double) * 2 * N * groups, st);
+    if (e != hipSuccess) return msda::hip_fail(e, __func__);
     int strips = (HW + 2047) / 2048;
     if (strips > 64) strips = 64;
     hipLaunchKernelGGL(gn8_stats_kernel, dim3(strips, groups, N), dim3(256), 0, st, x, stats, HW, C);
     const long long n_vec = (long long)N * HW * groups;
     const int grid = (int)((n_vec + 255) / 256 < 65536 ? (n_vec + 255) / 256 : 65536);
     hipLaunchKernelGGL(gn8_apply_kernel, dim3(grid), dim3(256), 0, st, x, stats, gamma, beta, eps, N, HW, C, out_f32, out_bf16);
-    e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* Backward of msda_groupnorm8_nhwc_bf16: x, dy (N, HW, C) bf16; stats as the forward left them; bstats: N * (C / 8) * 16 doubles of
@@ -1064,22 +1036,20 @@ int msda_groupnorm8_nhwc_bf16(const uint16_t *x, const float *gamma, const float
 int msda_groupnorm8_backward_nhwc_bf16(const uint16_t *x, const uint16_t *dy, const float *gamma, float eps, int N, int HW, int C,
                                        const double *stats, double *bstats, uint16_t *dx, float *dgamma, float *dbeta, msda_stream_t stream)
 {
-    if (!x || !dy || !gamma || !stats || !bstats || !dx) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (N < 1 || HW < 1 || C < 8 || C % 8 != 0 || C / 8 > 65535 || N > 65535) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(dx)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!x || !dy || !gamma || !stats || !bstats || !dx) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (N < 1 || HW < 1 || C < 8 || C % 8 != 0 || C / 8 > 65535 || N > 65535) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, dy, gamma, dx})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int groups = C / 8;
-    hipError_t e = hipMemsetAsync(bstats, 0, sizeof(double) * 16 * N * groups, st);
-    if (e != hipSuccess) return (int)e;
+    const hipError_t e = hipMemsetAsync(bstats, 0, sizeof(double) * 16 * N * groups, st);
+    if (e != hipSuccess) return msda::hip_fail(e, __func__);
     int strips = (HW + 2047) / 2048;
     if (strips > 64) strips = 64;
     hipLaunchKernelGGL(gn8_bwd_stats_kernel, dim3(strips, groups, N), dim3(256), 0, st, x, dy, stats, eps, bstats, HW, C);
     const long long n_vec = (long long)N * HW * groups;
     const int grid = (int)((n_vec + 255) / 256 < 65536 ? (n_vec + 255) / 256 : 65536);
     hipLaunchKernelGGL(gn8_bwd_apply_kernel, dim3(grid), dim3(256), 0, st, x, dy, stats, bstats, gamma, eps, N, HW, C, dx, dgamma, dbeta);
-    e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* Pooling on NHWC bf16 (the pools around the backbones' convolutions: nn.AvgPool2d(k) of the CLIP ResNet, clip/model.py:24, :36, :115;
@@ -1088,12 +1058,12 @@ int msda_groupnorm8_backward_nhwc_bf16(const uint16_t *x, const uint16_t *dy, co
 int msda_pool_nhwc_bf16(const uint16_t *x, int N, int H, int W, int C, int k, int stride, int pad, int is_max, uint16_t *out,
                         msda_stream_t stream)
 {
-    if (!x || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!x || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (N < 1 || H < 1 || W < 1 || C < 8 || C % 8 != 0 || k < 1 || stride < 1 || pad < 0 || (!is_max && pad != 0) || pad >= k)
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int Ho = (H + 2 * pad - k) / stride + 1, Wo = (W + 2 * pad - k) / stride + 1;
-    if (Ho < 1 || Wo < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (Ho < 1 || Wo < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, out})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     const long long n = (long long)N * Ho * Wo * (C / 8);
     const int grid = (int)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1101,8 +1071,7 @@ int msda_pool_nhwc_bf16(const uint16_t *x, int N, int H, int W, int C, int k, in
         hipLaunchKernelGGL(pool_nhwc_kernel<true>, dim3(grid), dim3(256), 0, st, x, out, N, H, W, C, Ho, Wo, k, stride, pad);
     else
         hipLaunchKernelGGL(pool_nhwc_kernel<false>, dim3(grid), dim3(256), 0, st, x, out, N, H, W, C, Ho, Wo, k, stride, pad);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* Gradient of msda_conv_forward_bf16 w.r.t. its input, by the same kernel: a stride-1 convolution of the (zero-upsampled, for a
@@ -1118,10 +1087,10 @@ int msda_conv_dgrad_bf16(const uint16_t *dy, const uint16_t *packed_weight_t, in
 /* bytes of zeroed fp32 workspace with which msda_conv_dgrad_ws_bf16 splits the k loop (k = KH KW C_out here) of this problem (0: none) */
 int msda_conv_dgrad_workspace_bytes(int N, int Ho, int Wo, int Cout, int Cin, int KH, int KW, int stride, int pad, int H, int W, int64_t *bytes)
 {
-    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (N < 1 || Ho < 1 || Wo < 1 || H < 1 || W < 1 || Cout < 32 || Cout % 32 != 0 || Cin < 16 || Cin % 16 != 0 || KH < 1 || KW < 1 ||
         KH > 16 || KW > 16 || stride < 1 || pad < 0)
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     int ct, pt;
     choose_tiling((long long)N * H * W, Cin, KH * KW * Cout, ct, pt);
     *bytes = choose_ksplit((long long)N * H * W, Cin, Cout, KH, KW, ct, pt) > 1 ? (int64_t)N * H * W * Cin * (int64_t)sizeof(float) : 0;
@@ -1145,18 +1114,16 @@ int msda_conv_dgrad_fused_bf16(const uint16_t *dy, const uint16_t *packed_weight
                                int stride, int pad, int H, int W, const uint16_t *add, const uint16_t *relu_out, uint16_t *dx,
                                void *workspace, msda_stream_t stream)
 {
-    if (!dy || !packed_weight_t || !dx) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!dy || !packed_weight_t || !dx) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (N < 1 || Ho < 1 || Wo < 1 || H < 1 || W < 1 || Cout < 32 || Cout % 32 != 0 || Cin < 16 || Cin % 16 != 0 || KH < 1 || KW < 1 ||
         KH > 16 || KW > 16 || stride < 1 || pad < 0 || pad > KH - 1 || pad > KW - 1)
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((long long)N * H * W * Cin >= (1ll << 40) || (long long)N * Ho * Wo * Cout >= (1ll << 40)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(packed_weight_t) | reinterpret_cast<uintptr_t>(dx) |
-         reinterpret_cast<uintptr_t>(add) | reinterpret_cast<uintptr_t>(relu_out)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if ((H + 2 * pad - KH) / stride + 1 != Ho || (W + 2 * pad - KW) / stride + 1 != Wo) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if ((long long)N * H * W * Cin >= (1ll << 40) || (long long)N * Ho * Wo * Cout >= (1ll << 40)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
+    if (!msda::aligned(16, {dy, packed_weight_t, dx, add, relu_out})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     // as a forward call: input dy with Cout channels, output dx with Cin channels and H x W pixels, padding KH - 1 - pad
     // (KH == KW is not required: the column padding is KW - 1 - pad, see below), virtual input upsampled by `stride`
-    if (KH - 1 - pad != KW - 1 - pad) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);      // one padding value in the kernel's geometry: square kernels
+    if (KH - 1 - pad != KW - 1 - pad) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);      // one padding value in the kernel's geometry: square kernels
     int ct, pt;
     choose_tiling((long long)N * H * W, Cin, KH * KW * Cout, ct, pt);
     const int fct = g_force_ct.load(), fpt = g_force_pt.load();
@@ -1165,8 +1132,9 @@ int msda_conv_dgrad_fused_bf16(const uint16_t *dy, const uint16_t *packed_weight
     ConvArgs a{dy, packed_weight_t, nullptr, nullptr, add, dx, ConvGeom{N, Ho, Wo, Cout, H, W, Cin, KH, KW, 1, KH - 1 - pad, stride},
                0, static_cast<hipStream_t>(stream)};
     a.mask = relu_out;
+    a.entry = __func__;
     if (workspace) {
-        if (reinterpret_cast<uintptr_t>(workspace) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+        if (!msda::aligned(16, {workspace})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
         a.nz = choose_ksplit((long long)N * H * W, Cin, Cout, KH, KW, ct, pt);
         a.ksum = a.nz > 1 ? static_cast<float *>(workspace) : nullptr;
     }

@@ -23,16 +23,12 @@
 
 #include <atomic>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "mfma_common.h"
+#include "msda_host.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBM = 128, kBN = 128;     // output / input channels per workgroup
 constexpr int kStagePx = 64;            // pixels per stage (two k-steps of 32)
@@ -651,11 +647,11 @@ extern "C" {
  * n <= 8; workspace: msda_conv_wgrad_group_workspace_bytes() bytes (may be NULL when that is 0). */
 int msda_conv_wgrad_group_workspace_bytes(const msda_wgrad_problem *problems, int n, int64_t *bytes)
 {
-    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     WgradGroup grp;
     int64_t fl = 0;
     const int rc = plan_group(problems, n, grp, fl);
-    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
     *bytes = fl * (int64_t)sizeof(float);
     return MSDA_OK;
 }
@@ -665,16 +661,15 @@ int msda_conv_wgrad_group_bf16(const msda_wgrad_problem *problems, int n, void *
     WgradGroup grp;
     int64_t fl = 0;
     const int rc = plan_group(problems, n, grp, fl);
-    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
-    if (fl > 0 && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
+    if (fl > 0 && (!workspace || !msda::aligned(16, {workspace}))) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     float *ws = static_cast<float *>(workspace);
     bool any_bias = false;
     int max_cout = 0;
     for (int j = 0; j < n; ++j) {
         const msda_wgrad_problem &p = problems[j];
-        if (!p.dz || !p.x || !p.dw) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-        if ((reinterpret_cast<uintptr_t>(p.dz) | reinterpret_cast<uintptr_t>(p.x) | reinterpret_cast<uintptr_t>(p.dw)) & 15)
-            return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+        if (!p.dz || !p.x || !p.dw) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+        if (!msda::aligned(16, {p.dz, p.x, p.dw})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
         grp.dz[j] = p.dz;
         grp.x[j] = p.x;
         grp.dw[j] = p.dw;
@@ -695,24 +690,22 @@ int msda_conv_wgrad_group_bf16(const msda_wgrad_problem *problems, int n, void *
         hipLaunchKernelGGL((conv_wgrad_group_kernel<true, true>), ggrid, dim3(kThreads), 0, st, grp);
     else
         hipLaunchKernelGGL((conv_wgrad_group_kernel<true, false>), ggrid, dim3(kThreads), 0, st, grp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = msda::launched(__func__)) return rc;
     const long long total = grp.red_first[n];
     if (total > 0 || max_cout > 0) {
         long long blocks = (total + 63) / 64 < 8192 ? (total + 63) / 64 : 8192;
         if (blocks < (max_cout + 63) / 64) blocks = (max_cout + 63) / 64;      // (the bias partials: 64 channels per workgroup)
         const int grid = (int)blocks;
         hipLaunchKernelGGL(conv_wgrad_group_reduce_kernel, dim3(grid), dim3(256), 0, st, grp);
-        e = hipGetLastError();
     }
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* Tuning / tests: 1 (default) = the weight-gradient kernels prefetch their operand stages three ahead through an LDS ring (LDS DMA);
  * 0 = the register-staged form (one stage ahead).  Same products, same order: same results. */
 int msda_conv_set_wgrad_ring(int on)
 {
-    if (on != 0 && on != 1) return msda_note_error(MSDA_ERR_BAD_OPTION, __func__);
+    if (on != 0 && on != 1) return msda::arg_fail(MSDA_ERR_BAD_OPTION, __func__);
     g_wgrad_ring = on;
     return MSDA_OK;
 }
@@ -720,12 +713,12 @@ int msda_conv_set_wgrad_ring(int on)
 /* bytes of workspace msda_conv_wgrad_bf16 needs for a problem (0: none) */
 int msda_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int64_t *bytes)
 {
-    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (N < 1 || H < 1 || W < 1 || Cin < kBN || Cin % kBN != 0 || Cout < kBM || Cout % kBM != 0 || KH < 1 || KW < 1 || KH > 16 || KW > 16 ||
         stride < 1 || pad < 0)
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho < 1 || Wo < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (Ho < 1 || Wo < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     WgradGeom g{N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, (long long)N * Ho * Wo, 0, 0};
     long long split, chunk;
     wgrad_split(g, split, chunk);
@@ -736,23 +729,23 @@ int msda_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int 
 int msda_conv_wgrad_bf16(const uint16_t *dz, const uint16_t *x, int N, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                          int pad, float *dw, float *dbias, const float *scale, int torch_layout, void *workspace, msda_stream_t stream)
 {
-    if (!dz || !x || !dw) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!dz || !x || !dw) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (N < 1 || H < 1 || W < 1 || Cin < kBN || Cin % kBN != 0 || Cout < kBM || Cout % kBM != 0 || KH < 1 || KW < 1 || KH > 16 || KW > 16 ||
         stride < 1 || pad < 0)
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho < 1 || Wo < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((long long)N * H * W * Cin >= (1ll << 40) || (long long)N * Ho * Wo * Cout >= (1ll << 40)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
-    if ((reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dw)) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (Ho < 1 || Wo < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if ((long long)N * H * W * Cin >= (1ll << 40) || (long long)N * Ho * Wo * Cout >= (1ll << 40)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
+    if (!msda::aligned(16, {dz, x, dw})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     WgradGeom g{N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, (long long)N * Ho * Wo, 0, torch_layout};
-    if (g.P >= (1ll << 31) - (1 << 20) || (long long)N * H * W >= (1ll << 31)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);      // 32-bit pixel counters
+    if (g.P >= (1ll << 31) - (1 << 20) || (long long)N * H * W >= (1ll << 31)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);      // 32-bit pixel counters
     long long split;
     wgrad_split(g, split, g.chunk);
     const long long blocks_y = (long long)KH * KW * (Cout / kBM) * (Cin / kBN);
     const long long n_dw = (long long)Cout * KH * KW * Cin;
-    if (split > 1 && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (blocks_y > 65535) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
+    if (split > 1 && (!workspace || !msda::aligned(16, {workspace}))) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (blocks_y > 65535) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
     float *ws_bias = split > 1 ? static_cast<float *>(workspace) + split * n_dw : nullptr;
     const dim3 grid((unsigned)split, (unsigned)blocks_y);
     float *part = split > 1 ? static_cast<float *>(workspace) : dw, *bpart = dbias ? (split > 1 ? ws_bias : dbias) : nullptr;
@@ -762,16 +755,14 @@ int msda_conv_wgrad_bf16(const uint16_t *dz, const uint16_t *x, int N, int H, in
         hipLaunchKernelGGL((conv_wgrad_kernel<true, true>), grid, dim3(kThreads), 0, st, dz, x, part, bpart, scale, split > 1 ? 0 : 1, g);
     else
         hipLaunchKernelGGL((conv_wgrad_kernel<true, false>), grid, dim3(kThreads), 0, st, dz, x, part, bpart, scale, split > 1 ? 0 : 1, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = msda::launched(__func__)) return rc;
     if (split > 1) {
         const long long n4 = n_dw / 4;
         const int grid = (int)((n4 + 63) / 64 < 8192 ? (n4 + 63) / 64 : 8192);
         hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3(grid), dim3(256), 0, st, static_cast<const float *>(workspace), dw, n4, (int)split,
                            dbias ? ws_bias : nullptr, dbias, Cout, scale, KH * KW, Cin, torch_layout);
     }
-    e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 }  // extern "C"

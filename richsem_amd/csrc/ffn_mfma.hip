@@ -31,18 +31,14 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <initializer_list>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "mfma_common.h"
+#include "msda_host.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kD = 256;            // d_model (fixed: 8 output row tiles, 16 k-steps)
 constexpr int kTokWave = 48;       // tokens per wave (three 16-token MFMA column tiles)
@@ -50,20 +46,10 @@ constexpr int kWaves = 4;
 constexpr int kRing = 3;           // weight tiles in LDS
 constexpr int kTokWg = kTokWave * kWaves;
 constexpr int kHT = 32;            // hidden units per weight tile
-constexpr int kFragShorts = 512;   // one MFMA operand fragment: 64 lanes x 8 bf16
 constexpr int kTileFrags = 32;     // 16 of W1 (k-steps over d_model) + 16 of W2 (8 row tiles x 2 k-steps)
 constexpr int kMaxFfn = 4096;
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)   // one v_cvt_pk_bf16_f32 (round to nearest even)
-{
-    const bf16x2_t p = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
-    return __builtin_bit_cast(unsigned, p);
-}
 __device__ __forceinline__ float relu1(float x) { return __builtin_amdgcn_fmed3f(x, 0.f, __builtin_inff()); }   // one v_med3_f32
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 // W2 (256 x F, row-major) -> the k order the accumulator-as-operand idiom needs: inside every 32 hidden columns, position
 // 8 q + j holds column 4 q + j (j < 4) or 16 + 4 q + (j - 4) (j >= 4).
@@ -75,13 +61,6 @@ __global__ void pack_w2_kernel(const uint16_t *__restrict__ w2, uint16_t *__rest
         w2p[i] = w2[(i & ~31ll) + src];
     }
 }
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// one operand fragment from LDS, not visible to the compiler's wait-count bookkeeping (see the header)
-#define FFN_READ(dst, addr, byte_off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(byte_off))
-// "at most n LDS reads still in flight": everything older has arrived.  The operand ties the fragment to the wait.
-#define FFN_WAIT(n, a) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a) : "n"(n))
 
 __global__ __launch_bounds__(kWaves * 64) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ w1, const float *__restrict__ b1,
@@ -176,11 +155,11 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
         f32x4 bias[2];   // rows 16 rt + 4 q + 0..3 of the tile: read in the same stream, ahead of fragment 0 (whose wait covers them)
         {
             const unsigned ba = (unsigned)(uintptr_t)lb1 + (unsigned)(ht * kHT + 4 * q) * 4u;
-            FFN_READ(bias[0], ba, 0);
-            FFN_READ(bias[1], ba, 64);
+            MFMA_LDS_READ(bias[0], ba, 0);
+            MFMA_LDS_READ(bias[1], ba, 64);
         }
-        FFN_READ(fr[0], wt, 0 * 1024); FFN_READ(fr[1], wt, 1 * 1024); FFN_READ(fr[2], wt, 2 * 1024); FFN_READ(fr[3], wt, 3 * 1024);
-        FFN_READ(fr[4], wt, 4 * 1024); FFN_READ(fr[5], wt, 5 * 1024); FFN_READ(fr[6], wt, 6 * 1024); FFN_READ(fr[7], wt, 7 * 1024);
+        MFMA_LDS_READ(fr[0], wt, 0 * 1024); MFMA_LDS_READ(fr[1], wt, 1 * 1024); MFMA_LDS_READ(fr[2], wt, 2 * 1024); MFMA_LDS_READ(fr[3], wt, 3 * 1024);
+        MFMA_LDS_READ(fr[4], wt, 4 * 1024); MFMA_LDS_READ(fr[5], wt, 5 * 1024); MFMA_LDS_READ(fr[6], wt, 6 * 1024); MFMA_LDS_READ(fr[7], wt, 7 * 1024);
 
         // ---- H^T tile (two 16-row tiles) = W1 tile . x^T + b1 ---------------------------------------------------------------
         // The MFMAs of this product are inline: their accumulators must be VGPRs (relu and the conversion read them; hipcc
@@ -211,28 +190,28 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
         acc[1][t_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, hb[1], acc[1][t_], 0, 0, 0);                                \
         acc[2][t_] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_, hb[2], acc[2][t_], 0, 0, 0);                                \
     }
-        FFN_WAIT(7, fr[0]);
+        MFMA_LDS_WAIT(7, fr[0]);
         asm volatile("" : "+v"(bias[0]), "+v"(bias[1]));
-        FFN_USE1(0) FFN_READ(fr[0], wt, 8 * 1024);
-        FFN_WAIT(7, fr[1]); FFN_USE1(1) FFN_READ(fr[1], wt, 9 * 1024);
-        FFN_WAIT(7, fr[2]); FFN_USE1(2) FFN_READ(fr[2], wt, 10 * 1024);
+        FFN_USE1(0) MFMA_LDS_READ(fr[0], wt, 8 * 1024);
+        MFMA_LDS_WAIT(7, fr[1]); FFN_USE1(1) MFMA_LDS_READ(fr[1], wt, 9 * 1024);
+        MFMA_LDS_WAIT(7, fr[2]); FFN_USE1(2) MFMA_LDS_READ(fr[2], wt, 10 * 1024);
         FFN_STAGE(0)
-        FFN_WAIT(7, fr[3]); FFN_USE1(3) FFN_READ(fr[3], wt, 11 * 1024);
-        FFN_WAIT(7, fr[4]); FFN_USE1(4) FFN_READ(fr[4], wt, 12 * 1024);
-        FFN_WAIT(7, fr[5]); FFN_USE1(5) FFN_READ(fr[5], wt, 13 * 1024);
-        FFN_WAIT(7, fr[6]); FFN_USE1(6) FFN_READ(fr[6], wt, 14 * 1024);
+        MFMA_LDS_WAIT(7, fr[3]); FFN_USE1(3) MFMA_LDS_READ(fr[3], wt, 11 * 1024);
+        MFMA_LDS_WAIT(7, fr[4]); FFN_USE1(4) MFMA_LDS_READ(fr[4], wt, 12 * 1024);
+        MFMA_LDS_WAIT(7, fr[5]); FFN_USE1(5) MFMA_LDS_READ(fr[5], wt, 13 * 1024);
+        MFMA_LDS_WAIT(7, fr[6]); FFN_USE1(6) MFMA_LDS_READ(fr[6], wt, 14 * 1024);
         FFN_STAGE(1)
-        FFN_WAIT(7, fr[7]); FFN_USE1(7) FFN_READ(fr[7], wt, 15 * 1024);
-        FFN_WAIT(7, fr[0]); FFN_USE1(8) FFN_READ(fr[0], wt, 16 * 1024);
-        FFN_WAIT(7, fr[1]); FFN_USE1(9) FFN_READ(fr[1], wt, 17 * 1024);
-        FFN_WAIT(7, fr[2]); FFN_USE1(10) FFN_READ(fr[2], wt, 18 * 1024);
+        MFMA_LDS_WAIT(7, fr[7]); FFN_USE1(7) MFMA_LDS_READ(fr[7], wt, 15 * 1024);
+        MFMA_LDS_WAIT(7, fr[0]); FFN_USE1(8) MFMA_LDS_READ(fr[0], wt, 16 * 1024);
+        MFMA_LDS_WAIT(7, fr[1]); FFN_USE1(9) MFMA_LDS_READ(fr[1], wt, 17 * 1024);
+        MFMA_LDS_WAIT(7, fr[2]); FFN_USE1(10) MFMA_LDS_READ(fr[2], wt, 18 * 1024);
         FFN_STAGE(2)
-        FFN_WAIT(7, fr[3]); FFN_USE1(11) FFN_READ(fr[3], wt, 19 * 1024);
-        FFN_WAIT(7, fr[4]); FFN_USE1(12) FFN_READ(fr[4], wt, 20 * 1024);
-        FFN_WAIT(7, fr[5]); FFN_USE1(13) FFN_READ(fr[5], wt, 21 * 1024);
-        FFN_WAIT(7, fr[6]); FFN_USE1(14) FFN_READ(fr[6], wt, 22 * 1024);
+        MFMA_LDS_WAIT(7, fr[3]); FFN_USE1(11) MFMA_LDS_READ(fr[3], wt, 19 * 1024);
+        MFMA_LDS_WAIT(7, fr[4]); FFN_USE1(12) MFMA_LDS_READ(fr[4], wt, 20 * 1024);
+        MFMA_LDS_WAIT(7, fr[5]); FFN_USE1(13) MFMA_LDS_READ(fr[5], wt, 21 * 1024);
+        MFMA_LDS_WAIT(7, fr[6]); FFN_USE1(14) MFMA_LDS_READ(fr[6], wt, 22 * 1024);
         FFN_STAGE(3)
-        FFN_WAIT(7, fr[7]); FFN_USE1(15) FFN_READ(fr[7], wt, 23 * 1024);
+        MFMA_LDS_WAIT(7, fr[7]); FFN_USE1(15) MFMA_LDS_READ(fr[7], wt, 23 * 1024);
         FFN_STAMP(2)   // first product
         // (results of an inline MFMA: the compiler does not know to keep its distance -- a 4-pass MFMA's result may be read by a
         // vector instruction 11 wait states later)
@@ -249,26 +228,26 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
         }
         FFN_STAMP(3)   // relu + conversion
         // ---- out^T += W2 tile . relu(H^T): fragment 16 + t = 16-channel row tile t ------------------------------------------------
-        FFN_WAIT(7, fr[0]); FFN_USE2(16) FFN_READ(fr[0], wt, 24 * 1024);
-        FFN_WAIT(7, fr[1]); FFN_USE2(17) FFN_READ(fr[1], wt, 25 * 1024);
-        FFN_WAIT(7, fr[2]); FFN_USE2(18) FFN_READ(fr[2], wt, 26 * 1024);
+        MFMA_LDS_WAIT(7, fr[0]); FFN_USE2(16) MFMA_LDS_READ(fr[0], wt, 24 * 1024);
+        MFMA_LDS_WAIT(7, fr[1]); FFN_USE2(17) MFMA_LDS_READ(fr[1], wt, 25 * 1024);
+        MFMA_LDS_WAIT(7, fr[2]); FFN_USE2(18) MFMA_LDS_READ(fr[2], wt, 26 * 1024);
         FFN_STAGE(4)
-        FFN_WAIT(7, fr[3]); FFN_USE2(19) FFN_READ(fr[3], wt, 27 * 1024);
-        FFN_WAIT(7, fr[4]); FFN_USE2(20) FFN_READ(fr[4], wt, 28 * 1024);
-        FFN_WAIT(7, fr[5]); FFN_USE2(21) FFN_READ(fr[5], wt, 29 * 1024);
-        FFN_WAIT(7, fr[6]); FFN_USE2(22) FFN_READ(fr[6], wt, 30 * 1024);
+        MFMA_LDS_WAIT(7, fr[3]); FFN_USE2(19) MFMA_LDS_READ(fr[3], wt, 27 * 1024);
+        MFMA_LDS_WAIT(7, fr[4]); FFN_USE2(20) MFMA_LDS_READ(fr[4], wt, 28 * 1024);
+        MFMA_LDS_WAIT(7, fr[5]); FFN_USE2(21) MFMA_LDS_READ(fr[5], wt, 29 * 1024);
+        MFMA_LDS_WAIT(7, fr[6]); FFN_USE2(22) MFMA_LDS_READ(fr[6], wt, 30 * 1024);
         FFN_STAGE(5)
-        FFN_WAIT(7, fr[7]); FFN_USE2(23) FFN_READ(fr[7], wt, 31 * 1024);
-        FFN_WAIT(7, fr[0]); FFN_USE2(24)
-        FFN_WAIT(6, fr[1]); FFN_USE2(25)
-        FFN_WAIT(5, fr[2]); FFN_USE2(26)
+        MFMA_LDS_WAIT(7, fr[7]); FFN_USE2(23) MFMA_LDS_READ(fr[7], wt, 31 * 1024);
+        MFMA_LDS_WAIT(7, fr[0]); FFN_USE2(24)
+        MFMA_LDS_WAIT(6, fr[1]); FFN_USE2(25)
+        MFMA_LDS_WAIT(5, fr[2]); FFN_USE2(26)
         FFN_STAGE(6)
-        FFN_WAIT(4, fr[3]); FFN_USE2(27)
-        FFN_WAIT(3, fr[4]); FFN_USE2(28)
-        FFN_WAIT(2, fr[5]); FFN_USE2(29)
-        FFN_WAIT(1, fr[6]); FFN_USE2(30)
+        MFMA_LDS_WAIT(4, fr[3]); FFN_USE2(27)
+        MFMA_LDS_WAIT(3, fr[4]); FFN_USE2(28)
+        MFMA_LDS_WAIT(2, fr[5]); FFN_USE2(29)
+        MFMA_LDS_WAIT(1, fr[6]); FFN_USE2(30)
         FFN_STAGE(7)
-        FFN_WAIT(0, fr[7]); FFN_USE2(31)
+        MFMA_LDS_WAIT(0, fr[7]); FFN_USE2(31)
 #undef FFN_USE1
 #undef FFN_USE2
 #undef FFN_STAGE
@@ -477,12 +456,11 @@ int msda_ffn_debug_stamps(void *device_buffer)
 
 int msda_ffn_pack_w2_bf16(const uint16_t *w2, int d_model, int d_ffn, uint16_t *w2_packed, msda_stream_t stream)
 {
-    if (!w2 || !w2_packed) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (d_model != kD || d_ffn < kHT || d_ffn % kHT != 0 || d_ffn > kMaxFfn) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!w2 || !w2_packed) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (d_model != kD || d_ffn < kHT || d_ffn % kHT != 0 || d_ffn > kMaxFfn) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const long long n = (long long)d_model * d_ffn;
     hipLaunchKernelGGL(pack_w2_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w2, w2_packed, n);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* msda_ffn_forward_bf16 that also writes what the backward needs besides x: the LayerNorm's 1 / sqrt(var + eps) per token (rstd, `tokens`
@@ -502,27 +480,19 @@ int msda_ffn_forward_train_bf16(const uint16_t *x, const uint16_t *w1, const flo
                                 const float *ln_weight, const float *ln_bias, float eps, int tokens, int d_model, int d_ffn,
                                 uint16_t *out, float *rstd, uint16_t *yhat, msda_stream_t stream)
 {
-    if (!x || !w1 || !b1 || !w2_packed || !b2 || !ln_weight || !ln_bias || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (d_model != kD || d_ffn < kHT || d_ffn % kHT != 0 || d_ffn > kMaxFfn || tokens < 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2_packed) |
-         reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(b2) |
-         reinterpret_cast<uintptr_t>(ln_weight) | reinterpret_cast<uintptr_t>(ln_bias)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!x || !w1 || !b1 || !w2_packed || !b2 || !ln_weight || !ln_bias || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (d_model != kD || d_ffn < kHT || d_ffn % kHT != 0 || d_ffn > kMaxFfn || tokens < 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, w1, w2_packed, out, b1, b2, ln_weight, ln_bias})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     if (tokens == 0) return MSDA_OK;
     const size_t lds = ffn_lds_bytes(d_ffn);
-    static std::atomic<bool> raised[64];   // per device: the dynamic-LDS limit is a property of (function, device)
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return msda_note_error(MSDA_ERR_NO_DEVICE, __func__);
-    if (!raised[dev].load()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        raised[dev] = true;
-    }
+    if (hipGetDevice(&dev) != hipSuccess) return msda::arg_fail(MSDA_ERR_NO_DEVICE, __func__);
+    const hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(ffn_fwd_kernel), 160 * 1024);
+    if (e != hipSuccess) return msda::hip_fail(e, __func__);
     const int grid = (tokens + kTokWg - 1) / kTokWg;
     hipLaunchKernelGGL(ffn_fwd_kernel, dim3(grid), dim3(kWaves * 64), lds, static_cast<hipStream_t>(stream), x, w1, b1, w2_packed, b2,
                        ln_weight, ln_bias, eps, tokens, d_ffn, out, g_ffn_stamps, rstd, yhat);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* Backward, first step (see ffn_ln_backward_kernel): dy, yhat (tokens, 256) bf16; rstd (tokens), yhat from msda_ffn_forward_train_bf16;
@@ -531,22 +501,19 @@ int msda_ffn_forward_train_bf16(const uint16_t *x, const uint16_t *w1, const flo
 int msda_ffn_ln_backward_bf16(const uint16_t *dy, const uint16_t *yhat, const float *rstd, const float *ln_weight, int tokens, int d_model,
                               uint16_t *dz, float *grad_ln_weight, float *grad_ln_bias, float *grad_b2, msda_stream_t stream)
 {
-    if (!dy || !yhat || !rstd || !ln_weight || !dz || !grad_ln_weight || !grad_ln_bias || !grad_b2) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (tokens < 0 || d_model != kD) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(yhat) | reinterpret_cast<uintptr_t>(dz) |
-         reinterpret_cast<uintptr_t>(ln_weight)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!dy || !yhat || !rstd || !ln_weight || !dz || !grad_ln_weight || !grad_ln_bias || !grad_b2) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (tokens < 0 || d_model != kD) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {dy, yhat, dz, ln_weight})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (float *p : {grad_ln_weight, grad_ln_bias, grad_b2}) {
         const hipError_t e = hipMemsetAsync(p, 0, kD * sizeof(float), st);
-        if (e != hipSuccess) return (int)e;
+        if (e != hipSuccess) return msda::hip_fail(e, __func__);
     }
     if (tokens == 0) return MSDA_OK;
     const int grid = (tokens + 3) / 4 < 512 ? (tokens + 3) / 4 : 512;
     hipLaunchKernelGGL(ffn_ln_backward_kernel, dim3(grid), dim3(256), 0, st, dy, yhat, rstd, ln_weight, tokens, dz, grad_ln_weight, grad_ln_bias,
                        grad_b2);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* out = LayerNorm(a + b) (256 channels; b may be NULL): a, b, out (tokens, 256) bf16; gamma, beta f32; rstd (tokens) f32 and yhat
@@ -554,17 +521,14 @@ int msda_ffn_ln_backward_bf16(const uint16_t *dy, const uint16_t *yhat, const fl
 int msda_add_layernorm_forward_bf16(const uint16_t *a, const uint16_t *b, const float *ln_weight, const float *ln_bias, float eps, int tokens,
                                     int d_model, uint16_t *out, float *rstd, uint16_t *yhat, msda_stream_t stream)
 {
-    if (!a || !ln_weight || !ln_bias || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (tokens < 0 || d_model != kD) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(yhat) |
-         reinterpret_cast<uintptr_t>(ln_weight) | reinterpret_cast<uintptr_t>(ln_bias)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!a || !ln_weight || !ln_bias || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (tokens < 0 || d_model != kD) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {a, b, out, yhat, ln_weight, ln_bias})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     if (tokens == 0) return MSDA_OK;
     const int grid = (tokens + 3) / 4 < 4096 ? (tokens + 3) / 4 : 4096;
     hipLaunchKernelGGL(add_layernorm_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), a, b, ln_weight, ln_bias, eps, tokens,
                        out, rstd, yhat);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 }  // extern "C"

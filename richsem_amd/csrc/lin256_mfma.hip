@@ -14,31 +14,15 @@
 #include <hip/hip_bf16.h>
 #include <stdint.h>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "mfma_common.h"
+#include "msda_host.h"
 
 namespace {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int kD = 256;
 constexpr int kTokWave = 48, kWaves = 4, kTokWg = kTokWave * kWaves;
-constexpr int kFragShorts = 512;
 constexpr int kBlockRows = 64;                                  // output channels per LDS block
 constexpr int kBlockShorts = 4 * 8 * kFragShorts;              // 32 KB
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    const bf16x2_t p = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
-    return __builtin_bit_cast(unsigned, p);
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __uint_as_float(u & 0xFFFF0000u); }
 
 // W (N x 256) bf16 row-major -> packed[block][k-step][tile u][lane][8]; lane (r = 4 q' + i, q) of tile u = output channel
 // 64 block + 16 q' + 4 u + i, input channels 32 step + 8 q + 0..7
@@ -288,7 +272,7 @@ void lin256_f32_kernel(const float *__restrict__ x, const uint16_t *__restrict__
 }
 
 template <int EPI>
-int launch_lin(const uint16_t *x, const uint16_t *packed, const float *bias, const uint16_t *mask, int T, int N, uint16_t *out,
+int launch_lin(const char *entry, const uint16_t *x, const uint16_t *packed, const float *bias, const uint16_t *mask, int T, int N, uint16_t *out,
                hipStream_t st, long long chunk_elems = 0)
 {
     const int gx = (T + kTokWg - 1) / kTokWg, nb = N / kBlockRows;
@@ -300,8 +284,7 @@ int launch_lin(const uint16_t *x, const uint16_t *packed, const float *bias, con
     if (gy > nb) gy = nb;
     if (gy > 8) gy = 8;
     hipLaunchKernelGGL(lin256_kernel<EPI>, dim3(gx, gy), dim3(kWaves * 64), 0, st, x, packed, bias, mask, T, N, out, chunk_elems);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(entry);
 }
 
 }  // namespace
@@ -310,65 +293,57 @@ extern "C" {
 
 int msda_lin256_pack_bf16(const uint16_t *w, int out_features, int in_features, uint16_t *packed, msda_stream_t stream)
 {
-    if (!w || !packed) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (in_features != kD || out_features < kBlockRows || out_features % kBlockRows != 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!w || !packed) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (in_features != kD || out_features < kBlockRows || out_features % kBlockRows != 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     hipLaunchKernelGGL(lin256_pack_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w, packed, out_features);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 int msda_lin256_forward_bf16(const uint16_t *x, const uint16_t *packed_w, const float *bias, const uint16_t *relu_mask, int epilogue,
                              int tokens, int in_features, int out_features, uint16_t *out, msda_stream_t stream)
 {
-    if (!x || !packed_w || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!x || !packed_w || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     if (tokens < 0 || in_features != kD || out_features < kBlockRows || out_features % kBlockRows != 0 || epilogue < 0 || epilogue > 3)
-        return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if (epilogue >= 2 && !relu_mask) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed_w) | reinterpret_cast<uintptr_t>(out) |
-         reinterpret_cast<uintptr_t>(bias) | (epilogue == 2 ? reinterpret_cast<uintptr_t>(relu_mask) : 0)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (epilogue >= 2 && !relu_mask) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (!msda::aligned(16, {x, packed_w, out, bias, epilogue == 2 ? relu_mask : nullptr})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     if (tokens == 0) return MSDA_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     switch (epilogue) {
-    case 0: return launch_lin<0>(x, packed_w, bias, nullptr, tokens, out_features, out, st);
-    case 1: return launch_lin<1>(x, packed_w, bias, nullptr, tokens, out_features, out, st);
-    case 2: return launch_lin<2>(x, packed_w, nullptr, relu_mask, tokens, out_features, out, st);
-    default: return launch_lin<3>(x, packed_w, bias, relu_mask, tokens, out_features, out, st);
+    case 0: return launch_lin<0>(__func__, x, packed_w, bias, nullptr, tokens, out_features, out, st);
+    case 1: return launch_lin<1>(__func__, x, packed_w, bias, nullptr, tokens, out_features, out, st);
+    case 2: return launch_lin<2>(__func__, x, packed_w, nullptr, relu_mask, tokens, out_features, out, st);
+    default: return launch_lin<3>(__func__, x, packed_w, bias, relu_mask, tokens, out_features, out, st);
     }
 }
 
 int msda_lin256_forward_stacked_bf16(const uint16_t *x, const uint16_t *packed_w, const float *bias, const uint8_t *row_mask, int tokens,
                                      int in_features, int out_features, uint16_t *out, msda_stream_t stream)
 {
-    if (!x || !packed_w || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (tokens < 0 || in_features != kD || out_features < 256 || out_features % 256 != 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed_w) | reinterpret_cast<uintptr_t>(out) |
-         reinterpret_cast<uintptr_t>(bias)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!x || !packed_w || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (tokens < 0 || in_features != kD || out_features < 256 || out_features % 256 != 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, packed_w, out, bias})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     if (tokens == 0) return MSDA_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long chunk = (long long)tokens * 256;
-    if (row_mask) return launch_lin<3>(x, packed_w, bias, reinterpret_cast<const uint16_t *>(row_mask), tokens, out_features, out, st, chunk);
-    return launch_lin<0>(x, packed_w, bias, nullptr, tokens, out_features, out, st, chunk);
+    if (row_mask) return launch_lin<3>(__func__, x, packed_w, bias, reinterpret_cast<const uint16_t *>(row_mask), tokens, out_features, out, st, chunk);
+    return launch_lin<0>(__func__, x, packed_w, bias, nullptr, tokens, out_features, out, st, chunk);
 }
 
 int msda_lin256_pack_f32(const float *w, int out_features, int in_features, uint16_t *packed, msda_stream_t stream)
 {
-    if (!w || !packed) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (in_features != kD || out_features < kF32BlockRows || out_features % kF32BlockRows != 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!w || !packed) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (in_features != kD || out_features < kF32BlockRows || out_features % kF32BlockRows != 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     hipLaunchKernelGGL(lin256_pack_f32_kernel, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w, packed, out_features);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 int msda_lin256_forward_f32(const float *x, const uint16_t *packed_w, const float *bias, int tokens, int in_features, int out_features,
                             float *out, msda_stream_t stream)
 {
-    if (!x || !packed_w || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (tokens < 0 || in_features != kD || out_features < kF32BlockRows || out_features % kF32BlockRows != 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed_w) | reinterpret_cast<uintptr_t>(out) |
-         reinterpret_cast<uintptr_t>(bias)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!x || !packed_w || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (tokens < 0 || in_features != kD || out_features < kF32BlockRows || out_features % kF32BlockRows != 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {x, packed_w, out, bias})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     if (tokens == 0) return MSDA_OK;
     const int gx = (tokens + kTokWg - 1) / kTokWg, nb = out_features / kF32BlockRows;
     int gy = 1;          // (one workgroup per CU: 1 wave per SIMD at its register count; 233 workgroups at the training shape)
@@ -376,8 +351,7 @@ int msda_lin256_forward_f32(const float *x, const uint16_t *packed_w, const floa
     if (gy > 4) gy = 4;
     hipLaunchKernelGGL(lin256_f32_kernel, dim3(gx, gy), dim3(kWaves * 64), 0, static_cast<hipStream_t>(stream), x, packed_w, bias, tokens,
                        out_features, out);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 }  // extern "C"

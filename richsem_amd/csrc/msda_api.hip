@@ -14,20 +14,20 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/richsem_msda.h"
+#include "msda_host.h"
 #include "msda_direct.h"
 #include "msda_levelsum.h"
 #include "msda_prep.h"
-#include "msda_dn.h"
-#include "msda_topk.h"
-#include "msda_roi.h"
 #include "msda_band.h"
 #include "msda_rps.h"
 #include "msda_tiled.h"
 
 namespace {
-
 thread_local char g_err[512] = "";
+}
+
+// ---- the host layer of msda_host.h: every non-zero return of the library goes through one of these -----------------------------
+namespace msda {
 
 int fail(int code, const char *fmt, ...)
 {
@@ -38,27 +38,52 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-}  // namespace
-
-// Error note of the library's other translation units (conv / ffn / lin256 / cls / attn / rows): "<entry point>: <class of error>", so
-// that msda_last_error() after a failed call names the call and is never a stale message of an earlier one.  Not part of the C ABI.
-extern "C" __attribute__((visibility("hidden"))) int msda_note_error(int code, const char *entry)
+int arg_fail(int code, const char *entry)
 {
     const char *what = code == MSDA_ERR_NULL_POINTER ? "null pointer argument"
                      : code == MSDA_ERR_BAD_DIMS     ? "dimension out of the supported range (see include/richsem_msda.h)"
                      : code == MSDA_ERR_MISALIGNED   ? "pointer not aligned as required"
                      : code == MSDA_ERR_TOO_LARGE    ? "problem too large for 32-bit indexing"
+                     : code == MSDA_ERR_NO_DEVICE    ? "no device to run on"
+                     : code == MSDA_ERR_BAD_OPTION   ? "option value not among the accepted ones"
                                                      : "error";
     return fail(code, "%s: %s", entry, what);
 }
 
-namespace {
-
-int hip_fail(hipError_t e, const char *what, const char *tag = "")
+int hip_fail(hipError_t e, const char *what, const char *tag)
 {
     snprintf(g_err, sizeof(g_err), "%s%s: %s (hipError %d)", what, tag, hipGetErrorString(e), (int)e);
     return (int)e;
 }
+
+int launched(const char *what, const char *tag)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MSDA_OK : hip_fail(e, what, tag);
+}
+
+hipError_t set_lds_limit(const void *fn, size_t bytes)
+{
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> granted;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &have = granted[std::make_pair(dev, fn)];
+    if (have >= bytes) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) have = bytes;
+    return e;
+}
+
+}  // namespace msda
+
+namespace {
+
+using msda::aligned;
+using msda::fail;
+using msda::hip_fail;
+using msda::launched;
 
 struct Problem {
     int N, S, M, D, L, Lq, P;
@@ -278,8 +303,6 @@ int run_window_fwd(const FwdChoice &ch, int prof_variant, int dtype_bytes, const
     return MSDA_OK;
 }
 
-bool is_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
-
 // Argument checks shared by forward and backward.  Mirrors the reference's preconditions
 // (ms_deform_attn_cuda.cu:28-52) and adds the bounds the kernels rely on.
 int check_problem(Problem &pb, const int64_t *shapes_dev, const int64_t *lsi_dev, const int64_t *shapes_host,
@@ -341,9 +364,7 @@ int pick_channels(int D, int max_channels, std::initializer_list<const void *> p
 {
     int c = max_channels;
     for (; c > 1; c >>= 1) {
-        bool ok = D % c == 0;
-        for (const void *p : ptrs) ok = ok && is_aligned(p, sizeof(TV) * c);
-        if (ok) break;
+        if (D % c == 0 && aligned(sizeof(TV) * c, ptrs)) break;
     }
     return c;
 }
@@ -510,11 +531,8 @@ hipError_t launch_bwd_rps(const Problem &pb, const TV *value, const float *loc, 
 {
     msda::RpsPlan pl = msda::plan_rps(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data());
     if (!pl.ok) return hipErrorNotSupported;
-    constexpr uintptr_t row_align = sizeof(TV) * 4 - 1;   // 16 B (fp32) / 8 B (bf16) per lane access
-    if ((reinterpret_cast<uintptr_t>(value) | reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_value)) & row_align)
-        return hipErrorNotSupported;
-    if (reinterpret_cast<uintptr_t>(grad_acc) & 15) return hipErrorNotSupported;
-    if ((reinterpret_cast<uintptr_t>(grad_loc) | reinterpret_cast<uintptr_t>(loc)) & 7) return hipErrorNotSupported;
+    // rows: 16 B (fp32) / 8 B (bf16) per lane access
+    if (!aligned(sizeof(TV) * 4, {value, grad_out, grad_value}) || !aligned(16, {grad_acc}) || !aligned(8, {grad_loc, loc})) return hipErrorNotSupported;
     if ((int64_t)pb.N * pb.Lq * pb.M * msda::kRpsD * (int64_t)sizeof(TV) > (int64_t)0xFFFFFFFF) return hipErrorNotSupported;      // (the tile kernel addresses grad_out rows by 32-bit byte offsets)
     Workspace ws;
     const size_t n_runs = (size_t)pl.g.nbins * (size_t)pl.g.max_runs;
@@ -572,12 +590,9 @@ hipError_t launch_bwd_band(const Problem &pb, const TV *value, const float *loc,
     msda::BandPlan pl = msda::plan_band(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data());
     if (!pl.ok) return hipErrorNotSupported;
     pl.g.stamps = msda::tiled_options().stamps;
-    if ((reinterpret_cast<uintptr_t>(grad_loc) | reinterpret_cast<uintptr_t>(loc)) & 7) return hipErrorNotSupported;
-    constexpr uintptr_t row_align = sizeof(TV) * 4 - 1;   // 16 B (fp32) / 8 B (bf16) per lane access
-    if ((reinterpret_cast<uintptr_t>(value) | reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(grad_value)) & row_align)
-        return hipErrorNotSupported;
+    // rows: 16 B (fp32) / 8 B (bf16) per lane access
+    if (!aligned(8, {grad_loc, loc}) || !aligned(sizeof(TV) * 4, {value, grad_out, grad_value}) || !aligned(16, {grad_acc})) return hipErrorNotSupported;
     if (pl.atomic_levels && !grad_acc) return hipErrorNotSupported;
-    if (reinterpret_cast<uintptr_t>(grad_acc) & 15) return hipErrorNotSupported;
     hipError_t e;
     if (pl.atomic_levels)      // the levels several workgroups add to: zero in every image
         hipLaunchKernelGGL(msda::band_zero_kernel, dim3(128), dim3(256), 0, stream, grad_acc, pl.g, pl.atomic_levels);
@@ -693,13 +708,12 @@ int forward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, con
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
     if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, sizeof(TV)) || !is_aligned(out, sizeof(TV)) || !is_aligned(aw, sizeof(T)) ||
-        !is_aligned(loc, 2 * sizeof(T)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
+    if (!aligned(sizeof(TV), {value, out}) || !aligned(sizeof(T), {aw}) || !aligned(2 * sizeof(T), {loc}) || !aligned(8, {shapes, lsi}))
         return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs %s)", kBf16 ? "8 bytes" : "2*sizeof(T)");
 
     int variant = g_tl_fwd_variant >= 0 ? g_tl_fwd_variant : g_fwd_variant.load();
     if constexpr (std::is_same<T, float>::value) {      // the LDS-window kernel (msda_tiled.h): fp32 compute, rows read four channels at a time
-        if (variant != 1 && is_aligned(value, 4 * sizeof(TV)) && is_aligned(out, 4 * sizeof(TV)) &&
+        if (variant != 1 && aligned(4 * sizeof(TV), {value, out}) &&
             msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
             const FwdChoice ch = choose_window_fwd(variant, pb, loc, stream);      // automatic: follow the locality monitor
             variant = ch.variant;
@@ -732,9 +746,7 @@ int forward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, con
         if (many_items(pb)) hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 6, TV>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g);
         else hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 4, TV>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the direct forward kernel", kTag);
-    return MSDA_OK;
+    return launched("launch of the direct forward kernel", kTag);
 }
 
 // One attempt at a backward kernel that may answer hipErrorNotSupported -- its plan does not apply, or no workspace can be had right
@@ -767,9 +779,8 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
     if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, sizeof(TV)) || !is_aligned(grad_out, sizeof(TV)) || !is_aligned(grad_value, sizeof(TV)) ||
-        !is_aligned(aw, sizeof(T)) || !is_aligned(grad_aw, sizeof(T)) || !is_aligned(loc, 2 * sizeof(T)) ||
-        !is_aligned(grad_loc, 2 * sizeof(T)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
+    if (!aligned(sizeof(TV), {value, grad_out, grad_value}) || !aligned(sizeof(T), {aw, grad_aw}) || !aligned(2 * sizeof(T), {loc, grad_loc}) ||
+        !aligned(8, {shapes, lsi}))
         return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc / grad_sampling_loc need %s)", kBf16 ? "8 bytes" : "2*sizeof(T)");
     const size_t n_value = (size_t)N * S * M * D;
     hipError_t e = hipSuccess;
@@ -785,7 +796,7 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
     if constexpr (std::is_same<T, float>::value) {
         int variant = g_bwd_variant.load();
         if (variant == 0) variant = Lq == S ? 4 : 1;
-        const bool rows = !kBf16 || (is_aligned(value, 8) && is_aligned(grad_out, 8) && is_aligned(grad_value, 8));
+        const bool rows = !kBf16 || aligned(8, {value, grad_out, grad_value});
         float *acc = nullptr;
         if constexpr (!kBf16) acc = grad_value;
         if (variant == 4 && rows && (!kBf16 || (D == msda::kRpsD && bf16_scratch(stream, n_value, &acc)))) {
@@ -851,7 +862,7 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
         if (ls_levels) {
             // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
             // for element alignment only)
-            const bool vec = P == 4 && is_aligned(loc, 16) && is_aligned(aw, 16);
+            const bool vec = P == 4 && aligned(16, {loc, aw});
             auto kern = vec ? &msda::bwd_levelsum_kernel<true, TV> : &msda::bwd_levelsum_kernel<false, TV>;
             if ((e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), ls_lds)) != hipSuccess)
                 return hip_fail(e, kBf16 ? "LDS limit" : "launch of the level-sum backward kernel");
@@ -873,7 +884,7 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
     if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the direct backward kernel", kTag);
     if constexpr (kBf16) {
         if (ls_levels != all_levels) {      // one rounding of the fp32 sums
-            const size_t n4 = is_aligned(grad_value, 8) ? n_value / 4 : 0;
+            const size_t n4 = aligned(8, {grad_value}) ? n_value / 4 : 0;
             hipLaunchKernelGGL(round_to_bf16_kernel, dim3(2048), dim3(256), 0, stream, acc, grad_value, n4, n_value);
             if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "rounding grad_value to bf16");
         }
@@ -900,25 +911,6 @@ int prep_geom(msda::PrepGeom &g, int N, int Lq, int M, int L, int P, int ref_dim
     return MSDA_OK;
 }
 
-template <typename T>
-int roi_align_impl(const T *input, const T *rois, int K, int N, int C, int H, int W, int PH, int PW, double spatial_scale,
-                   int sampling_ratio, int aligned, T *output, msda_stream_t stream)
-{
-    g_err[0] = 0;
-    if (!input || !rois || !output) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (K < 0 || N < 1 || C < 1 || H < 1 || W < 1 || PH < 1 || PW < 1 || sampling_ratio < 0 || !(spatial_scale > 0))
-        return fail(MSDA_ERR_BAD_DIMS, "bad ROIAlign dimensions");
-    const int64_t n_out = (int64_t)K * C * PH * PW;
-    if (n_out == 0) return MSDA_OK;
-    if ((int64_t)N * C * H * W >= ((int64_t)1 << 40)) return fail(MSDA_ERR_TOO_LARGE, "input too large");
-    const int grid = (int)std::min<int64_t>((n_out + 255) / 256, 65536);
-    hipLaunchKernelGGL(msda::roi_align_fwd_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), input, rois, n_out, N, C,
-                       H, W, PH, PW, (T)spatial_scale, sampling_ratio, aligned, output);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the ROIAlign kernel");
-    return MSDA_OK;
-}
-
 template <typename T, typename TP = T>
 int prep_forward_impl(const TP *offsets, int64_t off_stride, const TP *logits, int64_t log_stride, const T *ref, int ref_dim,
                       const int64_t *shapes_host, int N, int Lq, int M, int L, int P, T *loc, T *aw, msda_stream_t stream_)
@@ -934,9 +926,7 @@ int prep_forward_impl(const TP *offsets, int64_t off_stride, const TP *logits, i
     const int64_t items = (int64_t)N * Lq * M, per_block = 256 / g.G;
     const int grid = (int)std::min<int64_t>((items + per_block - 1) / per_block, 8192);
     hipLaunchKernelGGL((msda::prep_forward_kernel<T, TP>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), offsets, logits, ref, loc, aw, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the location / softmax kernel");
-    return MSDA_OK;
+    return launched("launch of the location / softmax kernel");
 }
 
 template <typename T, typename TP = T>
@@ -958,22 +948,7 @@ int prep_backward_impl(const T *grad_loc, const T *grad_aw, const T *aw, const T
     const int grid = (int)std::min<int64_t>((items + per_block - 1) / per_block, 8192);
     hipLaunchKernelGGL((msda::prep_backward_kernel<T, TP>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), grad_loc, grad_aw,
                        aw, offsets, ref, grad_offsets, grad_logits, grad_ref, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the location / softmax backward kernel");
-    return MSDA_OK;
-}
-
-template <typename T>
-int mask_rows_impl(T *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream_)
-{
-    g_err[0] = 0;
-    if (!x || !mask) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (rows <= 0 || row_elems <= 0) return fail(MSDA_ERR_BAD_DIMS, "non-positive dimension");
-    const int grid = (int)std::min<int64_t>((rows + 255) / 256, 4096);
-    hipLaunchKernelGGL(msda::mask_rows_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), x, mask, (long long)rows, row_elems);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the padding-mask kernel");
-    return MSDA_OK;
+    return launched("launch of the location / softmax backward kernel");
 }
 
 }  // namespace
@@ -1004,9 +979,9 @@ int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi
             Problem pb{N, S, M, D, L, Lq, P, {}, {}};
             if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
             constexpr size_t row_align = sizeof(TV) * 4;
-            const bool aligned = is_aligned(value, row_align) && is_aligned(out, row_align) && is_aligned(offsets, 2 * sizeof(TP)) && off_stride % 2 == 0 &&
-                                 is_aligned(logits, sizeof(TP)) && is_aligned(ref, 8) && is_aligned(loc, 8) && is_aligned(aw, 4);
-            if (aligned && msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
+            const bool rows_ok = aligned(row_align, {value, out}) && aligned(2 * sizeof(TP), {offsets}) && off_stride % 2 == 0 &&
+                                 aligned(sizeof(TP), {logits}) && aligned(8, {ref, loc}) && aligned(4, {aw});
+            if (rows_ok && msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
                 const FwdChoice ch = choose_window_fwd(g_fwd_variant.load(), pb, loc, stream);
                 if (ch.variant == 2) {
                     const msda::TiledPrepSrc src{offsets, logits, (long long)off_stride, (long long)log_stride, ref, ref_dim, loc, aw};
@@ -1032,8 +1007,8 @@ int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi
     }
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
     if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!is_aligned(value, sizeof(TV)) || !is_aligned(out, sizeof(TV)) || !is_aligned(aw, sizeof(T)) || !is_aligned(loc, 2 * sizeof(T)) ||
-        !is_aligned(ref, sizeof(T)) || !is_aligned(offsets, sizeof(TP)) || !is_aligned(logits, sizeof(TP)) || !is_aligned(shapes, 8) || !is_aligned(lsi, 8))
+    if (!aligned(sizeof(TV), {value, out}) || !aligned(sizeof(T), {aw, ref}) || !aligned(2 * sizeof(T), {loc}) || !aligned(sizeof(TP), {offsets, logits}) ||
+        !aligned(8, {shapes, lsi}))
         return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs 2*sizeof(T))");
     const int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, out});
     const msda::DirectGeom g = direct_geom(pb, C);
@@ -1047,9 +1022,7 @@ int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi
         if (many_items(pb)) hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 6, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g);
         else hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 4, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g);
     });
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the fused location / softmax / gather kernel");
-    return MSDA_OK;
+    return launched("launch of the fused location / softmax / gather kernel");
 }
 
 // The options: one table read by msda_set_option and msda_get_option.  A value is accepted when it lies in [lo, hi] and, where `values`
@@ -1358,78 +1331,6 @@ int msda_prep_backward_bf16(const float *grad_loc, const float *grad_aw, const f
     return prep_backward_impl<float, msda::bf16_t>(grad_loc, grad_aw, aw, reinterpret_cast<const msda::bf16_t *>(offsets), off_stride, ref,
                                                    ref_dim, shapes_host, N, Lq, M, L, P, reinterpret_cast<msda::bf16_t *>(grad_offsets),
                                                    goff_stride, reinterpret_cast<msda::bf16_t *>(grad_logits), glog_stride, grad_ref, stream);
-}
-
-int msda_dn_indices_i64(const int64_t *cum, int batch, int64_t total, int groups2, int64_t single_pad, int64_t *known_bid,
-                        int64_t *map_known_indice, msda_stream_t stream)
-{
-    g_err[0] = 0;
-    if (!cum || !known_bid || !map_known_indice) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (batch < 1 || total < 0 || groups2 < 0 || single_pad < 0) return fail(MSDA_ERR_BAD_DIMS, "bad denoising dimensions");
-    const int64_t n = total * groups2;
-    if (n == 0) return MSDA_OK;
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL(msda::dn_indices_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), cum, batch, total, n, single_pad,
-                       known_bid, map_known_indice);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the denoising index kernel");
-    return MSDA_OK;
-}
-
-int msda_dn_attn_mask_u8(uint8_t *mask, int64_t tgt_size, int64_t pad_size, int64_t group_pad, msda_stream_t stream)
-{
-    g_err[0] = 0;
-    if (!mask) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (tgt_size < 0 || pad_size < 0 || pad_size > tgt_size || group_pad < 0) return fail(MSDA_ERR_BAD_DIMS, "bad mask dimensions");
-    if (tgt_size == 0) return MSDA_OK;
-    const int64_t n = tgt_size * tgt_size;
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL(msda::dn_attn_mask_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), mask, tgt_size, pad_size,
-                       group_pad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the denoising mask kernel");
-    return MSDA_OK;
-}
-
-int msda_roi_align_forward_f32(const float *input, const float *rois, int K, int N, int C, int H, int W, int pooled_h, int pooled_w,
-                               double spatial_scale, int sampling_ratio, int aligned, float *output, msda_stream_t stream)
-{
-    return roi_align_impl<float>(input, rois, K, N, C, H, W, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, output, stream);
-}
-int msda_roi_align_forward_f64(const double *input, const double *rois, int K, int N, int C, int H, int W, int pooled_h, int pooled_w,
-                               double spatial_scale, int sampling_ratio, int aligned, double *output, msda_stream_t stream)
-{
-    return roi_align_impl<double>(input, rois, K, N, C, H, W, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, output, stream);
-}
-
-int msda_topk_f32(const float *scores, int rows, int n, int k, int64_t *indices, float *values, msda_stream_t stream)
-{
-    g_err[0] = 0;
-    if (!scores || !indices) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (rows < 0 || n < 1 || k < 1 || k > n || k > msda::kTopkMaxK || n > msda::kTopkMaxN)
-        return fail(MSDA_ERR_BAD_DIMS, "top-k: 1 <= k <= min(n, %d), n <= %d (got n=%d, k=%d)", msda::kTopkMaxK, msda::kTopkMaxN, n, k);
-    if (rows == 0) return MSDA_OK;
-    const size_t lds = msda::topk_lds_bytes(n);
-    hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(msda::topk_rows_kernel), lds);
-    if (e != hipSuccess) return hip_fail(e, "LDS limit of the top-k kernel");
-    hipLaunchKernelGGL(msda::topk_rows_kernel, dim3(rows), dim3(msda::kTopkThreads), lds, static_cast<hipStream_t>(stream), scores, n, k,
-                       indices, values);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch of the top-k kernel");
-    return MSDA_OK;
-}
-
-int msda_mask_rows_f32(float *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream)
-{
-    return mask_rows_impl<float>(x, mask, rows, row_elems, stream);
-}
-int msda_mask_rows_f64(double *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream)
-{
-    return mask_rows_impl<double>(x, mask, rows, row_elems, stream);
-}
-int msda_mask_rows_bf16(uint16_t *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream)
-{
-    return mask_rows_impl<uint16_t>(x, mask, rows, row_elems, stream);
 }
 
 }  // extern "C"

@@ -20,12 +20,11 @@
 #pragma once
 
 #include <atomic>
-#include <map>
-#include <mutex>
 #include <type_traits>
 #include <utility>
 
 #include "msda_common.h"
+#include "msda_host.h"      // set_lds_limit
 
 namespace msda {
 
@@ -938,22 +937,6 @@ inline int persistent_grid(int total, int cap, int nsub)
     int g8 = cap / kXcds;
     while (g8 > 1 && gcd(g8, nsub) != 1) --g8;
     return g8 * kXcds;
-}
-
-// Raise a kernel's dynamic-LDS limit.  Done once per (device, kernel, size class): repeating the runtime call on every
-// launch costs time and is not something to issue while the caller captures its stream into a graph.
-inline hipError_t set_lds_limit(const void *fn, size_t bytes)
-{
-    static std::mutex mu;
-    static std::map<std::pair<int, const void *>, size_t> granted;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lock(mu);
-    size_t &have = granted[std::make_pair(dev, fn)];
-    if (have >= bytes) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) have = bytes;
-    return e;
 }
 
 // TV = float or bf16_t (storage of value / out); loc / attn are fp32

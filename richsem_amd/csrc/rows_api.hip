@@ -1,38 +1,41 @@
-// rows_api.hip -- C ABI of the rows around the operator that SURVEY.md section 8 marks "next" (declared in
-// include/richsem_msda.h): the matcher's cost blocks (section 8f rank 4), the attention-pool core (rank 3).  A translation unit of its own so that the operator's
-// kernels (msda_api.hip) are not rebuilt with it.  Error reporting: return codes + msda_note_error() (msda_api.hip), so msda_last_error() names the failed call.
+// rows_api.hip -- C ABI of the rows around the operator (declared in include/richsem_msda.h): the matcher's cost blocks and the assignment
+// solver, the attention-pool core, the criterion's focal / box-pair / federated kernels, the decoder's box refinement and sine embedding,
+// the narrow linear backward, PostProcess (top-k over query x class, box decode, NMS), and the module-level helpers that are not the
+// operator itself: the denoising indices and mask, per-row top-k, ROIAlign and the padding-mask rows.  A translation unit of its own so
+// that the operator's kernels (msda_api.hip) are not rebuilt with it.  Error reporting: msda_host.h.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
 #include <cstdint>
 
-#include "../../include/richsem_msda.h"
-
-extern "C" int msda_note_error(int code, const char *entry);      // msda_api.hip: sets msda_last_error()
+#include "msda_host.h"
 #include "msda_attnpool.h"
 #include "msda_matcher.h"
 #include "msda_lsap.h"
 #include "msda_postproc.h"
+#include "msda_dn.h"
+#include "msda_topk.h"
+#include "msda_roi.h"
+#include "msda_prep.h"      // (mask_rows_kernel)
 
 namespace {
 
 template <typename T, bool TM = false>
-int matcher_cost_impl(const T *logits, const T *boxes, const int64_t *tgt_ids, const T *tgt_boxes, const int64_t *tgt_offsets, int B,
+int matcher_cost_impl(const char *entry, const T *logits, const T *boxes, const int64_t *tgt_ids, const T *tgt_boxes, const int64_t *tgt_offsets, int B,
                       int Q, int C, int64_t n_targets, double w_class, double w_bbox, double w_giou, double alpha, T *cost,
                       msda_stream_t stream)
 {
-    if (!logits || !boxes || !tgt_offsets || !cost) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (B < 1 || Q < 0 || C < 1 || n_targets < 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if (n_targets > 0 && (!tgt_ids || !tgt_boxes)) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!logits || !boxes || !tgt_offsets || !cost) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (B < 1 || Q < 0 || C < 1 || n_targets < 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (n_targets > 0 && (!tgt_ids || !tgt_boxes)) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     const int64_t total = (int64_t)Q * n_targets;
     if (total == 0) return MSDA_OK;
-    if (total >= ((int64_t)1 << 40)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
+    if (total >= ((int64_t)1 << 40)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 16384);
     hipLaunchKernelGGL((msda::matcher_cost_kernel<T, TM>), dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, boxes, tgt_ids,
                        tgt_boxes, tgt_offsets, B, Q, C, (T)w_class, (T)w_bbox, (T)w_giou, (T)alpha, cost);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(entry);
 }
 
 // the LDS a launch of the solver needs, or a negative error: the host knows Q and the total number of targets only
@@ -47,40 +50,31 @@ int lsap_sizes(int n_out, int B, int Q, int64_t n_targets, int *cols_cap, int *r
 }
 
 template <typename T>
-int lsap_impl(const T *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
+int lsap_impl(const char *entry, const T *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
               int64_t *query_of_target, int32_t *status, msda_stream_t stream)
 {
-    if (!tgt_offsets || !status || (n_targets > 0 && (!query_of_target || (Q > 0 && !cost)))) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!tgt_offsets || !status || (n_targets > 0 && (!query_of_target || (Q > 0 && !cost)))) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     int cols_cap = 0, rows_cap = 0;
     size_t lds = 0;
     const int rc = lsap_sizes(n_out, B, Q, n_targets, &cols_cap, &rows_cap, &lds);
-    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
-    if (lds > 64 * 1024) {      // beyond the default limit of dynamic LDS: raised once per device (the attribute is per kernel and device)
-        static bool raised[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return (int)e;
-        if (dev < 0 || dev >= 64 || !raised[dev]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(msda::lsap_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)msda::lsap_lds_bytes(msda::kLsapMaxDim, msda::kLsapMaxDim));
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0 && dev < 64) raised[dev] = true;
-        }
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
+    if (lds > 64 * 1024) {      // beyond the default limit of dynamic LDS
+        const hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(msda::lsap_kernel<T>), msda::lsap_lds_bytes(msda::kLsapMaxDim, msda::kLsapMaxDim));
+        if (e != hipSuccess) return msda::hip_fail(e, entry);
     }
     hipLaunchKernelGGL(msda::lsap_kernel<T>, dim3(n_out * B), dim3(64), lds, static_cast<hipStream_t>(stream), cost, target_major, tgt_offsets, B, Q,
                        n_targets, cols_cap, rows_cap, query_of_target, status);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(entry);
 }
 
 template <typename T>
-int attnpool_core_impl(const T *u, const T *feat, const T *pos, const T *spos, int K, int H, int C, int Tn, int head_major, T *z,
+int attnpool_core_impl(const char *entry, const T *u, const T *feat, const T *pos, const T *spos, int K, int H, int C, int Tn, int head_major, T *z,
                        msda_stream_t stream)
 {
-    if (!u || !feat || !pos || !spos || !z) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (K < 0 || H < 1 || C < 1 || Tn < 1 || Tn > msda::kAttnPoolMaxT) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!u || !feat || !pos || !spos || !z) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (K < 0 || H < 1 || C < 1 || Tn < 1 || Tn > msda::kAttnPoolMaxT) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     if (K == 0) return MSDA_OK;
-    if ((int64_t)K * H >= ((int64_t)1 << 31) || (int64_t)K * C * Tn >= ((int64_t)1 << 40)) return msda_note_error(MSDA_ERR_TOO_LARGE, __func__);
+    if ((int64_t)K * H >= ((int64_t)1 << 31) || (int64_t)K * C * Tn >= ((int64_t)1 << 40)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
     const int waves = msda::kAttnPoolThreads / msda::kWave;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (H % 4 == 0) {
@@ -92,8 +86,7 @@ int attnpool_core_impl(const T *u, const T *feat, const T *pos, const T *spos, i
         hipLaunchKernelGGL((msda::attnpool_core_kernel<T, 1>), dim3(K * H), dim3(msda::kAttnPoolThreads), lds, st, u, feat, pos, spos, K, H, C,
                            Tn, head_major, z);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(entry);
 }
 
 // gen_sineembed_for_position (models/richsem/utils.py:142-168): one thread per (token, pair of channels) writes sin | cos of
@@ -368,25 +361,23 @@ extern "C" {
 int msda_focal_neg_sum_f32(const float *logits, const float *row_weight, int64_t rows, int C, float alpha, double *partial, int max_partial,
                            int *n_partial, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !partial || !n_partial) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1 || max_partial < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!logits || !row_weight || !partial || !n_partial) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows < 1 || C < 1 || max_partial < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int grid = (int)std::min<int64_t>(std::min<int64_t>(rows, 4096), max_partial);
     *n_partial = grid;
     hipLaunchKernelGGL(focal_neg_sum_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
                        1.f - alpha, partial);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 int msda_focal_neg_grad_f32(const float *logits, const float *row_weight, int64_t rows, int C, float alpha, const float *gscale,
                             float *grad_logits, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !gscale || !grad_logits) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!logits || !row_weight || !gscale || !grad_logits) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows < 1 || C < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int grid = (int)std::min<int64_t>(rows, 8192);
     hipLaunchKernelGGL(focal_neg_grad_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
                        1.f - alpha, gscale, grad_logits);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* msda_fed_class_mask_f32: per group g, mask[g][c] = 1 for the classes among labels and for m = max(num_sample_cats - appeared, 0) more
@@ -396,38 +387,35 @@ int msda_focal_neg_grad_f32(const float *logits, const float *row_weight, int64_
 int msda_fed_class_mask_f32(const int64_t *labels, int64_t n_labels, const float *class_weight, const float *uniform, int groups, int C,
                             int num_sample_cats, float *mask, int32_t *n_chosen, msda_stream_t stream)
 {
-    if (!class_weight || !uniform || !mask || !n_chosen || (n_labels > 0 && !labels)) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (n_labels < 0 || groups < 1 || C < 1 || C > msda::kFedMaxClasses || num_sample_cats < 0) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!class_weight || !uniform || !mask || !n_chosen || (n_labels > 0 && !labels)) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (n_labels < 0 || groups < 1 || C < 1 || C > msda::kFedMaxClasses || num_sample_cats < 0) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     int P2 = 1;
     while (P2 < C) P2 <<= 1;
     const int threads = std::min(msda::kFedThreads, std::max(64, P2 / 2));
     hipLaunchKernelGGL(msda::fed_class_mask_kernel, dim3(groups), dim3(threads), sizeof(unsigned long long) * P2, static_cast<hipStream_t>(stream),
                        labels, (long long)n_labels, class_weight, uniform, C, P2, num_sample_cats, mask, n_chosen);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 int msda_focal_neg_sum_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
                                   int64_t rows, int C, float alpha, double *partial, int max_partial, int *n_partial, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !row_group || !class_mask || !partial || !n_partial) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1 || groups < 1 || max_partial < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!logits || !row_weight || !row_group || !class_mask || !partial || !n_partial) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows < 1 || C < 1 || groups < 1 || max_partial < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int grid = (int)std::min<int64_t>(std::min<int64_t>(rows, 4096), max_partial);
     *n_partial = grid;
     hipLaunchKernelGGL(msda::focal_neg_sum_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
                        class_mask, groups, (long long)rows, C, 1.f - alpha, partial);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
                                    int64_t rows, int C, float alpha, const float *gscale, float *grad_logits, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !row_group || !class_mask || !gscale || !grad_logits) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1 || groups < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!logits || !row_weight || !row_group || !class_mask || !gscale || !grad_logits) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows < 1 || C < 1 || groups < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int grid = (int)std::min<int64_t>(rows, 8192);
     hipLaunchKernelGGL(msda::focal_neg_grad_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
                        class_mask, groups, (long long)rows, C, 1.f - alpha, gscale, grad_logits);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* The criterion's per-pair tails, one launch each (K pairs, float32, one workgroup): loss[0] <- the weighted sum, grad (K, 4) / (K) <- its
@@ -438,21 +426,18 @@ int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight,
 int msda_box_pair_loss_f32(const float *pred, const float *target, const float *weight, int K, float c_l1, float c_giou, float *loss, float *grad_pred,
                            msda_stream_t stream)
 {
-    if (!pred || !target || !weight || !loss || !grad_pred) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (K < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(grad_pred)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!pred || !target || !weight || !loss || !grad_pred) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (K < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {pred, target, grad_pred})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipLaunchKernelGGL(box_pair_loss_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), pred, target, weight, K, c_l1, c_giou, loss, grad_pred);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 int msda_focal_pos_sum_f32(const float *x, const float *weight, int K, float alpha, float *loss, float *grad_x, msda_stream_t stream)
 {
-    if (!x || !weight || !loss || !grad_x) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (K < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!x || !weight || !loss || !grad_x) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (K < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     hipLaunchKernelGGL(focal_pos_sum_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), x, weight, K, alpha, loss, grad_x);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* Backward of y = x W^T + b for a 256 -> n layer, n <= 8: dy (T, n) bf16 contiguous, x (T, 256) bf16, w (n, 256) f32 -> dx (T, 256) bf16
@@ -460,13 +445,13 @@ int msda_focal_pos_sum_f32(const float *x, const float *weight, int K, float alp
 int msda_narrow_linear_backward_bf16(const uint16_t *dy, const uint16_t *x, const float *w, int T, int n, uint16_t *dx, float *dw, float *db,
                                      msda_stream_t stream)
 {
-    if (!dy || !x || !w || !dw) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (T < 1 || n < 1 || n > 8) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(x)) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!dy || !x || !w || !dw) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (T < 1 || n < 1 || n > 8) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {dx, x})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * n * 256, st);
     if (e == hipSuccess && db) e = hipMemsetAsync(db, 0, sizeof(float) * n, st);
-    if (e != hipSuccess) return (int)e;
+    if (e != hipSuccess) return msda::hip_fail(e, __func__);
     if (dx) {
         const long long total = (long long)T * 32;
         hipLaunchKernelGGL(narrow_linear_dx_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, st, dy,
@@ -474,22 +459,20 @@ int msda_narrow_linear_backward_bf16(const uint16_t *dy, const uint16_t *x, cons
     }
     const int chunk = T >= 65536 ? 256 : (T >= 8192 ? 128 : 32);
     hipLaunchKernelGGL(narrow_linear_dw_kernel, dim3((unsigned)((T + chunk - 1) / chunk)), dim3(256), 0, st, dy, x, T, n, chunk, dw, db);
-    e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* y = sigmoid(delta + inverse_sigmoid(ref)): delta (n) bf16 or f32, ref (n) f32, y (n) f32 */
 int msda_box_refine_forward(const void *delta, int delta_is_bf16, const float *ref, float eps, int64_t n, float *y, msda_stream_t stream)
 {
-    if (!delta || !ref || !y) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (n < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!delta || !ref || !y) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (n < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     if (delta_is_bf16)
         hipLaunchKernelGGL(box_refine_kernel<true>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), delta, ref, eps, (long long)n, y);
     else
         hipLaunchKernelGGL(box_refine_kernel<false>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), delta, ref, eps, (long long)n, y);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* grad_delta = grad_y * y * (1 - y), written in delta's type */
@@ -502,8 +485,8 @@ int msda_box_refine_backward(const float *grad_y, const float *y, int64_t n, voi
 int msda_box_refine_backward_ref(const float *grad_y, const float *y, int64_t n, void *grad_delta, int delta_is_bf16, const float *ref, float eps,
                                  float *grad_ref, msda_stream_t stream)
 {
-    if (!grad_y || !y || !grad_delta || (grad_ref && !ref)) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (n < 1) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
+    if (!grad_y || !y || !grad_delta || (grad_ref && !ref)) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (n < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
     const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
     if (delta_is_bf16)
         hipLaunchKernelGGL(box_refine_grad_kernel<true>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), grad_y, y, (long long)n, grad_delta,
@@ -511,48 +494,46 @@ int msda_box_refine_backward_ref(const float *grad_y, const float *y, int64_t n,
     else
         hipLaunchKernelGGL(box_refine_grad_kernel<false>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), grad_y, y, (long long)n, grad_delta,
                            ref, eps, grad_ref);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 /* the decoder's positional query embedding: boxes (tokens, >= dims) f32 with row stride ld (floats), dims = 2 | 4 -> out (tokens,
  * dims * pe_dim) bf16 */
 int msda_sine_embed_bf16(const float *boxes, int ld, int tokens, int dims, int pe_dim, float temperature, uint16_t *out, msda_stream_t stream)
 {
-    if (!boxes || !out) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (tokens < 1 || (dims != 2 && dims != 4) || ld < dims || pe_dim < 2 || (pe_dim & 1) || !(temperature > 0.f)) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if (reinterpret_cast<uintptr_t>(out) & 3) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!boxes || !out) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (tokens < 1 || (dims != 2 && dims != 4) || ld < dims || pe_dim < 2 || (pe_dim & 1) || !(temperature > 0.f)) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(4, {out})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     const long long n = (long long)tokens * dims * (pe_dim / 2);
     const int grid = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     hipLaunchKernelGGL(sine_embed_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), boxes, ld, tokens, dims, pe_dim,
                        log2f(temperature), reinterpret_cast<unsigned *>(out));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 int msda_attnpool_core_f32(const float *u, const float *feat, const float *pos, const float *spos, int K, int H, int C, int T,
                            int head_major, float *z, msda_stream_t stream)
 {
-    return attnpool_core_impl<float>(u, feat, pos, spos, K, H, C, T, head_major, z, stream);
+    return attnpool_core_impl<float>(__func__, u, feat, pos, spos, K, H, C, T, head_major, z, stream);
 }
 int msda_attnpool_core_f64(const double *u, const double *feat, const double *pos, const double *spos, int K, int H, int C, int T,
                            int head_major, double *z, msda_stream_t stream)
 {
-    return attnpool_core_impl<double>(u, feat, pos, spos, K, H, C, T, head_major, z, stream);
+    return attnpool_core_impl<double>(__func__, u, feat, pos, spos, K, H, C, T, head_major, z, stream);
 }
 
 int msda_matcher_cost_f32(const float *logits, const float *boxes, const int64_t *tgt_ids, const float *tgt_boxes,
                           const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
                           double w_giou, double alpha, float *cost, msda_stream_t stream)
 {
-    return matcher_cost_impl<float>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
+    return matcher_cost_impl<float>(__func__, logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
                                     cost, stream);
 }
 int msda_matcher_cost_f64(const double *logits, const double *boxes, const int64_t *tgt_ids, const double *tgt_boxes,
                           const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
                           double w_giou, double alpha, double *cost, msda_stream_t stream)
 {
-    return matcher_cost_impl<double>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
+    return matcher_cost_impl<double>(__func__, logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
                                      cost, stream);
 }
 
@@ -560,24 +541,24 @@ int msda_matcher_cost_tm_f32(const float *logits, const float *boxes, const int6
                              const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
                              double w_giou, double alpha, float *cost, msda_stream_t stream)
 {
-    return matcher_cost_impl<float, true>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
+    return matcher_cost_impl<float, true>(__func__, logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
                                           cost, stream);
 }
 int msda_matcher_cost_tm_f64(const double *logits, const double *boxes, const int64_t *tgt_ids, const double *tgt_boxes,
                              const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
                              double w_giou, double alpha, double *cost, msda_stream_t stream)
 {
-    return matcher_cost_impl<double, true>(logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
+    return matcher_cost_impl<double, true>(__func__, logits, boxes, tgt_ids, tgt_boxes, tgt_offsets, B, Q, C, n_targets, w_class, w_bbox, w_giou, alpha,
                                            cost, stream);
 }
 
 int msda_lsap_workspace_bytes(int n_out, int B, int Q, int64_t n_targets, int64_t *bytes)
 {
-    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     int cols_cap = 0, rows_cap = 0;
     size_t lds = 0;
     const int rc = lsap_sizes(n_out, B, Q, n_targets, &cols_cap, &rows_cap, &lds);
-    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
     *bytes = 0;      // every supported size keeps its state in LDS
     return MSDA_OK;
 }
@@ -585,13 +566,13 @@ int msda_lsap_f32(const float *cost, int target_major, const int64_t *tgt_offset
                   int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream)
 {
     (void)workspace;
-    return lsap_impl<float>(cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
+    return lsap_impl<float>(__func__, cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
 }
 int msda_lsap_f64(const double *cost, int target_major, const int64_t *tgt_offsets, int n_out, int B, int Q, int64_t n_targets,
                   int64_t *query_of_target, int32_t *status, void *workspace, msda_stream_t stream)
 {
     (void)workspace;
-    return lsap_impl<double>(cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
+    return lsap_impl<double>(__func__, cost, target_major, tgt_offsets, n_out, B, Q, n_targets, query_of_target, status, stream);
 }
 
 }  // extern "C"
@@ -631,9 +612,9 @@ extern "C" {
 
 int msda_postprocess_workspace_bytes(int B, int Q, int C, int k, int64_t *bytes)
 {
-    if (!bytes) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     const int rc = postprocess_dims(B, Q, C, k);
-    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
     const int64_t words = (int64_t)B * (msda::kPpZeroWords + 2 * msda::kPpMaxK +
                                          (int64_t)(1 + msda::kPpEqSlots) * msda::pp_chunks((int64_t)Q * C));
     *bytes = (words * 4 + 15) & ~(int64_t)15;
@@ -645,13 +626,11 @@ int msda_postprocess_select(const void *logits, int logits_is_bf16, const float 
                             msda_stream_t stream)
 {
     if (!logits || !boxes || !sizes_hw || !scores || !labels || !out_boxes || !query_idx || !workspace)
-        return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
     const int rc = postprocess_dims(B, Q, C, k);
-    if (rc != MSDA_OK) return msda_note_error(rc, __func__);
-    if (box_mode < 0 || box_mode > 2) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(boxes) | reinterpret_cast<uintptr_t>(out_boxes) |
-         reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
+    if (box_mode < 0 || box_mode > 2) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {logits, boxes, out_boxes, workspace})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     hipStream_t st = static_cast<hipStream_t>(stream);
     // histograms, tickets and counters start every call at zero (a replayed graph or a second call on the same workspace starts clean)
     const int zero_words = B * msda::kPpZeroWords;
@@ -661,33 +640,122 @@ int msda_postprocess_select(const void *logits, int logits_is_bf16, const float 
         postprocess_launch<true>(logits, boxes, sizes_hw, B, Q, C, k, box_mode, scores, labels, out_boxes, query_idx, static_cast<unsigned *>(workspace), st);
     else
         postprocess_launch<false>(logits, boxes, sizes_hw, B, Q, C, k, box_mode, scores, labels, out_boxes, query_idx, static_cast<unsigned *>(workspace), st);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
 }
 
 int msda_nms_f32(const float *boxes_xyxy, const int64_t *labels_or_null, int B, int K, float iou_threshold, uint8_t *keep, int64_t *kept_idx,
                  int32_t *n_kept, msda_stream_t stream)
 {
-    if (!boxes_xyxy || !keep || !kept_idx || !n_kept) return msda_note_error(MSDA_ERR_NULL_POINTER, __func__);
-    if (B < 1 || K < 1 || K > msda::kNmsMaxK) return msda_note_error(MSDA_ERR_BAD_DIMS, __func__);
-    if (reinterpret_cast<uintptr_t>(boxes_xyxy) & 15) return msda_note_error(MSDA_ERR_MISALIGNED, __func__);
+    if (!boxes_xyxy || !keep || !kept_idx || !n_kept) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (B < 1 || K < 1 || K > msda::kNmsMaxK) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!msda::aligned(16, {boxes_xyxy})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
     const size_t lds = msda::nms_lds_bytes(K);
-    if (lds > 64 * 1024) {      // beyond the default limit of dynamic LDS: raised once per device, as for the assignment solver
-        static bool raised[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return (int)e;
-        if (dev < 0 || dev >= 64 || !raised[dev]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(msda::nms_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)msda::nms_lds_bytes(msda::kNmsMaxK));
-            if (e != hipSuccess) return (int)e;
-            if (dev >= 0 && dev < 64) raised[dev] = true;
-        }
+    if (lds > 64 * 1024) {      // beyond the default limit of dynamic LDS, as for the assignment solver
+        const hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(msda::nms_kernel), msda::nms_lds_bytes(msda::kNmsMaxK));
+        if (e != hipSuccess) return msda::hip_fail(e, __func__);
     }
     hipLaunchKernelGGL(msda::nms_kernel, dim3(B), dim3(msda::kNmsMaxK), lds, static_cast<hipStream_t>(stream), boxes_xyxy, labels_or_null, K,
                        iou_threshold, keep, kept_idx, n_kept);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MSDA_OK : (int)e;
+    return msda::launched(__func__);
+}
+
+}  // extern "C"
+
+/* ---- module-level helpers that are not the operator: denoising indices and mask (msda_dn.h), per-row top-k (msda_topk.h), ROIAlign
+ * (msda_roi.h), padding-mask rows (msda_prep.h).  Their runtime failures read "<entry point>: launch of ...". ------------------------------ */
+namespace {
+
+template <typename T>
+int roi_align_impl(const char *entry, const T *input, const T *rois, int K, int N, int C, int H, int W, int PH, int PW, double spatial_scale,
+                   int sampling_ratio, int aligned, T *output, msda_stream_t stream)
+{
+    if (!input || !rois || !output) return msda::fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (K < 0 || N < 1 || C < 1 || H < 1 || W < 1 || PH < 1 || PW < 1 || sampling_ratio < 0 || !(spatial_scale > 0))
+        return msda::fail(MSDA_ERR_BAD_DIMS, "bad ROIAlign dimensions");
+    const int64_t n_out = (int64_t)K * C * PH * PW;
+    if (n_out == 0) return MSDA_OK;
+    if ((int64_t)N * C * H * W >= ((int64_t)1 << 40)) return msda::fail(MSDA_ERR_TOO_LARGE, "input too large");
+    const int grid = (int)std::min<int64_t>((n_out + 255) / 256, 65536);
+    hipLaunchKernelGGL(msda::roi_align_fwd_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), input, rois, n_out, N, C,
+                       H, W, PH, PW, (T)spatial_scale, sampling_ratio, aligned, output);
+    return msda::launched(entry, ": launch of the ROIAlign kernel");
+}
+
+template <typename T>
+int mask_rows_impl(const char *entry, T *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream_)
+{
+    if (!x || !mask) return msda::fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (rows <= 0 || row_elems <= 0) return msda::fail(MSDA_ERR_BAD_DIMS, "non-positive dimension");
+    const int grid = (int)std::min<int64_t>((rows + 255) / 256, 4096);
+    hipLaunchKernelGGL(msda::mask_rows_kernel<T>, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream_), x, mask, (long long)rows, row_elems);
+    return msda::launched(entry, ": launch of the padding-mask kernel");
+}
+
+}  // namespace
+
+extern "C" {
+
+int msda_dn_indices_i64(const int64_t *cum, int batch, int64_t total, int groups2, int64_t single_pad, int64_t *known_bid,
+                        int64_t *map_known_indice, msda_stream_t stream)
+{
+    if (!cum || !known_bid || !map_known_indice) return msda::fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (batch < 1 || total < 0 || groups2 < 0 || single_pad < 0) return msda::fail(MSDA_ERR_BAD_DIMS, "bad denoising dimensions");
+    const int64_t n = total * groups2;
+    if (n == 0) return MSDA_OK;
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(msda::dn_indices_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), cum, batch, total, n, single_pad,
+                       known_bid, map_known_indice);
+    return msda::launched(__func__, ": launch of the denoising index kernel");
+}
+
+int msda_dn_attn_mask_u8(uint8_t *mask, int64_t tgt_size, int64_t pad_size, int64_t group_pad, msda_stream_t stream)
+{
+    if (!mask) return msda::fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (tgt_size < 0 || pad_size < 0 || pad_size > tgt_size || group_pad < 0) return msda::fail(MSDA_ERR_BAD_DIMS, "bad mask dimensions");
+    if (tgt_size == 0) return MSDA_OK;
+    const int64_t n = tgt_size * tgt_size;
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(msda::dn_attn_mask_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), mask, tgt_size, pad_size,
+                       group_pad);
+    return msda::launched(__func__, ": launch of the denoising mask kernel");
+}
+
+int msda_roi_align_forward_f32(const float *input, const float *rois, int K, int N, int C, int H, int W, int pooled_h, int pooled_w,
+                               double spatial_scale, int sampling_ratio, int aligned, float *output, msda_stream_t stream)
+{
+    return roi_align_impl<float>(__func__, input, rois, K, N, C, H, W, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, output, stream);
+}
+int msda_roi_align_forward_f64(const double *input, const double *rois, int K, int N, int C, int H, int W, int pooled_h, int pooled_w,
+                               double spatial_scale, int sampling_ratio, int aligned, double *output, msda_stream_t stream)
+{
+    return roi_align_impl<double>(__func__, input, rois, K, N, C, H, W, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, output, stream);
+}
+
+int msda_topk_f32(const float *scores, int rows, int n, int k, int64_t *indices, float *values, msda_stream_t stream)
+{
+    if (!scores || !indices) return msda::fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (rows < 0 || n < 1 || k < 1 || k > n || k > msda::kTopkMaxK || n > msda::kTopkMaxN)
+        return msda::fail(MSDA_ERR_BAD_DIMS, "top-k: 1 <= k <= min(n, %d), n <= %d (got n=%d, k=%d)", msda::kTopkMaxK, msda::kTopkMaxN, n, k);
+    if (rows == 0) return MSDA_OK;
+    const size_t lds = msda::topk_lds_bytes(n);
+    const hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(msda::topk_rows_kernel), lds);
+    if (e != hipSuccess) return msda::hip_fail(e, __func__, ": LDS limit of the top-k kernel");
+    hipLaunchKernelGGL(msda::topk_rows_kernel, dim3(rows), dim3(msda::kTopkThreads), lds, static_cast<hipStream_t>(stream), scores, n, k,
+                       indices, values);
+    return msda::launched(__func__, ": launch of the top-k kernel");
+}
+
+int msda_mask_rows_f32(float *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream)
+{
+    return mask_rows_impl<float>(__func__, x, mask, rows, row_elems, stream);
+}
+int msda_mask_rows_f64(double *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream)
+{
+    return mask_rows_impl<double>(__func__, x, mask, rows, row_elems, stream);
+}
+int msda_mask_rows_bf16(uint16_t *x, const uint8_t *mask, int64_t rows, int row_elems, msda_stream_t stream)
+{
+    return mask_rows_impl<uint16_t>(__func__, x, mask, rows, row_elems, stream);
 }
 
 }  // extern "C"

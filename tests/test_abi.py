@@ -187,6 +187,50 @@ def test_error_notes_of_the_other_translation_units_name_the_call():
     rc = L.msda_sine_embed_bf16(None, 4, 1, 4, 128, 10000.0, None, None)
     with pytest.raises(RuntimeError, match="msda_sine_embed_bf16.*null pointer"):
         _lib.check(rc)
+    # the codes that used to come out as "<entry point>: error": a bad option value, and (on a machine without a GPU) no device
+    assert L.msda_conv_set_ring(5) == -7
+    assert re.fullmatch(r"msda_conv_set_ring: option value .*", _lib.last_error())
+    import torch
+    if not torch.cuda.is_available():
+        buf = (ctypes.c_char * 1024)()
+        p = (ctypes.addressof(buf) + 255) & ~255
+        rc = L.msda_ffn_forward_bf16(p, p, p, p, p, p, p, 1e-5, 4, 256, 2048, p, None)
+        assert rc == -6 and re.fullmatch(r"msda_ffn_forward\w*_bf16: no device.*", _lib.last_error()), _lib.last_error()      # MSDA_ERR_NO_DEVICE
+
+
+def test_a_failed_launch_names_its_own_entry_point():
+    """Without a device every launch fails (hipErrorNoDevice): the call returns the positive hipError_t and msda_last_error() is
+    "<entry point>...: <hipGetErrorString> (hipError N)" of THIS call, not the text an earlier failed call left behind.  One entry point
+    per translation unit.  With a GPU the host pointers below must never reach a launch: skipped before any library call."""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("needs a machine without a GPU: the launches below are meant to fail")
+    L = _lib.load()
+    buf = (ctypes.c_char * 4096)()
+    p = (ctypes.addressof(buf) + 255) & ~255
+    n = ctypes.c_int64(0)
+    seeds = {      # a failed argument check of a DIFFERENT entry point
+        "msda_sine_embed_bf16": lambda: L.msda_sine_embed_bf16(None, 4, 1, 4, 128, 10000.0, None, None),
+        "msda_cls_packed_elems": lambda: L.msda_cls_packed_elems(0, ctypes.byref(n)),
+    }
+    calls = [
+        ("msda_mask_rows_f32", lambda: L.msda_mask_rows_f32(p, p, 4, 8, None)),                                      # rows_api (moved there)
+        ("msda_sine_embed_bf16", lambda: L.msda_sine_embed_bf16(p, 4, 1, 4, 128, 1e4, p, None)),                     # rows_api
+        ("msda_lin256_pack_bf16", lambda: L.msda_lin256_pack_bf16(p, 64, 256, p, None)),                             # lin256_mfma
+        ("msda_ffn_pack_w2_bf16", lambda: L.msda_ffn_pack_w2_bf16(p, 256, 32, p, None)),                             # ffn_mfma
+        ("msda_cls_pack", lambda: L.msda_cls_pack(p, 16, p, 256, p, None)),                                          # cls_mfma
+        ("msda_conv_pack_weight", lambda: L.msda_conv_pack_weight(p, 32, 32, 1, 1, p, None)),                        # conv_mfma
+        ("msda_attn_forward_bf16", lambda: L.msda_attn_forward_bf16(p, 256, p, 256, p, 256, None, 32, 1, 0, 8, p, p, p, None)),   # attn_mfma
+        ("msda_conv_wgrad_bf16", lambda: L.msda_conv_wgrad_bf16(p, p, 1, 4, 4, 128, 128, 1, 1, 1, 0, p, None, None, 0, p, None)),  # conv_wgrad
+    ]
+    for name, call in calls:
+        seed = "msda_cls_packed_elems" if name == "msda_sine_embed_bf16" else "msda_sine_embed_bf16"
+        assert seeds[seed]() < 0 and seed in _lib.last_error()
+        rc = call()
+        text = _lib.last_error()
+        assert rc > 0, (name, rc)
+        assert name in text and "hipError" in text, (name, text)
+        assert seed not in text, (name, text)
 
 
 def test_round4_entry_points_check_their_arguments_on_the_host():
