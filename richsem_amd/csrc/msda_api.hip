@@ -693,7 +693,8 @@ __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restr
 //   bwd_direct_cpl option             honoured                                      ignored
 //   direct backward adds grad_value   into grad_value                               into the fp32 scratch (null when level-sum took everything)
 //   no scratch during stream capture  n/a                                           MSDA_ERR_BAD_DIMS
-//   error texts                       as written                                    + " (bf16)"; "... needs 8 bytes"; "LDS limit"
+//   error texts                       as written                                    the runtime's (HIP) errors + " (bf16)", "LDS limit"; "... needs 8
+//                                                                                   bytes"; the refusals ("too many levels", no scratch) untagged
 int too_many_levels(int L) { return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L); }
 
 template <typename T, typename TV = T>

@@ -151,6 +151,45 @@ def test_argument_errors_are_reported_not_printed(lib):
         _lib.check(-5)
 
 
+# element sizes of (value / out / grad_out / grad_value, sampling_loc / attn_weight and their gradients) per entry-point suffix
+_ELEM = {"f32": (4, 4), "f64": (8, 8), "bf16": (2, 4)}
+
+
+def _call_with_pointers(lib, sfx, backward, bad):
+    """msda_forward_<sfx> / msda_backward_<sfx> with fake device pointers, all 0x1000 except those in ``bad`` (argument name -> address), and
+    the host mirrors given: a call the alignment check refuses never dereferences any of them."""
+    N, S, M, D, L, Lq, P = 2, 30, 2, 4, 2, 5, 2
+    sh = np.asarray([[6, 4], [3, 2]], dtype=np.int64)
+    ls = np.asarray([0, 24], dtype=np.int64)
+    names = ["value", "shapes", "lsi", "loc", "aw"] + (["grad_out"] if backward else [])
+    outs = ["grad_value", "grad_loc", "grad_aw"] if backward else ["out"]
+    assert set(bad) <= set(names + outs)
+    p = lambda k: bad.get(k, 0x1000)
+    fn = getattr(lib, ("msda_backward_" if backward else "msda_forward_") + sfx)
+    return fn(*[p(k) for k in names], N, S, M, D, L, Lq, P, 64, *[p(k) for k in outs], sh.ctypes.data, ls.ctypes.data, None)
+
+
+@pytest.mark.parametrize("sfx", ["f32", "f64", "bf16"])
+def test_every_entry_point_refuses_pointers_below_element_alignment(lib, sfx):
+    """Row "pointer alignment demanded" of the dispatch table (msda_api.hip, above too_many_levels): sizeof(TV) for value / out / grad_out /
+    grad_value, sizeof(T) for attn_weight and its gradient, 2*sizeof(T) for sampling_loc and its gradient -- for bf16 storage 2, 4 and
+    8 bytes -- in all six entry points.  Each call has ONE pointer the library refuses; none is ever dereferenced.  Row "error texts":
+    the bf16 message names "8 bytes", the others "2*sizeof(T)"."""
+    ev, et = _ELEM[sfx]
+    need = "8 bytes" if sfx == "bf16" else "2*sizeof(T)"
+    cases = [(False, k, 0x1000 + ev // 2) for k in ("value", "out")]
+    cases += [(True, k, 0x1000 + ev // 2) for k in ("value", "grad_out", "grad_value")]
+    for backward in (False, True):
+        cases += [(backward, "loc", 0x1000 + et), (backward, "aw", 0x1000 + et // 2)]      # loc: an element boundary, not a pair boundary
+    cases += [(True, "grad_loc", 0x1000 + et), (True, "grad_aw", 0x1000 + et // 2)]
+    for backward, name, addr in cases:
+        assert _call_with_pointers(lib, sfx, backward, {name: addr}) == -5, (sfx, backward, name, hex(addr))      # MSDA_ERR_MISALIGNED
+        text = _lib.last_error()
+        assert "misaligned pointer" in text and need in text, (sfx, backward, name, text)
+        assert ("grad_sampling_loc" in text) == backward, text
+    assert (0x1004, 0x1008)[sfx == "f64"] == 0x1000 + et      # (the addresses the loc cases use: 0x1004 for f32 / bf16, 0x1008 for f64)
+
+
 def test_host_variants_are_declared_and_not_implemented_as_in_the_reference(lib):
     """msda_forward_cpu / msda_backward_cpu (SURVEY.md section 8b "host (_cpu) variants of both"): the reference's bodies are
     AT_ERROR("Not implement on cpu") (src/cpu/ms_deform_attn_cpu.cpp:17-41); these return MSDA_ERR_NOT_ON_CPU with that text, touch no
