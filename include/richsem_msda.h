@@ -649,7 +649,9 @@ int msda_lin256_forward_stacked_bf16(const uint16_t *x, const uint16_t *packed_w
  * apart, a head's 32 channels at column 32 h; out / dout the same rows, heads * 32 wide, contiguous; lse (bs * heads, ceil32(nq)) f32: log2-sum-exp per query, written by the forward, read by
  * the backward; mask_bits (nq, ceil(nq / 32)) uint32: bit j of word (q, kb) set = query q must not attend to key 32 kb + j;
  * maskt_bits the same of the transposed mask (both NULL = no mask); workspace: msda_attn_workspace_bytes(nq, bs, heads) bytes.
- * 16-byte aligned pointers, ld* multiples of 8.  Every element of out / dq / dk / dv is written. */
+ * 16-byte aligned pointers, ld* multiples of 8.  Every element of out / dq / dk / dv is written.  A query whose mask row allows no key
+ * gets out = 0 and lse = +inf, its dq is 0 and it contributes nothing to dk / dv (torch's softmax gives NaN there); the entries
+ * [nq, ceil32(nq)) of every lse row are +inf as well. */
 int64_t msda_attn_workspace_bytes(int nq, int bs, int heads);
 int msda_attn_forward_bf16(const uint16_t *q, int ldq, const uint16_t *k, int ldk, const uint16_t *v, int ldv, const uint32_t *mask_bits,
                            int nq, int bs, int batch_first, int heads, uint16_t *out, float *lse, void *workspace, msda_stream_t stream);
