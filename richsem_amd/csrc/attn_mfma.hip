@@ -32,14 +32,6 @@ constexpr int kHd = 32;            // head dimension
 constexpr int kQW = 16;            // queries (or keys) per wave
 constexpr int kWaves = 4;
 
-__device__ __forceinline__ bf16x8 pack8(const float (&p)[8])
-{
-    const unsigned u0 = pack_bf16(p[0], p[1]), u1 = pack_bf16(p[2], p[3]), u2 = pack_bf16(p[4], p[5]), u3 = pack_bf16(p[6], p[7]);
-    return __builtin_bit_cast(bf16x8, (u32x4){u0, u1, u2, u3});
-}
-__device__ __forceinline__ float xor16(float v) { return __shfl_xor(v, 16, 64); }
-__device__ __forceinline__ float xor32(float v) { return __shfl_xor(v, 32, 64); }
-
 // fragment of a transposed copy X^T (32 x nqp) for the product that sums over an accumulator tile's rows: lane (row d, group g),
 // element j <-> column 32 blk + 16 (j >> 2) + 4 g + (j & 3)
 __device__ __forceinline__ bf16x8 frag_t(const uint16_t *xt, int nqp, int d, int blk, int g)
@@ -140,8 +132,7 @@ __global__ __launch_bounds__(kWaves * 64) void attn_fwd_kernel(const uint16_t *_
             s[j] = dead ? -__builtin_inff() : (j < 4 ? s0[j & 3] : s1[j & 3]) * scale2;
             mx = fmaxf(mx, s[j]);
         }
-        mx = fmaxf(mx, xor16(mx));
-        mx = fmaxf(mx, xor32(mx));
+        mx = lane_groups_max(mx);
         const float m_new = fmaxf(m, mx);
         const float m_use = m_new == -__builtin_inff() ? 0.f : m_new;
         const float alpha = exp2f(m - m_use);     // (m = -inf: 0)
@@ -158,12 +149,11 @@ __global__ __launch_bounds__(kWaves * 64) void attn_fwd_kernel(const uint16_t *_
             o0[i] *= alpha;
             o1[i] *= alpha;
         }
-        const bf16x8 pb = pack8(p);
+        const bf16x8 pb = pack_bf16x8(p);
         o0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v0, pb, o0, 0, 0, 0);
         o1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(v1, pb, o1, 0, 0, 0);
     }
-    l += xor16(l);
-    l += xor32(l);
+    l = lane_groups_sum(l);
     // the four waves' partial results (each over a quarter of the keys) are merged by wave 0
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -198,6 +188,7 @@ __global__ __launch_bounds__(kWaves * 64) void attn_fwd_kernel(const uint16_t *_
     const float inv = l > 0.f ? 1.f / l : 0.f;
     if (qi < nq) {
         uint16_t *op = out + tk.row(qi, b) * (H * kHd) + h * kHd + 4 * g;
+        // (not pack_bf16x4: scaling the tile as a vector first changes this kernel's instructions)
         *reinterpret_cast<uint2 *>(op) = make_uint2(pack_bf16(o0[0] * inv, o0[1] * inv), pack_bf16(o0[2] * inv, o0[3] * inv));
         *reinterpret_cast<uint2 *>(op + 16) = make_uint2(pack_bf16(o1[0] * inv, o1[1] * inv), pack_bf16(o1[2] * inv, o1[3] * inv));
     }
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(kWaves * 64) void attn_bwd_kv_kernel(
             p[j] = dead ? 0.f : exp2f(sv - lv);                   // (rows beyond nq: lse = +inf -> 0)
             ds[j] = p[j] * (dp - dl) * scale;
         }
-        const bf16x8 pb = pack8(p), dsb = pack8(ds);
+        const bf16x8 pb = pack_bf16x8(p), dsb = pack_bf16x8(ds);
         dv0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_do0, pb, dv0, 0, 0, 0);
         dv1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_do1, pb, dv1, 0, 0, 0);
         dk0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_q0, dsb, dk0, 0, 0, 0);
@@ -275,10 +266,10 @@ __global__ __launch_bounds__(kWaves * 64) void attn_bwd_kv_kernel(
         }
     if (ki < nq) {
         uint16_t *pk = dk + tk.row(ki, b) * lddk + h * kHd + 4 * g, *pv = dv + tk.row(ki, b) * lddv + h * kHd + 4 * g;
-        *reinterpret_cast<uint2 *>(pk) = make_uint2(pack_bf16(dk0[0], dk0[1]), pack_bf16(dk0[2], dk0[3]));
-        *reinterpret_cast<uint2 *>(pk + 16) = make_uint2(pack_bf16(dk1[0], dk1[1]), pack_bf16(dk1[2], dk1[3]));
-        *reinterpret_cast<uint2 *>(pv) = make_uint2(pack_bf16(dv0[0], dv0[1]), pack_bf16(dv0[2], dv0[3]));
-        *reinterpret_cast<uint2 *>(pv + 16) = make_uint2(pack_bf16(dv1[0], dv1[1]), pack_bf16(dv1[2], dv1[3]));
+        *reinterpret_cast<uint2 *>(pk) = pack_bf16x4(dk0);
+        *reinterpret_cast<uint2 *>(pk + 16) = pack_bf16x4(dk1);
+        *reinterpret_cast<uint2 *>(pv) = pack_bf16x4(dv0);
+        *reinterpret_cast<uint2 *>(pv + 16) = pack_bf16x4(dv1);
     }
 }
 
@@ -319,7 +310,7 @@ __global__ __launch_bounds__(kWaves * 64) void attn_bwd_q_kernel(
             const float pj = dead ? 0.f : exp2f(sv - lq);
             ds[j] = pj * (dp - dl) * scale;
         }
-        const bf16x8 dsb = pack8(ds);
+        const bf16x8 dsb = pack_bf16x8(ds);
         dq0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_k0, dsb, dq0, 0, 0, 0);
         dq1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_k1, dsb, dq1, 0, 0, 0);
     }
@@ -341,8 +332,8 @@ __global__ __launch_bounds__(kWaves * 64) void attn_bwd_q_kernel(
         }
     if (qi < nq) {
         uint16_t *pq = dq + tk.row(qi, b) * lddq + h * kHd + 4 * g;
-        *reinterpret_cast<uint2 *>(pq) = make_uint2(pack_bf16(dq0[0], dq0[1]), pack_bf16(dq0[2], dq0[3]));
-        *reinterpret_cast<uint2 *>(pq + 16) = make_uint2(pack_bf16(dq1[0], dq1[1]), pack_bf16(dq1[2], dq1[3]));
+        *reinterpret_cast<uint2 *>(pq) = pack_bf16x4(dq0);
+        *reinterpret_cast<uint2 *>(pq + 16) = pack_bf16x4(dq1);
     }
 }
 

@@ -56,11 +56,10 @@ __global__ void cls_pack_kernel(const float *__restrict__ G, int classes, const 
         } else {
             v = A[(long long)(row - 16 * ct) * kD + k];
         }
-        const unsigned hi = pack_bf16(v, 0.f) & 0xFFFFu;
-        const unsigned lo = pack_bf16(v - __uint_as_float(hi << 16), 0.f) & 0xFFFFu;
+        const Bf16Split parts = split_bf16(v);
         const long long base = (long long)t * kTileShorts + (long long)s * kFragShorts + lane * 8 + j;
-        packed[base] = (uint16_t)hi;
-        packed[base + 8 * kFragShorts] = (uint16_t)lo;
+        packed[base] = parts.hi;
+        packed[base + 8 * kFragShorts] = parts.lo;
     }
 }
 
@@ -76,55 +75,30 @@ void cls_score_kernel(const void *__restrict__ xv, const uint16_t *__restrict__ 
     const int c = lane & 15, q = lane >> 4;
     const int tok0 = blockIdx.x * kTokWg + wave * kTokWave;
     const int ct = (classes + 15) / 16, n_tiles = ct + kD / 16;
-    constexpr int kChunks = WPARTS * 8 * kFragShorts * 2 / 16 / (kWaves * 64);   // 16-byte chunks per thread and tile: 4 or 2
 
     // this wave's x fragments (B operand): lane (c, q) holds x[token c][32 s + 8 q + 0..7]
     bf16x8 xh[3][8], xl[XF32 ? 3 : 1][8];
+    if constexpr (XF32) {      // (row by row: a whole-wave loader like load_x_frags renumbers this kernel's registers)
 #pragma unroll
-    for (int t3 = 0; t3 < 3; ++t3) {
-        const int tok = min(tok0 + 16 * t3 + c, T - 1);
-        if (XF32) {
-            const float *row = static_cast<const float *>(xv) + (size_t)tok * kD + 8 * q;
+        for (int t3 = 0; t3 < 3; ++t3) {
+            const float *row = static_cast<const float *>(xv) + (size_t)min(tok0 + 16 * t3 + c, T - 1) * kD + 8 * q;
 #pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const float4 a = *reinterpret_cast<const float4 *>(row + 32 * s), b = *reinterpret_cast<const float4 *>(row + 32 * s + 4);
-                const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-                u32x4 h, l;
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    h[p] = pack_bf16(v[2 * p], v[2 * p + 1]);
-                    l[p] = pack_bf16(v[2 * p] - bf16_lo(h[p]), v[2 * p + 1] - bf16_hi(h[p]));
-                }
-                xh[t3][s] = __builtin_bit_cast(bf16x8, h);
-                xl[XF32 ? t3 : 0][s] = __builtin_bit_cast(bf16x8, l);
-            }
-        } else {
-            const uint16_t *row = static_cast<const uint16_t *>(xv) + (size_t)tok * kD + 8 * q;
-#pragma unroll
-            for (int s = 0; s < 8; ++s) xh[t3][s] = *reinterpret_cast<const bf16x8 *>(row + 32 * s);
+            for (int s = 0; s < 8; ++s) split_bf16x8(row + 32 * s, xh[t3][s], xl[t3][s]);
         }
+    } else {
+        load_x_frags(static_cast<const uint16_t *>(xv), tok0, T, c, q, xh);
     }
 
     float mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()}, nrm[3] = {0.f, 0.f, 0.f};
 
     // tile -> registers -> LDS, one tile ahead of the products
-    u32x4 stage[kChunks];
-    auto fetch = [&](int t) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(packed + (size_t)t * kTileShorts);
-#pragma unroll
-        for (int i = 0; i < kChunks; ++i) stage[i] = src[tid + i * (kWaves * 64)];
-    };
-    auto park = [&](int slot) {
-        u32x4 *dst = reinterpret_cast<u32x4 *>(wbuf[slot]);
-#pragma unroll
-        for (int i = 0; i < kChunks; ++i) dst[tid + i * (kWaves * 64)] = stage[i];
-    };
-    fetch(0);
-    park(0);
+    OperandStager<WPARTS * 8 * kFragShorts * 2 / 16 / (kWaves * 64), kWaves * 64> stage;   // 16-byte chunks per thread and tile: 4 or 2
+    stage.fetch(packed, tid);
+    stage.park(wbuf[0], tid);
     __syncthreads();
 
     for (int t = 0; t < n_tiles; ++t) {
-        if (t + 1 < n_tiles) fetch(t + 1);
+        if (t + 1 < n_tiles) stage.fetch(packed + (size_t)(t + 1) * kTileShorts, tid);
         const short *wt = wbuf[t & 1];
         f32x4 acc[3];
 #pragma unroll
@@ -158,30 +132,25 @@ void cls_score_kernel(const void *__restrict__ xv, const uint16_t *__restrict__ 
 #pragma unroll
             for (int t3 = 0; t3 < 3; ++t3) {
                 const int tok = min(tok0 + 16 * t3 + c, T - 1);
-                float xs[4];
-                if (XF32) {
+                f32x4 xs;
+                if (XF32) {      // (a float4, not an f32x4, load: the other changes this kernel's instructions)
                     const float4 v = *reinterpret_cast<const float4 *>(static_cast<const float *>(xv) + (size_t)tok * kD + ch0);
-                    xs[0] = v.x; xs[1] = v.y; xs[2] = v.z; xs[3] = v.w;
+                    xs = (f32x4){v.x, v.y, v.z, v.w};
                 } else {
-                    const uint2 v = *reinterpret_cast<const uint2 *>(static_cast<const uint16_t *>(xv) + (size_t)tok * kD + ch0);
-                    xs[0] = bf16_lo(v.x); xs[1] = bf16_hi(v.x); xs[2] = bf16_lo(v.y); xs[3] = bf16_hi(v.y);
+                    xs = unpack_bf16x4(*reinterpret_cast<const uint2 *>(static_cast<const uint16_t *>(xv) + (size_t)tok * kD + ch0));
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) nrm[t3] = fmaf(acc[t3][i], xs[i], nrm[t3]);
             }
         }
-        if (t + 1 < n_tiles) park((t + 1) & 1);
+        if (t + 1 < n_tiles) stage.park(wbuf[(t + 1) & 1], tid);
         __syncthreads();
     }
 
     // fold the four lane groups (rows 4 q + i live on lane group q), one store per token
 #pragma unroll
     for (int t3 = 0; t3 < 3; ++t3) {
-        float m = mx[t3], n2 = nrm[t3];
-        m = fmaxf(m, __shfl_xor(m, 16, 64));
-        m = fmaxf(m, __shfl_xor(m, 32, 64));
-        n2 += __shfl_xor(n2, 16, 64);
-        n2 += __shfl_xor(n2, 32, 64);
+        const float m = lane_groups_max(mx[t3]), n2 = lane_groups_sum(nrm[t3]);
         const int tok = tok0 + 16 * t3 + c;
         if (q == 0 && tok < T) scores[tok] = scale * m / sqrtf(n2);
     }

@@ -411,16 +411,13 @@ struct RingRequest {
         unsigned char *wdst = wring + (slot * WFR + wave * WPW) * 1024;
 #pragma unroll
         for (int i = 0; i < WPW; ++i)
-            __builtin_amdgcn_global_load_lds(wsrc[i], reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(wdst + i * 1024)),
-                                             16, 0, 0);
+            lds_dma16(wsrc[i], wdst + i * 1024);
         unsigned char *adst = aring + ((wave * R + slot) * AFR) * 1024;
 #pragma unroll
         for (int h = 0; h < KT; ++h)
 #pragma unroll
             for (int t3 = 0; t3 < PT; ++t3)
-                __builtin_amdgcn_global_load_lds(asrc[t3] ? asrc[t3] + 64 * cb + 8 * h : zero,
-                                                 reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(adst + (h * PT + t3) * 1024)),
-                                                 16, 0, 0);
+                lds_dma16(asrc[t3] ? asrc[t3] + 64 * cb + 8 * h : zero, adst + (h * PT + t3) * 1024);
         if (it + 1 < S) {      // (uniform) the next one; past the end the last one is repeated into a free slot
             ++it;
             if (++cb == cpb) {
@@ -513,7 +510,7 @@ void conv_ring_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict
     const unsigned wbase = (unsigned)(uintptr_t)wring + lane * 16, abase = (unsigned)(uintptr_t)aring + (wave * R * AFR) * 1024 + lane * 16;
     int slot = 0;
     for (int s = 0; s < S; ++s) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((R - 2) * NPI) : "memory");      // iteration s has landed (this wave's requests)
+        MFMA_VM_WAIT((R - 2) * NPI);                                               // iteration s has landed (this wave's requests)
         __builtin_amdgcn_s_barrier();                                              // ... everybody's; and slot (s - 1) % R is free
         rq.template request<R>(slot == 0 ? R - 1 : slot - 1, wave, S, cpb, x, g, img, hi0, wi0, q, wring, aring, zero);
         const unsigned wa = wbase + slot * (WFR * 1024), ba = abase + slot * (AFR * 1024);
@@ -523,7 +520,7 @@ void conv_ring_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict
         ring_products<0, CO_TILES, PT>(acc, fr, bfr, wa);
         slot = slot + 1 == R ? 0 : slot + 1;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the repeated requests of the last iterations)
+    MFMA_VM_WAIT(0);      // (the repeated requests of the last iterations)
     conv_epilogue<CO_TILES, PT>(acc, pout, q, co0, g.Cout, scale, shift, residual, relu, mask, out);
 }
 

@@ -242,9 +242,8 @@ struct WgradRing {      // a workgroup's request side: the two rows (of four con
             const uint16_t *pa = live ? acol[j] + (size_t)rp[j] * g.Cout : zero;
             const uint16_t *pb = in ? bcol[j] + ((size_t)(rn[j] * g.H + hi) * g.W + wi) * g.Cin : zero;
             unsigned char *dst = ring + slot * kRingSlotBytes + (8 * wave + 4 * j) * 256;
-            __builtin_amdgcn_global_load_lds(pa, reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(dst)), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(pb, reinterpret_cast<__attribute__((address_space(3))) void *>(reinterpret_cast<uintptr_t>(dst + kRingImage)), 16,
-                                             0, 0);
+            lds_dma16(pa, dst);
+            lds_dma16(pb, dst + kRingImage);
             rp[j] += kRingStagePx;
             rwo[j] += kRingStagePx;
             while (rwo[j] >= g.Wo) {
@@ -367,12 +366,12 @@ __device__ __forceinline__ void wgrad_block_ring(const uint16_t *__restrict__ dz
     const bool want_bias = BIAS && dbias != nullptr && tap == 0 && cib == 0 && wn == 0;
     int slot = 0;
     for (int st = 0; st < n_stage; ++st) {
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // this stage has landed (this wave's requests; two younger stages may be in flight)
+        MFMA_VM_WAIT(8);      // this stage has landed (this wave's requests; two younger stages may be in flight)
         __builtin_amdgcn_s_barrier();      // ... everybody's; and the slot of stage st - 1 is free
         wgrad_ring_products<BIAS>(acc, bacc, aa, ab, (unsigned)slot * kRingSlotBytes, want_bias, rq, (slot + kRingSlots - 1) % kRingSlots, g);      // (+ stage st + 3's requests)
         slot = (slot + 1) % kRingSlots;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the zero-line requests past the end)
+    MFMA_VM_WAIT(0);      // (the zero-line requests past the end)
 
     const int taps = g.KH * g.KW;
     float *out = dw + (size_t)bx * g.Cout * taps * g.Cin;

@@ -84,13 +84,7 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
 
     // this wave's x fragments (B operand of the first product): lane (c, q) holds x[token c][32 s + 8 q + 0..7]
     bf16x8 xf[3][8];
-#pragma unroll
-    for (int ct = 0; ct < 3; ++ct) {
-        const int tok = min(tok0 + 16 * ct + c, T - 1);
-        const uint16_t *row = x + (size_t)tok * kD + 8 * q;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) xf[ct][s] = *reinterpret_cast<const bf16x8 *>(row + 32 * s);
-    }
+    load_x_frags(x, tok0, T, c, q, xf);
 
     f32x4 acc[3][16];   // out^T: [token tile][16-channel row tile]; lane (c, q) holds channels 16 t + 4 q + 0..3 of token c
 #pragma unroll
@@ -108,13 +102,9 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
     auto stage_piece = [&](int ht, int slot, int i) {   // piece i of 8 (i < 4: W1, else W2)
         short *dst = wbuf + slot * (kTileFrags * kFragShorts);
         if (i < 4)   // i = 2 (s - 2 w) + rt
-            __builtin_amdgcn_global_load_lds(p1 + (size_t)ht * (kHT * kD) + (size_t)(i & 1) * 16 * kD + 32 * (i >> 1),
-                                             reinterpret_cast<__attribute__((address_space(3))) void *>(
-                                                 reinterpret_cast<uintptr_t>(dst + (4 * wave + i) * kFragShorts)), 16, 0, 0);
+            lds_dma16(p1 + (size_t)ht * (kHT * kD) + (size_t)(i & 1) * 16 * kD + 32 * (i >> 1), dst + (4 * wave + i) * kFragShorts);
         else
-            __builtin_amdgcn_global_load_lds(p2 + ht * kHT + (size_t)(i - 4) * 16 * F,
-                                             reinterpret_cast<__attribute__((address_space(3))) void *>(
-                                                 reinterpret_cast<uintptr_t>(dst + (16 + 4 * wave + (i - 4)) * kFragShorts)), 16, 0, 0);
+            lds_dma16(p2 + ht * kHT + (size_t)(i - 4) * 16 * F, dst + (16 + 4 * wave + (i - 4)) * kFragShorts);
     };
     auto stage = [&](int ht, int slot) {
 #pragma unroll
@@ -137,8 +127,8 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
     int slot = 0;
     for (int ht = 0; ht < nt; ++ht) {
         // tile ht has landed: at most the 8 DMAs of tile ht + 1 may still be in flight
-        if (ht + 1 < nt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (ht + 1 < nt) MFMA_VM_WAIT(8);
+        else MFMA_VM_WAIT(0);
         FFN_STAMP(0)   // wait for the tile's DMAs
         __builtin_amdgcn_s_barrier();   // ... everybody's share of it; and everybody is done with tile ht - 1, whose slot is refilled now
         FFN_STAMP(1)   // barrier
@@ -217,6 +207,7 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
         // vector instruction 11 wait states later)
         asm volatile("s_nop 7\n\ts_nop 7" : "+v"(hacc[0][0]), "+v"(hacc[0][1]), "+v"(hacc[1][0]), "+v"(hacc[1][1]), "+v"(hacc[2][0]), "+v"(hacc[2][1]));
         // ---- relu, to bf16: elements 0..3 = rows 4 q + 0..3 of row tile 0, elements 4..7 = the same rows of row tile 1 ------------
+        // (not pack_bf16x8: it changes this kernel's instructions)
 #pragma unroll
         for (int ct = 0; ct < 3; ++ct) {
             u32x4 u;
@@ -273,15 +264,14 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
             const int ch = 16 * t + 4 * q;   // channels ch .. ch + 3 <-> the four registers of row tile t
             const uint2 xr = *reinterpret_cast<const uint2 *>(xrow + ch);
             const f32x4 bb = *reinterpret_cast<const f32x4 *>(lb2 + ch);
-            const float xv[4] = {bf16_lo(xr.x), bf16_hi(xr.x), bf16_lo(xr.y), bf16_hi(xr.y)};
+            const f32x4 xv = unpack_bf16x4(xr);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 acc[ct][t][i] += bb[i] + xv[i];
                 sum += acc[ct][t][i];
             }
         }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
+        sum = lane_groups_sum(sum);
         const float mean = sum * (1.f / kD);
         float var = 0.f;
 #pragma unroll
@@ -291,8 +281,7 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
                 const float d = acc[ct][t][i] - mean;
                 var += d * d;
             }
-        var += __shfl_xor(var, 16, 64);
-        var += __shfl_xor(var, 32, 64);
+        var = lane_groups_sum(var);
         const float rstd = rsqrtf(var * (1.f / kD) + eps);
         if (rstd_out && live && q == 0) rstd_out[tok] = rstd;      // for the backward (msda_ffn_ln_backward_bf16)
         if (live) {
@@ -301,22 +290,15 @@ void ffn_fwd_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__
             for (int t = 0; t < 16; ++t) {
                 const int ch = 16 * t + 4 * q;
                 const f32x4 ga = *reinterpret_cast<const f32x4 *>(lgam + ch), be = *reinterpret_cast<const f32x4 *>(lbet + ch);
-                float y[4], yh[4];
+                f32x4 y, yh;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     yh[i] = (acc[ct][t][i] - mean) * rstd;
                     y[i] = yh[i] * ga[i] + be[i];
                 }
-                uint2 o;
-                o.x = pack_bf16(y[0], y[1]);
-                o.y = pack_bf16(y[2], y[3]);
-                *reinterpret_cast<uint2 *>(orow + ch) = o;
-                if (yhat_out) {      // training: the normalised pre-affine value, for the LayerNorm's backward
-                    uint2 h;
-                    h.x = pack_bf16(yh[0], yh[1]);
-                    h.y = pack_bf16(yh[2], yh[3]);
-                    *reinterpret_cast<uint2 *>(yhat_out + (size_t)tok * kD + ch) = h;
-                }
+                *reinterpret_cast<uint2 *>(orow + ch) = pack_bf16x4(y);
+                // training: the normalised pre-affine value, for the LayerNorm's backward
+                if (yhat_out) *reinterpret_cast<uint2 *>(yhat_out + (size_t)tok * kD + ch) = pack_bf16x4(yh);
             }
         }
     }
@@ -342,6 +324,7 @@ __global__ __launch_bounds__(256) void ffn_ln_backward_kernel(const uint16_t *__
     const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + ch);
     float s_g[4] = {0.f, 0.f, 0.f, 0.f}, s_b[4] = {0.f, 0.f, 0.f, 0.f}, s_z[4] = {0.f, 0.f, 0.f, 0.f};
     for (int tok = blockIdx.x * 4 + wave; tok < T; tok += gridDim.x * 4) {
+        // (not unpack_bf16x4: it changes this kernel's instructions)
         const uint2 d = *reinterpret_cast<const uint2 *>(dy + (size_t)tok * kD + ch), o = *reinterpret_cast<const uint2 *>(yhat + (size_t)tok * kD + ch);
         const float dv[4] = {bf16_lo(d.x), bf16_hi(d.x), bf16_lo(d.y), bf16_hi(d.y)};
         const float ov[4] = {bf16_lo(o.x), bf16_hi(o.x), bf16_lo(o.y), bf16_hi(o.y)};
@@ -354,12 +337,12 @@ __global__ __launch_bounds__(256) void ffn_ln_backward_kernel(const uint16_t *__
             b += g[i] * yh[i];
         }
 #pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
+        for (int m = 1; m < 64; m <<= 1) {      // (the 64-lane sums stay written out here and below: see mfma_common.h)
             a += __shfl_xor(a, m, 64);
             b += __shfl_xor(b, m, 64);
         }
         const float r = rstd[tok], ma = a * (1.f / kD), mb = b * (1.f / kD);
-        float z[4];
+        f32x4 z;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             z[i] = r * (g[i] - ma - yh[i] * mb);
@@ -367,10 +350,7 @@ __global__ __launch_bounds__(256) void ffn_ln_backward_kernel(const uint16_t *__
             s_b[i] += dv[i];
             s_z[i] += z[i];
         }
-        uint2 zo;
-        zo.x = pack_bf16(z[0], z[1]);
-        zo.y = pack_bf16(z[2], z[3]);
-        *reinterpret_cast<uint2 *>(dz + (size_t)tok * kD + ch) = zo;
+        *reinterpret_cast<uint2 *>(dz + (size_t)tok * kD + ch) = pack_bf16x4(z);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -399,12 +379,8 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__re
     const int ch = 4 * lane;
     const f32x4 ga = *reinterpret_cast<const f32x4 *>(gamma + ch), be = *reinterpret_cast<const f32x4 *>(beta + ch);
     for (int tok = blockIdx.x * 4 + wave; tok < T; tok += gridDim.x * 4) {
-        const uint2 ua = *reinterpret_cast<const uint2 *>(a + (size_t)tok * kD + ch);
-        float v[4] = {bf16_lo(ua.x), bf16_hi(ua.x), bf16_lo(ua.y), bf16_hi(ua.y)};
-        if (b) {
-            const uint2 ub = *reinterpret_cast<const uint2 *>(b + (size_t)tok * kD + ch);
-            v[0] += bf16_lo(ub.x); v[1] += bf16_hi(ub.x); v[2] += bf16_lo(ub.y); v[3] += bf16_hi(ub.y);
-        }
+        f32x4 v = unpack_bf16x4(*reinterpret_cast<const uint2 *>(a + (size_t)tok * kD + ch));
+        if (b) v += unpack_bf16x4(*reinterpret_cast<const uint2 *>(b + (size_t)tok * kD + ch));
         float s = v[0] + v[1] + v[2] + v[3];
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);
@@ -418,22 +394,14 @@ __global__ __launch_bounds__(256) void add_layernorm_kernel(const uint16_t *__re
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) q += __shfl_xor(q, m, 64);
         const float r = rsqrtf(q * (1.f / kD) + eps);
-        float yh[4], y[4];
+        f32x4 yh, y;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             yh[i] = v[i] * r;
             y[i] = yh[i] * ga[i] + be[i];
         }
-        uint2 o;
-        o.x = pack_bf16(y[0], y[1]);
-        o.y = pack_bf16(y[2], y[3]);
-        *reinterpret_cast<uint2 *>(out + (size_t)tok * kD + ch) = o;
-        if (yhat_out) {
-            uint2 h;
-            h.x = pack_bf16(yh[0], yh[1]);
-            h.y = pack_bf16(yh[2], yh[3]);
-            *reinterpret_cast<uint2 *>(yhat_out + (size_t)tok * kD + ch) = h;
-        }
+        *reinterpret_cast<uint2 *>(out + (size_t)tok * kD + ch) = pack_bf16x4(y);
+        if (yhat_out) *reinterpret_cast<uint2 *>(yhat_out + (size_t)tok * kD + ch) = pack_bf16x4(yh);
         if (rstd_out && lane == 0) rstd_out[tok] = r;
     }
 }

@@ -55,34 +55,17 @@ void lin256_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ 
     const int b_lo = (int)((long long)nb_all * blockIdx.y / gridDim.y), b_hi = (int)((long long)nb_all * (blockIdx.y + 1) / gridDim.y);
 
     bf16x8 xf[3][8];
-#pragma unroll
-    for (int t3 = 0; t3 < 3; ++t3) {
-        const int tok = min(tok0 + 16 * t3 + c, T - 1);
-        const uint16_t *row = x + (size_t)tok * kD + 8 * q;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) xf[t3][s] = *reinterpret_cast<const bf16x8 *>(row + 32 * s);
-    }
+    load_x_frags(x, tok0, T, c, q, xf);
 
-    constexpr int kChunks = kBlockShorts * 2 / 16 / (kWaves * 64);      // 8 x 16 bytes per thread and block
-    u32x4 stage[kChunks];
-    auto fetch = [&](int b) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(packed + (size_t)b * kBlockShorts);
-#pragma unroll
-        for (int i = 0; i < kChunks; ++i) stage[i] = src[tid + i * (kWaves * 64)];
-    };
-    auto park = [&](int slot) {
-        u32x4 *dst = reinterpret_cast<u32x4 *>(wbuf[slot]);
-#pragma unroll
-        for (int i = 0; i < kChunks; ++i) dst[tid + i * (kWaves * 64)] = stage[i];
-    };
+    OperandStager<kBlockShorts * 2 / 16 / (kWaves * 64), kWaves * 64> stage;      // 8 x 16 bytes per thread and block
     if (b_lo < b_hi) {
-        fetch(b_lo);
-        park(b_lo & 1);
+        stage.fetch(packed + (size_t)b_lo * kBlockShorts, tid);
+        stage.park(wbuf[b_lo & 1], tid);
     }
     __syncthreads();
 
     for (int b = b_lo; b < b_hi; ++b) {
-        if (b + 1 < b_hi) fetch(b + 1);
+        if (b + 1 < b_hi) stage.fetch(packed + (size_t)(b + 1) * kBlockShorts, tid);
         // the mask rows of this block, requested before the products that hide their latency
         u32x4 mreg[EPI == 2 ? 3 : 1][2];
         if (EPI == 2) {
@@ -152,7 +135,7 @@ void lin256_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ 
             op[0] = (u32x4){pack_bf16(y[0], y[1]), pack_bf16(y[2], y[3]), pack_bf16(y[4], y[5]), pack_bf16(y[6], y[7])};
             op[1] = (u32x4){pack_bf16(y[8], y[9]), pack_bf16(y[10], y[11]), pack_bf16(y[12], y[13]), pack_bf16(y[14], y[15])};
         }
-        if (b + 1 < b_hi) park((b + 1) & 1);
+        if (b + 1 < b_hi) stage.park(wbuf[(b + 1) & 1], tid);
         __syncthreads();
     }
 }
@@ -171,12 +154,10 @@ __global__ void lin256_pack_f32_kernel(const float *__restrict__ w, uint16_t *__
         const int j = (int)(i & 7), lane = (int)((i >> 3) & 63), u = (int)((i >> 9) & 1), s = (int)((i >> 10) & 7), blk = (int)(i >> 13);
         const int r = lane & 15, q = lane >> 4;
         const int ch = kF32BlockRows * blk + 8 * (r >> 2) + 4 * u + (r & 3), k = 32 * s + 8 * q + j;
-        const float v = w[(long long)ch * kD + k];
-        const unsigned hi = pack_bf16(v, 0.f) & 0xFFFFu;
-        const unsigned lo = pack_bf16(v - __uint_as_float(hi << 16), 0.f) & 0xFFFFu;
+        const Bf16Split v = split_bf16(w[(long long)ch * kD + k]);
         const long long base = (long long)blk * kF32BlockShorts + ((long long)(s * 2 + u) * 64 + lane) * 8 + j;
-        packed[base] = (uint16_t)hi;
-        packed[base + 8 * 2 * kFragShorts] = (uint16_t)lo;
+        packed[base] = v.hi;
+        packed[base + 8 * 2 * kFragShorts] = v.lo;
     }
 }
 
@@ -195,43 +176,20 @@ void lin256_f32_kernel(const float *__restrict__ x, const uint16_t *__restrict__
     bf16x8 xh[3][8], xl[3][8];
 #pragma unroll
     for (int t3 = 0; t3 < 3; ++t3) {
-        const int tok = min(tok0 + 16 * t3 + c, T - 1);
-        const float *row = x + (size_t)tok * kD + 8 * q;
+        const float *row = x + (size_t)min(tok0 + 16 * t3 + c, T - 1) * kD + 8 * q;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const float4 a = *reinterpret_cast<const float4 *>(row + 32 * s), b = *reinterpret_cast<const float4 *>(row + 32 * s + 4);
-            const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-            u32x4 h, l;
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                h[p] = pack_bf16(v[2 * p], v[2 * p + 1]);
-                l[p] = pack_bf16(v[2 * p] - bf16_lo(h[p]), v[2 * p + 1] - bf16_hi(h[p]));
-            }
-            xh[t3][s] = __builtin_bit_cast(bf16x8, h);
-            xl[t3][s] = __builtin_bit_cast(bf16x8, l);
-        }
+        for (int s = 0; s < 8; ++s) split_bf16x8(row + 32 * s, xh[t3][s], xl[t3][s]);
     }
 
-    constexpr int kChunks = kF32BlockShorts * 2 / 16 / (kWaves * 64);      // 8
-    u32x4 stage[kChunks];
-    auto fetch = [&](int b) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(packed + (size_t)b * kF32BlockShorts);
-#pragma unroll
-        for (int i = 0; i < kChunks; ++i) stage[i] = src[tid + i * (kWaves * 64)];
-    };
-    auto park = [&](int slot) {
-        u32x4 *dst = reinterpret_cast<u32x4 *>(wbuf[slot]);
-#pragma unroll
-        for (int i = 0; i < kChunks; ++i) dst[tid + i * (kWaves * 64)] = stage[i];
-    };
+    OperandStager<kF32BlockShorts * 2 / 16 / (kWaves * 64), kWaves * 64> stage;      // 8 x 16 bytes per thread and block
     if (b_lo < b_hi) {
-        fetch(b_lo);
-        park(b_lo & 1);
+        stage.fetch(packed + (size_t)b_lo * kF32BlockShorts, tid);
+        stage.park(wbuf[b_lo & 1], tid);
     }
     __syncthreads();
 
     for (int b = b_lo; b < b_hi; ++b) {
-        if (b + 1 < b_hi) fetch(b + 1);
+        if (b + 1 < b_hi) stage.fetch(packed + (size_t)(b + 1) * kF32BlockShorts, tid);
         const short *wt = wbuf[b & 1];
         f32x4 acc[3][2];
 #pragma unroll
@@ -266,7 +224,7 @@ void lin256_f32_kernel(const float *__restrict__ x, const uint16_t *__restrict__
             op[0] = acc[t3][0] + b0;
             op[1] = acc[t3][1] + b1;
         }
-        if (b + 1 < b_hi) park((b + 1) & 1);
+        if (b + 1 < b_hi) stage.park(wbuf[(b + 1) & 1], tid);
         __syncthreads();
     }
 }

@@ -108,15 +108,6 @@ inline BandPlan plan_band(int N, int S, int M, int D, int L, int Lq, int P, cons
 
 inline int band_grid(const BandGeom &g) { return kXcds * ((g.N * g.M + kXcds - 1) / kXcds) * g.nent; }
 
-// sum over the 8 lanes of a lane group (DPP only: two quad permutes, one mirror inside the half-row)
-__device__ __forceinline__ float band_group_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    return v;
-}
-
 // TV: storage type of value / grad_out / grad_value (float, or bf16_t with fp32 arithmetic).  grad_acc: where the slabbed levels are
 // accumulated with fp32 row atomics -- grad_value itself for TV = float, an fp32 image of it for bf16 (rounded by band_round_kernel).
 // Work decomposition of scan and reduce: an ITEM is (query, chunk of four points of this level) -- RichSem's P = 4: one item per query --;
@@ -303,7 +294,7 @@ __global__ __launch_bounds__(kBandThreads, 4) void bwd_band_kernel(const TV *__r
                         float d[4];
 #pragma unroll
                         for (int k = 0; k < 4; ++k)
-                            d[k] = band_group_sum(go.x * v[u][k].x + go.y * v[u][k].y + go.z * v[u][k].z + go.w * v[u][k].w);
+                            d[k] = group8_sum(go.x * v[u][k].x + go.y * v[u][k].y + go.z * v[u][k].z + go.w * v[u][k].w);
                         if (j == 0) {
                             const unsigned pt = pt0 + (unsigned)p;
                             grad_aw[pt] = hh * hwt * d[0] + hh * lw[u] * d[1] + lh[u] * hwt * d[2] + lh[u] * lw[u] * d[3];

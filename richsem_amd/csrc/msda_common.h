@@ -110,6 +110,37 @@ __device__ __forceinline__ bool decode_block(int bid, int pairs, int ntiles, int
     return pair < pairs;
 }
 
+// ---- lane movement that stays in the vector pipe (DPP: no LDS crossbar, no barrier) ----
+// lane l receives the value of the lane that the DPP control CTRL names for it, inside l's row of 16 lanes
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v)
+{
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
+}
+constexpr int kDppXor1 = 0xB1;        // quad_perm [1,0,3,2]: lane ^ 1
+constexpr int kDppXor2 = 0x4E;        // quad_perm [2,3,0,1]: lane ^ 2
+constexpr int kDppHalfMirror = 0x141; // row_half_mirror: lane 7 - l of the half-row
+
+// sum / maximum over the 4 lanes of a quad, sum over the 8 lanes of a half-row (a query's channel lanes)
+__device__ __forceinline__ float quad_sum(float v)
+{
+    v += dpp_f<kDppXor1>(v);
+    return v + dpp_f<kDppXor2>(v);
+}
+__device__ __forceinline__ float quad_max(float v)
+{
+    v = fmaxf(v, dpp_f<kDppXor1>(v));
+    return fmaxf(v, dpp_f<kDppXor2>(v));
+}
+__device__ __forceinline__ float group8_sum(float v)
+{
+    v = quad_sum(v);
+    return v + dpp_f<kDppHalfMirror>(v);
+}
+
+// a value that is the same in every lane, moved to a scalar register
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
 template <typename T>
 __device__ __forceinline__ T shfl_xor_t(T v, int mask)
 {

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(kDirectThreads, 4) void fwd_split_kernel(
     // the four point groups of an item: lanes 8 and 16 apart
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-        acc[c] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc[c]), 0x128, 0xF, 0xF, true));      // row_ror:8 = lane ^ 8 inside a row of 16
+        acc[c] += dpp_f<0x128>(acc[c]);      // row_ror:8 = lane ^ 8 inside a row of 16
         acc[c] += __shfl_xor(acc[c], 16, kWave);
     }
     if (live && pg == 0) {
@@ -358,15 +358,7 @@ __global__ __launch_bounds__(kDirectThreads, OCC) void fwd_direct_prep_kernel(
 // every level), D = 32, fp32 compute: the backward twin of fwd_split_kernel.  bwd_direct_kernel walks an item's L*P points one after the
 // other -- gathers, then three shuffle reductions, per point: sixteen rounds of memory latency per wave, 33 us at 1092 queries.  Here a
 // lane has its L*P/4 points' sixteen corner gathers in flight at once and the three sums of a point meet over the item's 8 channel lanes
-// in three DPP steps (no LDS crossbar).
-__device__ __forceinline__ float direct_group8_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    return v;
-}
-
+// in three DPP steps (group8_sum).
 template <typename TV, int PPG>
 __global__ __launch_bounds__(kDirectThreads, 4) void bwd_split_kernel(
     const TV *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
@@ -420,9 +412,9 @@ __global__ __launch_bounds__(kDirectThreads, 4) void bwd_split_kernel(
             s_h += (hw * (v[2][c] - v[0][c]) + lw * (v[3][c] - v[1][c])) * tgv;
         }
         // (with the point count known the three sums are kept and stored behind the loop: no store sits between the points' gathers)
-        r_a[i] = direct_group8_sum(s_a);
-        r_w[i] = (float)G_.W * direct_group8_sum(s_w);
-        r_h[i] = (float)G_.H * direct_group8_sum(s_h);
+        r_a[i] = group8_sum(s_a);
+        r_w[i] = (float)G_.W * group8_sum(s_w);
+        r_h[i] = (float)G_.H * group8_sum(s_h);
         if (!PPG && live && j == 0) {
             grad_aw[item * LP + gp] = r_a[i];
             Pack<float, 2> gl;

@@ -133,16 +133,6 @@ struct RpsLds {
 };
 static_assert(sizeof(RpsLds) <= 160 * 1024, "rps: LDS budget");
 
-__device__ __forceinline__ float rps_group8_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xF, 0xF, true));   // row_half_mirror
-    return v;
-}
-
-__device__ __forceinline__ int rps_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
 // Inclusive prefix sum over the 64 lanes of a wave in six DPP adds (shifts inside a row of 16, then the rows' last lanes broadcast to the
 // rows behind them): the shuffle form goes through the LDS crossbar six times (ds_bpermute), this one stays in the vector pipe.
 __device__ __forceinline__ int rps_wave_scan(int v)
@@ -369,7 +359,7 @@ __global__ __launch_bounds__(kRpsRouteThreads, 4) void rps_route_kernel(const fl
             if (l >= L) continue;   // (uniform)
             const RpsLevel &v = g.lv[l];
             const int ns = v.nslab;
-            const int slab = ns > 1 ? rps_uni(qb % ns) : 0;
+            const int slab = ns > 1 ? uni(qb % ns) : 0;
             ob[l] = (valid_m >> l & 1u) ? v.bin0 + slab + (int)(re[l] >> 8) + (int)((ce[l] >> 8) & 511u) : -1;
             const unsigned inr = (re[l] >> 6) & 3u, inc = (ce[l] >> 6) & 3u;
             inmap[l] = ((inr & 1u) ? inc : 0u) | ((inr & 2u) ? inc << 2 : 0u);      // bit 0 TL, 1 TR, 2 BL, 3 BR inside the map
@@ -487,9 +477,9 @@ typedef float rps_v4f __attribute__((ext_vector_type(4)));
 // vector instructions once the rest had shrunk).  The caller arranges the rotation where it is free: which value row a register holds.
 __device__ __forceinline__ float rps_quad_rotated_sum(float x0, float x1, float x2, float x3)
 {
-    const float ra = x0 + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x1), 0xB1, 0xF, 0xF, true));   // lane ^ 1: its x1 is corner j
-    const float rb = x2 + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x3), 0xB1, 0xF, 0xF, true));   //           its x3 is corner j ^ 2
-    return ra + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(rb), 0x4E, 0xF, 0xF, true));             // lane ^ 2: its rb is corner j
+    const float ra = x0 + dpp_f<kDppXor1>(x1);   // lane ^ 1: its x1 is corner j
+    const float rb = x2 + dpp_f<kDppXor1>(x3);   //           its x3 is corner j ^ 2
+    return ra + dpp_f<kDppXor2>(rb);   // lane ^ 2: its rb is corner j
 }
 
 // A lane's 8 channels of a grad_out row as they travel from memory: fp32 as two float4, bf16 as two packed 8-byte words that are
@@ -581,7 +571,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
     };
     auto item_geom = [&](int id) {
         Item it;
-        const unsigned unit = (unsigned)rps_uni((int)g.units[min(id, n_items - 1) / g.ppx]);
+        const unsigned unit = (unsigned)uni((int)g.units[min(id, n_items - 1) / g.ppx]);
         const int pr = xq + kXcds * (min(id, n_items - 1) % g.ppx);
         const int pair = min(pr, pairs - 1);
         it.live = id < n_items && pr < pairs;
@@ -641,8 +631,8 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
     // a bin's run table: global -> registers (one run per lane) -> LDS
     uint2 run_reg = make_uint2(0u, 0u);
     auto load_runs = [&](unsigned bin_, int nr) {
-        const int i = min(tid, max(rps_uni(nr) - 1, 0));
-        const unsigned b_ = (unsigned)rps_uni((int)bin_);
+        const int i = min(tid, max(uni(nr) - 1, 0));
+        const unsigned b_ = (unsigned)uni((int)bin_);
         run_reg = g.runs[(size_t)(b_ == 0xFFFFFFFFu ? 0u : b_) * g.max_runs + i];
     };
     auto park_runs = [&]() {
@@ -655,7 +645,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
     // lane reads ONE sample of the table (every T-th run), two ballots bracket the wave's first and last record between samples, and a lane
     // finishes inside that bracket -- a few runs -- with a short search of its own: 3-5 dependent reads instead of 10.
     auto fetch_recs = [&](int n_, int nr_, int ch) {      // (the bin's run table is in LDS)
-        const int n = rps_uni(n_), nr = rps_uni(nr_);
+        const int n = uni(n_), nr = uni(nr_);
         const int T = max((nr + kWave - 1) / kWave, 1);      // sample stride (nr <= kRpsMaxRuns: T <= 5)
         const bool s_ok = lane * T < nr;
         const unsigned sy = S->runs[min(lane * T, max(nr - 1, 0))].y;
@@ -711,13 +701,13 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
     if (tid == 0) S->item_slot[0] = (int)draw;
     draw = atomicAdd(draw_at, draw_by);
     __syncthreads();
-    int item_id = rps_uni(S->item_slot[0]);
+    int item_id = uni(S->item_slot[0]);
     unsigned e_bin;
     int n_ent, n_runs;
     bin_range(item_id, e_bin, n_ent, n_runs);
-    e_bin = (unsigned)rps_uni((int)e_bin);
-    n_ent = rps_uni(n_ent);
-    n_runs = rps_uni(n_runs);
+    e_bin = (unsigned)uni((int)e_bin);
+    n_ent = uni(n_ent);
+    n_runs = uni(n_runs);
     load_runs(e_bin, n_runs);
     park_runs();
     __syncthreads();
@@ -737,7 +727,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
         // (the item's value rows were requested before the previous item's sums were stored -- before the loop for the first item;
         // the f64 sums are zero: cleared before the loop, and by the lanes that read them out at the end of every item)
         __syncthreads();
-        const int next_id = rps_uni(S->item_slot[par ^ 1]);
+        const int next_id = uni(S->item_slot[par ^ 1]);
         unsigned next_bin, next_ok;
         unsigned long long next_st;
         int next_n = 0, next_runs = 0;
@@ -851,7 +841,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
 
             // ---- (4) the waves take groups of 16 units in turn; a quad walks its unit: four partial sums and four corner dots per
             //      point, grad_out rows straight from global memory, software-pipelined; then the sums go to the tile's f64 sums ----
-            const int n_segs = rps_uni(S->n_segs);
+            const int n_segs = uni(S->n_segs);
             for (int u0 = wave * 16; u0 < n_segs; u0 += kRpsWaves * 16) {   // (uniform)
                 unsigned long long wt0 = 0, wt1 = 0, wt2 = 0;      // (diagnostic: wave 0's time in a group's set-up / point loop / epilogue)
                 if (kStamps && g.stamps && tid == 0) wt0 = __builtin_amdgcn_s_memtime();
@@ -1095,9 +1085,9 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
         __syncthreads();
         RPS_STAMP(7)
         item_id = next_id;
-        e_bin = (unsigned)rps_uni((int)next_bin);
-        n_ent = rps_uni(next_n);
-        n_runs = rps_uni(next_runs);
+        e_bin = (unsigned)uni((int)next_bin);
+        n_ent = uni(next_n);
+        n_runs = uni(next_runs);
         it = nit;
         par ^= 1;
     }

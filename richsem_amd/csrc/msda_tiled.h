@@ -255,8 +255,6 @@ inline TiledPlan plan_tiled(int N, int S, int M, int D, int L, int Lq, int P, co
 }
 
 // ---- device helpers -------------------------------------------------------------------------------------
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
 // Diagnostic only (g.stamps is null in normal runs): slot i of this workgroup's stamp row <- shader clock.
 __device__ __forceinline__ void stamp(const TiledGeom &g, int i)
 {
@@ -365,14 +363,6 @@ struct LevelCtx {
 // DPP broadcast.
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-// Sum over the 4 lanes of a query (one quad) with DPP only: no LDS crossbar, no barrier.
-__device__ __forceinline__ float quad_sum(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true));   // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true));   // quad_perm [2,3,0,1]
-    return v;
-}
-
 // The four corner rows of an IN-WINDOW sampling point for this lane's 4*NV channels: straight-line LDS reads.
 template <int GC, int NV>
 __device__ __forceinline__ void lds_corners(const float *win, int nwc, int j, int mode, float4 (&v)[4][NV])
@@ -446,12 +436,6 @@ struct TiledPrepSrc {
     int ref_dim;                       // 2: reference points (x, y); 4: reference boxes (x, y, w, h)
     float *loc_out, *aw_out;           // by-products, or null
 };
-
-__device__ __forceinline__ float quad_max(float v)
-{
-    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true)));
-    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xF, 0xF, true)));
-}
 
 template <typename TP>
 __device__ __forceinline__ float tp_ld(const TP *p);
