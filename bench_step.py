@@ -29,6 +29,7 @@ from richsem_amd.backbone import InputProjection, ResNet50
 from richsem_amd.capture import quiet_gc
 from richsem_amd.clip_resnet import ModifiedResNetTeacher
 from richsem_amd.dn import prepare_dn_layout
+from richsem_amd.distill import DistillKL
 from richsem_amd.fed_loss import FedClassSampler, MaskedFocalNegativeSum, class_weights_from_image_counts
 from richsem_amd.functions.linear import Lin256Function, VersionCache, pack_linear256
 from richsem_amd.matcher import (BoxPairLoss, CostPlan, FocalNegativeSum, FocalPositiveSum, HungarianMatcher, LateStatus,
@@ -102,7 +103,7 @@ class Step(nn.Module):
     """the rows with their (synthetic) parameters; ``forward`` = model forward + criterion, returns the loss and section times"""
 
     def __init__(self, n_img=2, height=800, width=1333, boxes_per_image=12, seed=0, dev="cuda", fed_loss=False, fed_num_sample_cats=50,
-                 class_image_counts=None, device_matcher=False, keep_match_outputs=False):
+                 class_image_counts=None, device_matcher=False, keep_match_outputs=False, device_distill=False):
         super().__init__()
         torch.manual_seed(seed)
         self.n_img, self.H, self.Wimg, self.K = n_img, height, width, boxes_per_image
@@ -150,6 +151,8 @@ class Step(nn.Module):
             counts = synthetic_image_counts(NUM_CLASSES) if class_image_counts is None else class_image_counts
             self.fed_sampler = FedClassSampler(fed_num_sample_cats, class_weights_from_image_counts(counts, NUM_CLASSES))
         self.last_fed_mask = None
+        # the distillation term as one row kernel (richsem_amd/distill.py) instead of gathers + softmaxes + kl_div: opt-in, see loss_part
+        self.device_distill = bool(device_distill)
         # the Hungarian assignment on the device (msda_lsap_*, richsem_amd/matcher.py) instead of scipy on the host: opt-in.  The step then
         # has no host wait between its first and last kernel and captures whole (run_graphed(device_matcher=True)); the solver's status is
         # read one step late (matcher.LateStatus), the way AsyncLossLog reads the losses
@@ -441,7 +444,9 @@ class Step(nn.Module):
         fed_num_sample_cats by weighted draws without replacement, drawn afresh every step on the device (fed_loss.FedClassSampler, no host
         sync: the draw is captured and replayed with the rest) -- or the masks of ``freeze_fed``.  The all-negative term then runs
         with a class mask per row (fed_loss.MaskedFocalNegativeSum); the positive entries are appeared classes, always in the mask.
-        The last masks are kept as ``last_fed_mask`` (13, C).  Tensors in, the loss out."""
+        The last masks are kept as ``last_fed_mask`` (13, C).  With ``device_distill`` the KL term is one ``distill.DistillKL`` call on the same
+        rows (value and gradient rows from one kernel, the gather inside it) instead of two gathers, two softmaxes and ``kl_div``.
+        Tensors in, the loss out."""
         st = self.static
         dev = logits.device
         lay = st["lay"]
@@ -492,6 +497,12 @@ class Step(nn.Module):
         loss = loss + BoxPairLoss.apply(pb, tb, w_pair, 5.0, 2.0)
         # ---- distillation: KL of the matched queries' CLIP logits against the teacher's box logits (richsem.py:1255-1300) -------------------
         _, bi, si, tj = m_dis
+        if self.device_distill:      # the same rows, each with the weight 0.5 / K ("batchmean" over K rows), gathered inside one kernel
+            K = bi.numel()
+            w_dis = cst.get("w_dis")
+            if w_dis is None or w_dis.numel() != K:
+                w_dis = cst["w_dis"] = torch.full((K,), 0.5 / max(K, 1), dtype=torch.float32, device=dev)
+            return loss + DistillKL.apply(clip_logits, t_logits, bi * clip_logits.shape[1] + si + pad, tj, w_dis, None, None, False)
         loss = loss + 0.5 * F.kl_div(F.log_softmax(clip_logits[bi, si + pad], -1), F.softmax(t_logits[tj], -1), reduction="batchmean")
         return loss
 
@@ -654,7 +665,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
     try:
         del model
         torch.cuda.empty_cache()
-        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image")}
+        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill")}
         out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
@@ -969,12 +980,15 @@ if __name__ == "__main__":
     ap.add_argument("--fed-loss", action="store_true", help="the criterion's federated loss (use_fed_loss, 50 classes per draw; synthetic class "
                                                            "weights: Step.loss_part)")
     ap.add_argument("--boxes-per-image", type=int, default=12, help="targets per synthetic image (default 12)")
+    ap.add_argument("--device-distill", action="store_true", help="the criterion's KL distillation term as one row kernel (distill.DistillKL) "
+                                                                   "instead of the PyTorch composition: Step.loss_part")
     ap.add_argument("--device-matcher", action="store_true", help="time the graphed training step in both forms: the Hungarian assignment on the "
                                                                   "host between two captured parts (twice, to show its spread) and on the device "
                                                                   "inside one captured step")
     a_ = ap.parse_args()
     if a_.device_matcher:
-        kw = dict(steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}))
+        kw = dict(steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
+                  **({"device_distill": True} if a_.device_distill else {}))
         res = {"boxes_per_image": a_.boxes_per_image}
         for name, dm in (("host_matcher", False), ("host_matcher_again", False), ("device_matcher", True)):
             r = run_graphed(a_.images, torch.device("cuda", 0), device_matcher=dm, **kw)
@@ -984,5 +998,6 @@ if __name__ == "__main__":
         print(json.dumps(res, indent=1))
         sys.exit(0)
     print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at,
-                         **({"fed_loss": True} if a_.fed_loss else {}), **({"boxes_per_image": a_.boxes_per_image} if a_.boxes_per_image != 12 else {})),
+                         **({"fed_loss": True} if a_.fed_loss else {}), **({"device_distill": True} if a_.device_distill else {}),
+                         **({"boxes_per_image": a_.boxes_per_image} if a_.boxes_per_image != 12 else {})),
                      indent=1))

@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define RICHSEM_MSDA_ABI_VERSION 11
+#define RICHSEM_MSDA_ABI_VERSION 12
 
 /* Return codes: 0 = success; negative = argument error detected on the host (nothing was
  * launched); positive = hipError_t reported by the runtime. */
@@ -336,6 +336,42 @@ int msda_focal_neg_sum_masked_f32(const float *logits, const float *row_weight, 
                                   int64_t rows, int C, float alpha, double *partial, int max_partial, int *n_partial, msda_stream_t stream);
 int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
                                    int64_t rows, int C, float alpha, const float *gscale, float *grad_logits, msda_stream_t stream);
+
+/* ---- the distillation term (ABI v12; reference SetCriterion.loss_labels, models/richsem/richsem.py:967-1024): the detector's CLIP-space
+ * outputs pulled toward the frozen CLIP teacher's, over K gathered rows.  Row k reads pred[pred_row[k]] and tgt[tgt_row[k]] (pred (pred_rows,
+ * C), tgt (tgt_rows, C) contiguous; pred_row / tgt_row (K) int64 ON THE DEVICE -- the kernel guards them) with the weight row_weight[k]
+ * (K float32).  loss[0] (float32) <- the sum of the row losses, accumulated in f64; grad_rows (K, C) float32 <- d loss / d (the gathered student
+ * row), every element written; the teacher gets no gradient; the caller scatters the rows (rows that repeat in pred_row add) and multiplies
+ * by the incoming scalar gradient.  Value and gradient come from one launch, the total from a second small one; fixed shapes, no host
+ * synchronisation, no floating-point atomic: capturable, and the same inputs give the same bits.  K == 0 writes loss = 0 only.
+ * workspace: MSDA_DISTILL_WORKSPACE_BYTES of device memory owned by the CALLER (8-byte aligned; needed when K > 0; contents do not matter
+ * before and are garbage after): the workgroups' f64 partial sums.  The library keeps no memory for these calls, so a call -- eager,
+ * captured, or replayed on any stream -- touches its arguments only; two calls that may run at the same time need a workspace each.
+ * A row contributes loss 0 and a zero gradient row when row_weight[k] == 0, when pred_row[k] / tgt_row[k] lies outside [0, pred_rows) /
+ * [0, tgt_rows), when row_group[k] lies outside [0, groups), or when its class subset is empty.
+ * msda_distill_kl_f32 / msda_distill_kl_bf16 (distill_type 'clip_logits'): S_k = all C classes (row_group = class_mask = NULL, groups = 0),
+ *   or the classes with class_mask[row_group[k]][c] != 0 (row_group (K) int32, class_mask (groups, C) float32: use_fed_on_kd);
+ *     p = softmax(pred row over S_k),  t = softmax(tgt row over S_k),
+ *     row_loss_k = w_k dw_k sum_{c in S_k} t_c (log t_c - log p_c),     grad_rows[k][c] = w_k dw_k (p_c - t_c) on S_k, exactly 0 elsewhere,
+ *     dw_k = 1 (dynamic_weight = 0) or 2 H(softmax(tgt row over ALL C classes)) / ln C (dynamic_weight = 1: use_dynamic_distill_weight, formed
+ *     before the subset is taken, as the reference does; needs C >= 2).
+ *   log t and log p are formed analytically (x - max - log sum exp): an underflowed t_c = 0 contributes exactly 0 (F.kl_div's xlogy
+ *   convention), in the entropy too -- where the reference's tgt_prob * tgt_prob.log() is NaN -- so no term is NaN for finite inputs.
+ *   The bf16 entry point takes the student's logits in bf16 storage (the teacher's stay float32) and computes in f32 after the upcast: no
+ *   float32 copy of the student's logit tensor is needed.
+ * msda_distill_l1_f32 (distill_type 'clip_l1'; D >= 1 channels):  u = pred row / |pred row|_2,  v = tgt row (normalize_target = 0: objective
+ *   'gt') or tgt row / |tgt row|_2 (1: 'pred', 'pred_all');  row_loss_k = w_k |u - v|_1;  grad_rows[k] = w_k (s - u (u . s)) / |pred row|_2 with
+ *   s = sign(u - v), sign(0) = 0 (as torch differentiates |x|). */
+#define MSDA_DISTILL_WORKSPACE_BYTES 16384
+int msda_distill_kl_f32(const float *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int C, const int64_t *pred_row,
+                        const int64_t *tgt_row, const float *row_weight, int64_t K, const int32_t *row_group, const float *class_mask, int groups,
+                        int dynamic_weight, double *workspace, float *loss, float *grad_rows, msda_stream_t stream);
+int msda_distill_kl_bf16(const uint16_t *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int C, const int64_t *pred_row,
+                         const int64_t *tgt_row, const float *row_weight, int64_t K, const int32_t *row_group, const float *class_mask, int groups,
+                         int dynamic_weight, double *workspace, float *loss, float *grad_rows, msda_stream_t stream);
+int msda_distill_l1_f32(const float *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int D, const int64_t *pred_row,
+                        const int64_t *tgt_row, const float *row_weight, int64_t K, int normalize_target, double *workspace, float *loss,
+                        float *grad_rows, msda_stream_t stream);
 
 /* The criterion's per-pair tails, one launch each (K pairs, float32): loss[0] <- the weighted sum, grad <- its gradient w.r.t. the
  * predictions (multiply by the incoming scalar gradient).  msda_box_pair_loss_f32: sum_k w[k] (c_l1 |p_k - t_k|_1 + c_giou (1 - GIoU(p_k,

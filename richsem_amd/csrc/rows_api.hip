@@ -1,5 +1,5 @@
 // rows_api.hip -- C ABI of the rows around the operator (declared in include/richsem_msda.h): the matcher's cost blocks and the assignment
-// solver, the attention-pool core, the criterion's focal / box-pair / federated kernels, the decoder's box refinement and sine embedding,
+// solver, the attention-pool core, the criterion's focal / box-pair / federated / distillation kernels, the decoder's box refinement and sine embedding,
 // the narrow linear backward, PostProcess (top-k over query x class, box decode, NMS), and the module-level helpers that are not the
 // operator itself: the denoising indices and mask, per-row top-k, ROIAlign and the padding-mask rows.  A translation unit of its own so
 // that the operator's kernels (msda_api.hip) are not rebuilt with it.  Error reporting: msda_host.h.
@@ -261,6 +261,63 @@ __global__ __launch_bounds__(256) void focal_neg_grad_kernel(const float *__rest
 }
 
 #include "msda_fed.h"      // (the federated loss: class sampler + the masked form of the two kernels above, which it shares focal_neg with)
+#include "msda_distill.h"  // (the distillation term: KL of class distributions / L1 of unit vectors over gathered rows)
+
+namespace {
+
+static_assert(MSDA_DISTILL_WORKSPACE_BYTES == sizeof(double) * msda::kDistillMaxGrid, "one f64 partial per workgroup");
+
+// the checks the three distillation entry points share; MSDA_OK, or the code arg_fail has reported
+int distill_check(const char *entry, const void *pred, int64_t pred_rows, const void *tgt, int64_t tgt_rows, int C, const int64_t *pred_row,
+                  const int64_t *tgt_row, const float *row_weight, int64_t K, const int32_t *row_group, const float *class_mask, int groups,
+                  int dynamic_weight, const double *workspace, const float *loss, const float *grad_rows, size_t pred_elem)
+{
+    if (!loss || (K > 0 && (!workspace || !pred_row || !tgt_row || !row_weight || !grad_rows || (pred_rows > 0 && !pred) || (tgt_rows > 0 && !tgt))))
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, entry);
+    if (K < 0 || C < 1 || pred_rows < 0 || tgt_rows < 0 || groups < 0 || (dynamic_weight != 0 && dynamic_weight != 1) || (dynamic_weight && C < 2))
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, entry);
+    if ((class_mask != nullptr) != (groups > 0)) return msda::arg_fail(groups > 0 ? MSDA_ERR_NULL_POINTER : MSDA_ERR_BAD_DIMS, entry);      // a mask without groups, groups without a mask
+    if (class_mask && !row_group) return msda::arg_fail(MSDA_ERR_NULL_POINTER, entry);
+    if (!class_mask && row_group) return msda::arg_fail(MSDA_ERR_BAD_DIMS, entry);
+    if (!msda::aligned(pred_elem, {pred}) || !msda::aligned(4, {tgt, row_weight, row_group, class_mask, loss, grad_rows}) ||
+        !msda::aligned(8, {pred_row, tgt_row, workspace}))
+        return msda::arg_fail(MSDA_ERR_MISALIGNED, entry);
+    return MSDA_OK;
+}
+
+// K == 0: loss = 0 and nothing else; otherwise the row kernel `launch(grid)` and, with more than one workgroup, the total of the partials
+// the workgroups left in the caller's workspace
+template <typename Launch>
+int distill_run(const char *entry, int64_t K, double *partial, float *loss, hipStream_t stream, Launch launch)
+{
+    if (K == 0) {
+        const hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), stream);
+        return e == hipSuccess ? MSDA_OK : msda::hip_fail(e, entry, ": clearing the loss");
+    }
+    const int grid = (int)std::min<int64_t>(K, msda::kDistillMaxGrid);
+    launch(grid);
+    if (grid > 1)
+        hipLaunchKernelGGL(msda::distill_total_kernel, dim3(1), dim3(msda::kDistillThreads), 0, stream, (const double *)partial, grid, loss);
+    return msda::launched(entry);
+}
+
+template <typename TP>
+int distill_kl_impl(const char *entry, const TP *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int C, const int64_t *pred_row,
+                    const int64_t *tgt_row, const float *row_weight, int64_t K, const int32_t *row_group, const float *class_mask, int groups,
+                    int dynamic_weight, double *workspace, float *loss, float *grad_rows, msda_stream_t stream)
+{
+    const int rc = distill_check(entry, pred, pred_rows, tgt, tgt_rows, C, pred_row, tgt_row, row_weight, K, row_group, class_mask, groups,
+                                 dynamic_weight, workspace, loss, grad_rows, sizeof(TP));
+    if (rc != MSDA_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return distill_run(entry, K, workspace, loss, s, [&](int grid) {
+        hipLaunchKernelGGL(msda::distill_kl_kernel<TP>, dim3(grid), dim3(msda::kDistillThreads), 0, s, pred, (long long)pred_rows, tgt,
+                           (long long)tgt_rows, C, pred_row, tgt_row, row_weight, (long long)K, row_group, class_mask, groups, dynamic_weight,
+                           workspace, loss, grad_rows);
+    });
+}
+
+}  // namespace
 
 // ---- the criterion's per-pair tails as one kernel each (verdict item 3: "one kernel for the stacked focal + L1 + GIoU tails") -------------
 // Box loss of K matched pairs (reference SetCriterion.loss_boxes, models/richsem/richsem.py:1162-1188 with util/box_ops.py:9-64 on the
@@ -416,6 +473,38 @@ int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight,
     hipLaunchKernelGGL(msda::focal_neg_grad_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
                        class_mask, groups, (long long)rows, C, 1.f - alpha, gscale, grad_logits);
     return msda::launched(__func__);
+}
+
+/* The distillation term over K gathered rows (msda_distill.h; semantics in include/richsem_msda.h): loss[0] <- the sum of the row losses,
+ * grad_rows (K, C) <- the gradient w.r.t. the gathered student rows, one launch for both (+ one small launch for the total of the f64
+ * partials in the caller's workspace: the library owns no memory here). */
+int msda_distill_kl_f32(const float *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int C, const int64_t *pred_row,
+                        const int64_t *tgt_row, const float *row_weight, int64_t K, const int32_t *row_group, const float *class_mask, int groups,
+                        int dynamic_weight, double *workspace, float *loss, float *grad_rows, msda_stream_t stream)
+{
+    return distill_kl_impl(__func__, pred, pred_rows, tgt, tgt_rows, C, pred_row, tgt_row, row_weight, K, row_group, class_mask, groups,
+                           dynamic_weight, workspace, loss, grad_rows, stream);
+}
+int msda_distill_kl_bf16(const uint16_t *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int C, const int64_t *pred_row,
+                         const int64_t *tgt_row, const float *row_weight, int64_t K, const int32_t *row_group, const float *class_mask, int groups,
+                         int dynamic_weight, double *workspace, float *loss, float *grad_rows, msda_stream_t stream)
+{
+    return distill_kl_impl(__func__, reinterpret_cast<const msda::bf16_t *>(pred), pred_rows, tgt, tgt_rows, C, pred_row, tgt_row, row_weight, K,
+                           row_group, class_mask, groups, dynamic_weight, workspace, loss, grad_rows, stream);
+}
+int msda_distill_l1_f32(const float *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int D, const int64_t *pred_row,
+                        const int64_t *tgt_row, const float *row_weight, int64_t K, int normalize_target, double *workspace, float *loss,
+                        float *grad_rows, msda_stream_t stream)
+{
+    if (normalize_target != 0 && normalize_target != 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    const int rc = distill_check(__func__, pred, pred_rows, tgt, tgt_rows, D, pred_row, tgt_row, row_weight, K, nullptr, nullptr, 0, 0, workspace,
+                                 loss, grad_rows, sizeof(float));
+    if (rc != MSDA_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return distill_run(__func__, K, workspace, loss, s, [&](int grid) {
+        hipLaunchKernelGGL(msda::distill_l1_kernel, dim3(grid), dim3(msda::kDistillThreads), 0, s, pred, (long long)pred_rows, tgt,
+                           (long long)tgt_rows, D, pred_row, tgt_row, row_weight, (long long)K, normalize_target, workspace, loss, grad_rows);
+    });
 }
 
 /* The criterion's per-pair tails, one launch each (K pairs, float32, one workgroup): loss[0] <- the weighted sum, grad (K, 4) / (K) <- its
