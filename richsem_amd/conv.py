@@ -13,10 +13,6 @@ from . import _lib
 from .param_cache import VersionCache, capturing
 
 
-def _stream(dev):
-    return _lib.raw_stream(dev)
-
-
 def fold_bn(weight, bias, running_mean, running_var, eps=1e-5):
     """BatchNorm in eval mode / FrozenBatchNorm2d as y = x * scale + shift (backbone.py:45-56)"""
     scale = weight.float() * (running_var.float() + eps).rsqrt()
@@ -45,6 +41,18 @@ def _ksplit_workspace(fn, dims, device):
     return torch.zeros(n // 4, dtype=torch.float32, device=device) if n else None
 
 
+def _pack(w):
+    """w (C_out, C_in, KH, KW) fp32, contiguous -> the packed weight the forward kernel reads (``msda_conv_pack_weight``)"""
+    L = _lib.load()
+    Cout, Cin, KH, KW = w.shape
+    n = ctypes.c_int64(0)
+    _lib.check(L.msda_conv_packed_elems(Cout, Cin, KH, KW, ctypes.byref(n)))
+    packed = torch.empty(n.value, dtype=torch.int16, device=w.device)
+    with _lib.on_device(w.device):
+        _lib.check(L.msda_conv_pack_weight(w.data_ptr(), Cout, Cin, KH, KW, packed.data_ptr(), _lib.raw_stream(w.device)))
+    return packed
+
+
 class ConvAffine:
     """One convolution + affine (+ residual) (+ ReLU).  ``weight`` (C_out, C_in, KH, KW) as nn.Conv2d stores it; ``scale`` / ``shift``
     (C_out) fp32 (``None``: identity / zero).  C_out must be a multiple of 16; C_in a multiple of 32, or KH KW C_in <= 512 (the
@@ -62,12 +70,7 @@ class ConvAffine:
         dev = w.device
         self.scale = (torch.ones(self.Cout, device=dev) if scale is None else scale.detach().float().to(dev)).contiguous()
         self.shift = (torch.zeros(self.Cout, device=dev) if shift is None else shift.detach().float().to(dev)).contiguous()
-        L = _lib.load()
-        n = ctypes.c_int64(0)
-        _lib.check(L.msda_conv_packed_elems(self.Cout, self.Cin, self.KH, self.KW, ctypes.byref(n)))
-        self.packed = torch.empty(n.value, dtype=torch.int16, device=dev)
-        with _lib.on_device(dev):
-            _lib.check(L.msda_conv_pack_weight(w.data_ptr(), self.Cout, self.Cin, self.KH, self.KW, self.packed.data_ptr(), _stream(dev)))
+        self.packed = _pack(w)
 
     def out_hw(self, H, W):
         return (H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * self.pad - self.KW) // self.stride + 1
@@ -83,19 +86,10 @@ class ConvAffine:
         Ho, Wo = self.out_hw(H, W)
         if ConvAffine.flop_counter is not None:
             ConvAffine.flop_counter[0] += 2.0 * N * Ho * Wo * self.Cout * self.Cin * self.KH * self.KW
-        out = torch.empty((N, Ho, Wo, self.Cout), dtype=torch.bfloat16, device=x.device)
         if residual is not None:
-            assert residual.shape == out.shape and residual.dtype == torch.bfloat16
+            assert residual.shape == (N, Ho, Wo, self.Cout) and residual.dtype == torch.bfloat16
             residual = residual.contiguous()
-        with _lib.on_device(x.device):
-            L = _lib.load()
-            ws = _ksplit_workspace(L.msda_conv_forward_workspace_bytes, (N, H, W, self.Cin, self.Cout, self.KH, self.KW, self.stride, self.pad),
-                                   x.device)
-            _lib.check(L.msda_conv_forward_ws_bf16(
-                x.data_ptr(), self.packed.data_ptr(), self.scale.data_ptr(), self.shift.data_ptr(),
-                residual.data_ptr() if residual is not None else None, N, H, W, self.Cin, self.Cout, self.KH, self.KW, self.stride,
-                self.pad, int(self.relu), out.data_ptr(), ws.data_ptr() if ws is not None else None, _stream(x.device)))
-        return out
+        return conv_forward(x, self.packed, self.scale, self.shift, residual, self.Cout, self.KH, self.KW, self.stride, self.pad, self.relu)
 
 
 def set_tiling(co_tiles=0, pixel_tiles=0):
@@ -120,7 +114,7 @@ def conv_dgrad(dz, packed_t, x_shape, Cout, KH, KW, stride, padding, add=None, r
         _lib.check(L.msda_conv_dgrad_fused_bf16(dz.data_ptr(), packed_t.data_ptr(), N, dz.shape[1], dz.shape[2], Cout, Cin, KH, KW, stride, padding,
                                                 H, W, add.data_ptr() if add is not None else None,
                                                 relu_out.data_ptr() if relu_out is not None else None, dx.data_ptr(),
-                                                ws.data_ptr() if ws is not None else None, _stream(dz.device)))
+                                                ws.data_ptr() if ws is not None else None, _lib.raw_stream(dz.device)))
     return dx
 
 
@@ -135,8 +129,32 @@ def conv_forward(x, packed, scale, shift, residual, Cout, KH, KW, stride, paddin
         _lib.check(L.msda_conv_forward_ws_bf16(
             x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), residual.data_ptr() if residual is not None else None,
             N, H, W, Cin, Cout, KH, KW, stride, padding, int(relu), out.data_ptr(), ws.data_ptr() if ws is not None else None,
-            _stream(x.device)))
+            _lib.raw_stream(x.device)))
     return out
+
+
+def wgrad_launch(dz, x, dims, dw, dbias, scale, torch_layout):
+    """The one ``msda_conv_wgrad_bf16`` call, for a convolution (:func:`conv_wgrad`: ``scale``, no ``dbias``, ``torch_layout`` 1) and for a
+    linear layer (functions/linear.py: ``dbias``, no ``scale``, ``torch_layout`` 0): ``dims`` = (N, H, W, Cin, Cout, KH, KW, stride,
+    padding); writes ``dw`` (and ``dbias``), both fp32.  The workspace is not zeroed, and its size is asked for on every call."""
+    L = _lib.load()
+    nb = ctypes.c_int64(0)
+    _lib.check(L.msda_conv_wgrad_workspace_bytes(*dims, ctypes.byref(nb)))
+    ws = torch.empty(nb.value // 4, dtype=torch.float32, device=x.device) if nb.value else None
+    with _lib.on_device(x.device):
+        _lib.check(L.msda_conv_wgrad_bf16(dz.data_ptr(), x.data_ptr(), *dims, dw.data_ptr(), dbias.data_ptr() if dbias is not None else None,
+                                          scale.data_ptr() if scale is not None else None, torch_layout,
+                                          ws.data_ptr() if ws is not None else None, _lib.raw_stream(x.device)))
+
+
+def wgrad_group_launch(arr, n, device):
+    """The one ``msda_conv_wgrad_group_bf16`` call: ``arr`` = ``n`` (at most 8) filled ``_lib.WgradProblem``s on ``device``"""
+    L = _lib.load()
+    nb = ctypes.c_int64(0)
+    _lib.check(L.msda_conv_wgrad_group_workspace_bytes(arr, n, ctypes.byref(nb)))
+    ws = torch.empty(nb.value // 4, dtype=torch.float32, device=device) if nb.value else None
+    with _lib.on_device(device):
+        _lib.check(L.msda_conv_wgrad_group_bf16(arr, n, ws.data_ptr() if ws is not None else None, _lib.raw_stream(device)))
 
 
 def conv_wgrad(dz, x, Cout, KH, KW, stride, padding, scale=None):
@@ -144,21 +162,13 @@ def conv_wgrad(dz, x, Cout, KH, KW, stride, padding, scale=None):
     layout), times ``scale[co]`` when given.  Cout % 128 == 0 and Cin % 128 == 0."""
     N, H, W, Cin = x.shape
     dw = torch.empty((Cout, Cin, KH, KW), dtype=torch.float32, device=x.device)
-    L = _lib.load()
-    nb = ctypes.c_int64(0)
-    _lib.check(L.msda_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, padding, ctypes.byref(nb)))
-    ws = torch.empty(nb.value // 4, dtype=torch.float32, device=x.device) if nb.value else None
-    with _lib.on_device(x.device):
-        _lib.check(L.msda_conv_wgrad_bf16(dz.data_ptr(), x.data_ptr(), N, H, W, Cin, Cout, KH, KW, stride, padding, dw.data_ptr(), None,
-                                          scale.data_ptr() if scale is not None else None, 1, ws.data_ptr() if ws is not None else None,
-                                          _stream(x.device)))
+    wgrad_launch(dz, x, (N, H, W, Cin, Cout, KH, KW, stride, padding), dw, None, scale, 1)
     return dw
 
 
 def conv_wgrad_group(problems):
     """Several weight gradients in one launch (``msda_conv_wgrad_group_bf16``): ``problems`` = [(dz, x, Cout, KH, KW, stride, padding, scale)]
     as :func:`conv_wgrad` takes them (at most 8) -> the list of (Cout, Cin, KH, KW) fp32 results"""
-    L = _lib.load()
     n = len(problems)
     arr = (_lib.WgradProblem * n)()
     outs = []
@@ -169,11 +179,7 @@ def conv_wgrad_group(problems):
         outs.append(dw)
         arr[j] = _lib.WgradProblem(dz.data_ptr(), x.data_ptr(), dw.data_ptr(), scale.data_ptr() if scale is not None else None, None,
                                    N, H, W, Cin, Cout, KH, KW, stride, padding)
-    nb = ctypes.c_int64(0)
-    _lib.check(L.msda_conv_wgrad_group_workspace_bytes(arr, n, ctypes.byref(nb)))
-    ws = torch.empty(nb.value // 4, dtype=torch.float32, device=dev) if nb.value else None
-    with _lib.on_device(dev):
-        _lib.check(L.msda_conv_wgrad_group_bf16(arr, n, ws.data_ptr() if ws is not None else None, _stream(dev)))
+    wgrad_group_launch(arr, n, dev)
     return outs
 
 
@@ -184,7 +190,8 @@ def _pool(x, k, stride, pad, is_max):
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     out = torch.empty((N, Ho, Wo, C), dtype=torch.bfloat16, device=x.device)
     with _lib.on_device(x.device):
-        _lib.check(_lib.load().msda_pool_nhwc_bf16(x.data_ptr(), N, H, W, C, k, stride, pad, int(is_max), out.data_ptr(), _stream(x.device)))
+        _lib.check(_lib.load().msda_pool_nhwc_bf16(x.data_ptr(), N, H, W, C, k, stride, pad, int(is_max), out.data_ptr(),
+                                                   _lib.raw_stream(x.device)))
     return out
 
 
@@ -198,8 +205,9 @@ def max_pool_nhwc(x, k=3, stride=2, pad=1):
     return _pool(x, k, stride, pad, True)
 
 
-def group_norm8_nhwc(x, gamma, beta, eps=1e-5, want_f32=True, want_bf16=True):
-    """nn.GroupNorm(C // 8, C) on an NHWC bf16 tensor (N, H, W, C): -> (fp32 result or None, bf16 result or None), both (N, H, W, C)"""
+def _group_norm8(x, gamma, beta, eps, want_f32, want_bf16):
+    """the one ``msda_groupnorm8_nhwc_bf16`` call -> (fp32 result or None, bf16 result or None, and what the backward needs: the contiguous
+    x, the fp32 gamma, the groups' fp64 statistics)"""
     assert x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[3] % 8 == 0
     x = x.contiguous()
     N, H, W, C = x.shape
@@ -210,8 +218,13 @@ def group_norm8_nhwc(x, gamma, beta, eps=1e-5, want_f32=True, want_bf16=True):
     with _lib.on_device(x.device):
         _lib.check(_lib.load().msda_groupnorm8_nhwc_bf16(x.data_ptr(), g.data_ptr(), b.data_ptr(), float(eps), N, H * W, C, stats.data_ptr(),
                                                          o32.data_ptr() if o32 is not None else None,
-                                                         o16.data_ptr() if o16 is not None else None, _stream(x.device)))
-    return o32, o16
+                                                         o16.data_ptr() if o16 is not None else None, _lib.raw_stream(x.device)))
+    return o32, o16, x, g, stats
+
+
+def group_norm8_nhwc(x, gamma, beta, eps=1e-5, want_f32=True, want_bf16=True):
+    """nn.GroupNorm(C // 8, C) on an NHWC bf16 tensor (N, H, W, C): -> (fp32 result or None, bf16 result or None), both (N, H, W, C)"""
+    return _group_norm8(x, gamma, beta, eps, want_f32, want_bf16)[:2]
 
 
 class GroupNorm8Function(torch.autograd.Function):
@@ -220,15 +233,7 @@ class GroupNorm8Function(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        assert x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.shape[3] % 8 == 0
-        x = x.contiguous()
-        N, H, W, C = x.shape
-        stats = torch.empty(N * (C // 8) * 2, dtype=torch.float64, device=x.device)
-        out = torch.empty_like(x)
-        g, b = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
-        with _lib.on_device(x.device):
-            _lib.check(_lib.load().msda_groupnorm8_nhwc_bf16(x.data_ptr(), g.data_ptr(), b.data_ptr(), float(eps), N, H * W, C, stats.data_ptr(),
-                                                             None, out.data_ptr(), _stream(x.device)))
+        _, out, x, g, stats = _group_norm8(x, gamma, beta, eps, False, True)
         ctx.save_for_backward(x, g, stats)
         ctx.eps, ctx.dts = float(eps), (gamma.dtype, beta.dtype)
         return out
@@ -245,22 +250,11 @@ class GroupNorm8Function(torch.autograd.Function):
         with _lib.on_device(x.device):
             _lib.check(_lib.load().msda_groupnorm8_backward_nhwc_bf16(x.data_ptr(), dy.data_ptr(), g.data_ptr(), ctx.eps, N, H * W, C,
                                                                       stats.data_ptr(), bstats.data_ptr(), dx.data_ptr(), dgb[0].data_ptr(),
-                                                                      dgb[1].data_ptr(), _stream(x.device)))
+                                                                      dgb[1].data_ptr(), _lib.raw_stream(x.device)))
         return dx, dgb[0].to(ctx.dts[0]), dgb[1].to(ctx.dts[1]), None
 
 
 # ---- training: the same convolution with gradients ----------------------------------------------------------------------------------
-def _pack(w):
-    L = _lib.load()
-    Cout, Cin, KH, KW = w.shape
-    n = ctypes.c_int64(0)
-    _lib.check(L.msda_conv_packed_elems(Cout, Cin, KH, KW, ctypes.byref(n)))
-    packed = torch.empty(n.value, dtype=torch.int16, device=w.device)
-    with _lib.on_device(w.device):
-        _lib.check(L.msda_conv_pack_weight(w.data_ptr(), Cout, Cin, KH, KW, packed.data_ptr(), _stream(w.device)))
-    return packed
-
-
 class PackCache:
     """Packed forms of ONE convolution weight, owned by the module that owns the parameter (no global table: a freed tensor's address
     can come back with the same version counter): the forward weight and the flipped / transposed / scale-folded weight of the input
@@ -312,20 +306,10 @@ class ConvAffineFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, scale, shift, residual, stride, padding, relu, cache=None):
         assert x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-        Cout, Cin, KH, KW = weight.shape
+        Cout, _, KH, KW = weight.shape
         x = x.contiguous()
-        N, H, W, _ = x.shape
-        Ho, Wo = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
-        out = torch.empty((N, Ho, Wo, Cout), dtype=torch.bfloat16, device=x.device)
-        res = residual.contiguous() if residual is not None else None
-        packed = _packed_for(weight, scale, False, cache)
-        with _lib.on_device(x.device):
-            L = _lib.load()
-            ws = _ksplit_workspace(L.msda_conv_forward_workspace_bytes, (N, H, W, Cin, Cout, KH, KW, stride, padding), x.device)
-            _lib.check(L.msda_conv_forward_ws_bf16(
-                x.data_ptr(), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), res.data_ptr() if res is not None else None,
-                N, H, W, Cin, Cout, KH, KW, stride, padding, int(relu), out.data_ptr(), ws.data_ptr() if ws is not None else None,
-                _stream(x.device)))
+        out = conv_forward(x, _packed_for(weight, scale, False, cache), scale, shift, residual.contiguous() if residual is not None else None,
+                           Cout, KH, KW, stride, padding, relu)
         ctx.save_for_backward(x, weight, scale, out if relu else None)
         ctx.cfg = (stride, padding, relu, residual is not None, cache)
         return out
@@ -351,20 +335,12 @@ class ConvAffineFunction(torch.autograd.Function):
                 ws = _ksplit_workspace(L.msda_conv_dgrad_workspace_bytes, (N, dz.shape[1], dz.shape[2], Cout, Cin, KH, KW, stride, padding, H, W),
                                        x.device)
                 _lib.check(L.msda_conv_dgrad_ws_bf16(dz.data_ptr(), packed_t.data_ptr(), N, dz.shape[1], dz.shape[2], Cout, Cin, KH, KW, stride,
-                                                     padding, H, W, dx.data_ptr(), ws.data_ptr() if ws is not None else None, _stream(x.device)))
+                                                     padding, H, W, dx.data_ptr(), ws.data_ptr() if ws is not None else None,
+                                                     _lib.raw_stream(x.device)))
         if ctx.needs_input_grad[1]:
             # the weight gradient is taken with dz and scaled per output channel afterwards (the affine's scale commutes with the sum)
             if Cout % 128 == 0 and Cin % 128 == 0 and not ConvAffineFunction.library_wgrad:
-                dw = torch.empty((Cout, Cin, KH, KW), dtype=torch.float32, device=x.device)      # nn.Conv2d's layout, scaled: final
-                L = _lib.load()
-                nb = ctypes.c_int64(0)
-                _lib.check(L.msda_conv_wgrad_workspace_bytes(N, H, W, Cin, Cout, KH, KW, stride, padding, ctypes.byref(nb)))
-                ws = torch.empty(nb.value // 4, dtype=torch.float32, device=x.device) if nb.value else None
-                with _lib.on_device(x.device):
-                    _lib.check(L.msda_conv_wgrad_bf16(dz.data_ptr(), x.data_ptr(), N, H, W, Cin, Cout, KH, KW, stride, padding,
-                                                      dw.data_ptr(), None, scale.data_ptr(), 1, ws.data_ptr() if ws is not None else None,
-                                                      _stream(x.device)))
-                dw = dw.to(weight.dtype)
+                dw = conv_wgrad(dz, x, Cout, KH, KW, stride, padding, scale).to(weight.dtype)      # nn.Conv2d's layout, scaled: final
             else:       # channel counts the wgrad kernel does not take (ResNet-50's layer2-4 never get here): MIOpen
                 _, dw, _ = torch.ops.aten.convolution_backward(dz.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2),
                                                                weight.detach().to(torch.bfloat16), None, [stride, stride],

@@ -12,31 +12,13 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .linear import WgradGroup, deferrable, lin256, lin256_pack, linear_wgrad, linear_wgrad_bf16
 
 
 # The one-kernel forward walks all d_ffn / 32 weight tiles in every workgroup of 192 tokens: below this many tokens too few
 # CUs are busy and the block as library GEMMs is faster (MI355X: 2200 tokens 97 vs 78 us, 8000 tokens 100 vs 78 us, 44646 tokens
 # 117 vs 290 us).  The modules fall back to the op-by-op sequence below it.
 FUSED_FFN_MIN_TOKENS = 16384
-
-
-def _wgrad(dy, x, with_bias=False, fp32=False):
-    """dW = dy^T x (contraction over the tokens): the library's own MFMA kernel where it applies (functions/linear.py: 131 vs
-    208 us at the encoder shape), else the library's transposed GEMM.  bf16 result unless ``fp32`` (the kernel's own sums, for a caller
-    that hands them to float32 master parameters: no cast to bf16 and back)"""
-    from .linear import LinearBf16Function, linear_wgrad_bf16, linear_wgrad_supported
-    if linear_wgrad_supported(dy.shape[1], x.shape[1]) and dy.shape[0] >= LinearBf16Function.MIN_TOKENS:
-        if with_bias:
-            dw, db = linear_wgrad_bf16(dy, x.contiguous(), with_bias=True)
-            return (dw if fp32 else dw.to(torch.bfloat16)), db
-        dw = linear_wgrad_bf16(dy, x.contiguous())
-        return dw if fp32 else dw.to(torch.bfloat16)
-    dw = dy.t() @ x
-    return (dw, dy.sum(0, dtype=torch.float32)) if with_bias else dw
-
-
-def _stream(t):
-    return _lib.raw_stream(t.device)
 
 
 def pack_w2_bf16(w2):
@@ -46,7 +28,7 @@ def pack_w2_bf16(w2):
     assert w2.dtype == torch.bfloat16 and w2.is_contiguous()
     out = torch.empty_like(w2)
     with _lib.on_device(w2.device):
-        _lib.check(_lib.load().msda_ffn_pack_w2_bf16(w2.data_ptr(), w2.shape[0], w2.shape[1], out.data_ptr(), _stream(w2)))
+        _lib.check(_lib.load().msda_ffn_pack_w2_bf16(w2.data_ptr(), w2.shape[0], w2.shape[1], out.data_ptr(), _lib.raw_stream(w2.device)))
     return out
 
 
@@ -67,7 +49,7 @@ def ffn_forward_bf16(x, w1, b1, w2_packed, b2, ln_weight, ln_bias, eps=1e-5, ret
         _lib.check(_lib.load().msda_ffn_forward_train_bf16(
             x2.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2_packed.data_ptr(), b2.data_ptr(), ln_weight.data_ptr(),
             ln_bias.data_ptr(), float(eps), x2.shape[0], x2.shape[1], w1.shape[0], out.data_ptr(),
-            rstd.data_ptr() if rstd is not None else None, yhat.data_ptr() if yhat is not None else None, _stream(x)))
+            rstd.data_ptr() if rstd is not None else None, yhat.data_ptr() if yhat is not None else None, _lib.raw_stream(x.device)))
     return (out.view(x.shape), rstd, yhat) if return_rstd else out.view(x.shape)
 
 
@@ -79,7 +61,7 @@ def ffn_ln_backward_bf16(grad_out, yhat, rstd, ln_weight):
     with _lib.on_device(o2.device):
         _lib.check(_lib.load().msda_ffn_ln_backward_bf16(g2.data_ptr(), o2.data_ptr(), rstd.data_ptr(), ln_weight.data_ptr(),
                                                          o2.shape[0], 256, dz.data_ptr(), sums[0].data_ptr(),
-                                                         sums[1].data_ptr(), sums[2].data_ptr(), _stream(o2)))
+                                                         sums[1].data_ptr(), sums[2].data_ptr(), _lib.raw_stream(o2.device)))
     return dz, sums[0], sums[1], sums[2]
 
 
@@ -102,16 +84,16 @@ class FusedFFNFunction(Function):
         dz, grad_ln_w, grad_ln_b, grad_b2 = ffn_ln_backward_bf16(grad_out.to(torch.bfloat16), yhat, rstd, ln_weight)
         # the two token-parallel products with K = 256 on the library's own kernel (csrc/lin256_mfma.hip: 81 / 114 us against 173 / 204 us
         # for the library's GEMM + element-wise op): the hidden activation, recomputed, and the gradient at the ReLU's input
-        from .linear import lin256, lin256_pack
         if w1.shape[0] % 64 == 0:
             h = lin256(x2, lin256_pack(w1), b1, relu=True)
-            grad_w2 = _wgrad(dz, h)
+            grad_w2 = linear_wgrad(dz, h, False)[0].to(w2.dtype)
             gh = lin256(dz, lin256_pack(w2.t()), relu_mask=h)
         else:
             h = torch.relu(torch.addmm(b1.to(torch.bfloat16), x2, w1.t()))
-            grad_w2 = _wgrad(dz, h)
+            grad_w2 = linear_wgrad(dz, h, False)[0].to(w2.dtype)
             gh = torch.ops.aten.threshold_backward(dz @ w2, h, 0)
-        grad_w1, grad_b1 = _wgrad(gh, x2, with_bias=True)
+        grad_w1, grad_b1 = linear_wgrad(gh, x2, True)
+        grad_w1 = grad_w1.to(w1.dtype)
         grad_x = torch.addmm(dz, gh, w1).view(x.shape)                          # residual + first product's input gradient
         return grad_x, grad_w1, grad_b1, grad_w2, grad_b2, grad_ln_w, grad_ln_b, None
 
@@ -120,7 +102,6 @@ def pack_ffn(linear1_weight, linear1_bias, linear2_weight):
     """The derived forms :class:`FusedFFNCachedFunction` runs the feed-forward block from (kept by the layer in a ``VersionCache``: rebuilt
     when a parameter changes, not per call and not again in the backward): linear1.weight as bf16 and in lin256's fragment order,
     linear2.weight in the fused kernel's hidden-column order and its transpose in lin256's order, linear1.bias as float32."""
-    from .linear import lin256_pack
     w1_16 = linear1_weight.detach().to(torch.bfloat16).contiguous()
     w2_16 = linear2_weight.detach().to(torch.bfloat16).contiguous()
     return {"w1_16": w1_16, "w1_packed": lin256_pack(w1_16), "w2_ffn": pack_w2_bf16(w2_16), "w2t_packed": lin256_pack(w2_16.t().contiguous()),
@@ -131,7 +112,9 @@ class FusedFFNCachedFunction(Function):
     """:class:`FusedFFNFunction` for a caller that keeps the packed parameters (``pk`` from :func:`pack_ffn`) across calls and hands over the
     float32 master parameters themselves: ``apply(x, pk, eps, linear1.weight, linear1.bias, linear2.weight, linear2.bias, norm.weight,
     norm.bias)``.  No cast / pack / transpose kernels per call (the uncached form runs three in the forward and four in the backward), and
-    the weight gradients reach the parameters in float32 as the kernel sums them -- not rounded to bf16 on the way through a cast node."""
+    the weight gradients reach the parameters in float32 as the kernel sums them -- not rounded to bf16 on the way through a cast node.
+    The backward calls :func:`linear_wgrad_bf16` itself, not the rule of :func:`linear_wgrad`: the encoder layer hands this function only
+    layer widths the kernel takes, at token counts far above the rule's threshold (modules/encoder_layer.py: ``forward_ffn``)."""
 
     @staticmethod
     def forward(ctx, x, pk, eps, w1, b1, w2, b2, ln_weight, ln_bias):
@@ -145,7 +128,6 @@ class FusedFFNCachedFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        from .linear import lin256, linear_wgrad_bf16
         x, lw, yhat, rstd = ctx.saved_tensors
         pk, dts = ctx.pk, ctx.dts
         x2 = x.reshape(-1, x.shape[-1])
@@ -170,7 +152,7 @@ def add_layernorm_forward_bf16(a2, b2, ln_weight32, ln_bias32, eps, need_backwar
     with _lib.on_device(a2.device):
         _lib.check(_lib.load().msda_add_layernorm_forward_bf16(
             a2.data_ptr(), b2.data_ptr(), ln_weight32.data_ptr(), ln_bias32.data_ptr(), float(eps), a2.shape[0], 256, out.data_ptr(),
-            rstd.data_ptr() if need_backward else None, yhat.data_ptr() if need_backward else None, _stream(a2)))
+            rstd.data_ptr() if need_backward else None, yhat.data_ptr() if need_backward else None, _lib.raw_stream(a2.device)))
     return out, rstd, yhat
 
 
@@ -185,7 +167,6 @@ class FFNSmallFunction(Function):
 
     @staticmethod
     def forward(ctx, x, pk1, w2_16, w2t_packed, eps, w1, b1, w2, b2, ln_weight, ln_bias):
-        from .linear import lin256
         x2 = x.reshape(-1, 256).contiguous()
         h = lin256(x2, pk1["packed"], pk1["b32"], relu=True)
         y = torch.addmm(b2.detach().to(torch.bfloat16), h, w2_16.t())
@@ -193,33 +174,23 @@ class FFNSmallFunction(Function):
         out, rstd, yhat = add_layernorm_forward_bf16(x2, y, lw, lb, eps)
         ctx.save_for_backward(x2, h, yhat, rstd, lw, w2t_packed, pk1["w16"])
         ctx.meta = (x.shape, tuple(p.dtype for p in (w1, b1, w2, b2, ln_weight, ln_bias)))
-        from .linear import WgradGroup
         ctx.group = WgradGroup.active_for((w1, b1, w2))      # (only a boundary's aliases are deferred: functions/linear.py)
         return out.view(x.shape)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
-        from .linear import lin256
         x2, h, yhat, rstd, lw, w2t_packed, w1_16 = ctx.saved_tensors
         shape, dts = ctx.meta
         dz, g_lnw, g_lnb, g_b2 = ffn_ln_backward_bf16(grad_out.to(torch.bfloat16), yhat, rstd, lw)
         need = ctx.needs_input_grad
-        from .linear import deferrable
-        grp2 = deferrable(ctx.group, dz, h, (dts[2],))      # (the layer's deferred weight gradients: functions/linear.py, WgradGroup)
-        if need[7]:
-            g_w2 = grp2.add(dz, h, False)[0] if grp2 is not None else _wgrad(dz, h, fp32=dts[2] == torch.float32).to(dts[2])
-        else:
-            g_w2 = None
+        # (with the layer's group the weight gradients are deferred: functions/linear.py, WgradGroup; ``.to`` its own dtype is the tensor itself)
+        g_w2 = linear_wgrad(dz, h, False, deferrable(ctx.group, dts[2:3]))[0].to(dts[2]) if need[7] else None
         gh = lin256(dz, w2t_packed, relu_mask=h)
         g_w1 = g_b1 = None
         if need[5] or need[6]:
-            grp1 = deferrable(ctx.group, gh, x2, (dts[0], dts[1])) if (need[5] and need[6]) else None
-            if grp1 is not None:
-                g_w1, g_b1 = grp1.add(gh, x2, True)
-            else:
-                g_w1, g_b1 = _wgrad(gh, x2, with_bias=True, fp32=dts[0] == torch.float32)
-                g_w1, g_b1 = g_w1.to(dts[0]), g_b1.to(dts[1])
+            g_w1, g_b1 = linear_wgrad(gh, x2, True, deferrable(ctx.group, dts[:2]) if (need[5] and need[6]) else None)
+            g_w1, g_b1 = g_w1.to(dts[0]), g_b1.to(dts[1])
         dx = torch.addmm(dz, gh, w1_16).view(shape) if need[0] else None
         return dx, None, None, None, None, g_w1, g_b1, g_w2, g_b2.to(dts[3]), g_lnw.to(dts[4]), g_lnb.to(dts[5])
 
@@ -231,16 +202,10 @@ class AddLayerNormFunction(Function):
 
     @staticmethod
     def forward(ctx, a, b, ln_weight, ln_bias, eps):
-        a2, b2 = a.contiguous().view(-1, 256), b.contiguous().view(-1, 256)
-        out = torch.empty_like(a2)
         need = any(ctx.needs_input_grad)
-        rstd = torch.empty(a2.shape[0], dtype=torch.float32, device=a.device) if need else None
-        yhat = torch.empty_like(a2) if need else None
-        w, bi = ln_weight.detach().float().contiguous(), ln_bias.detach().float().contiguous()
-        with _lib.on_device(a.device):
-            _lib.check(_lib.load().msda_add_layernorm_forward_bf16(
-                a2.data_ptr(), b2.data_ptr(), w.data_ptr(), bi.data_ptr(), float(eps), a2.shape[0], 256, out.data_ptr(),
-                rstd.data_ptr() if need else None, yhat.data_ptr() if need else None, _stream(a)))
+        w = ln_weight.detach().float().contiguous()
+        out, rstd, yhat = add_layernorm_forward_bf16(a.contiguous().view(-1, 256), b.contiguous().view(-1, 256), w,
+                                                     ln_bias.detach().float().contiguous(), eps, need_backward=need)
         if need:
             ctx.save_for_backward(w, yhat, rstd)
         ctx.meta = (a.shape, ln_weight.dtype, ln_bias.dtype)

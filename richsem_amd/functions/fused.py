@@ -19,8 +19,14 @@ from .. import _lib
 _SFX = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}
 
 
-def _stream(t):
-    return _lib.raw_stream(t.device)
+def mask_rows_(t, mask):
+    """zero the rows of the contiguous ``t`` where the contiguous bool ``mask`` is set, IN PLACE (only those rows are touched): a row is
+    ``t.numel() // mask.numel()`` elements; float32 / float64 / bfloat16 -> ``t``"""
+    rows = mask.numel()
+    with _lib.on_device(t.device):
+        _lib.check(getattr(_lib.load(), "msda_mask_rows_" + _SFX[t.dtype])(
+            t.data_ptr(), mask.view(torch.uint8).data_ptr(), rows, t.numel() // rows, _lib.raw_stream(t.device)))
+    return t
 
 
 class MaskRows(Function):
@@ -30,11 +36,7 @@ class MaskRows(Function):
     def forward(ctx, value, mask):
         assert value.is_contiguous() and mask.dtype == torch.bool
         mask = mask.contiguous()
-        sfx = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}[value.dtype]
-        rows = mask.numel()
-        with _lib.on_device(value.device):
-            _lib.check(getattr(_lib.load(), "msda_mask_rows_" + sfx)(
-                value.data_ptr(), mask.view(torch.uint8).data_ptr(), rows, value.numel() // rows, _stream(value)))
+        mask_rows_(value, mask)
         ctx.mark_dirty(value)
         ctx.save_for_backward(mask)
         return value
@@ -43,13 +45,7 @@ class MaskRows(Function):
     @once_differentiable
     def backward(ctx, grad):
         (mask,) = ctx.saved_tensors
-        grad = grad.contiguous().clone()
-        sfx = {torch.float32: "f32", torch.float64: "f64", torch.bfloat16: "bf16"}[grad.dtype]
-        rows = mask.numel()
-        with _lib.on_device(grad.device):
-            _lib.check(getattr(_lib.load(), "msda_mask_rows_" + sfx)(
-                grad.data_ptr(), mask.view(torch.uint8).data_ptr(), rows, grad.numel() // rows, _stream(grad)))
-        return grad, None
+        return mask_rows_(grad.contiguous().clone(), mask), None
 
 
 class MSDeformAttnFusedFunction(Function):
@@ -90,7 +86,7 @@ class MSDeformAttnFusedFunction(Function):
                 value.data_ptr(), spatial_shapes.contiguous().data_ptr(), level_start_index.contiguous().data_ptr(),
                 qproj.data_ptr(), stride, qproj.data_ptr() + n_off * esz, stride, ref.data_ptr(), ref.shape[-1],
                 N, S, M, D, L, Lq, P, im2col_step, out.data_ptr(), loc.data_ptr(), aw.data_ptr(), sh.ctypes.data, ls.ctypes.data,
-                _stream(qproj)))
+                _lib.raw_stream(qproj.device)))
         ctx.save_for_backward(value, spatial_shapes, level_start_index, loc, aw, ref, qproj)
         ctx.dims = (M, L, P, im2col_step)
         return out
@@ -113,5 +109,5 @@ class MSDeformAttnFusedFunction(Function):
                 grad_loc.data_ptr(), grad_aw.data_ptr(), aw.data_ptr(), qproj.data_ptr(), stride, ref.data_ptr(),
                 ref.shape[-1], sh.ctypes.data, N, Lq, M, L, P, grad_qproj.data_ptr(), stride,
                 grad_qproj.data_ptr() + n_off * esz, stride,
-                ctypes.c_void_p(grad_ref.data_ptr()) if grad_ref is not None else None, _stream(qproj)))
+                ctypes.c_void_p(grad_ref.data_ptr()) if grad_ref is not None else None, _lib.raw_stream(qproj.device)))
         return grad_value, None, None, grad_qproj, grad_ref, None, None, None, None

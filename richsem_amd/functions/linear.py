@@ -3,12 +3,12 @@ transposed GEMM is slowest at (36 TFLOP/s at the MSDeformAttn projections' shape
 (csrc/conv_wgrad.hip) on a 1 x 1 convolution over a 1 x T "image": natural [token][channel] tiles staged through LDS and read
 transposed.  Used by the bf16 module path for the four projections of MSDeformAttn (ops/modules/ms_deform_attn.py:52-56) and by the
 feed-forward block's backward."""
-import ctypes
-
 import torch
 
 from .. import _lib
+from ..conv import wgrad_group_launch, wgrad_launch
 from ..param_cache import VersionCache  # noqa: F401  (the caches' home: richsem_amd/param_cache.py)
+from .fused import mask_rows_
 
 
 def linear_wgrad_supported(out_features, in_features):
@@ -23,27 +23,39 @@ def linear_wgrad_bf16(dy, x, with_bias=False):
     dy, x = dy.contiguous(), x.contiguous()
     T, cout = dy.shape
     cin = x.shape[1]
-    L = _lib.load()
     dw = torch.empty((cout, cin), dtype=torch.float32, device=x.device)
     db = torch.empty(cout, dtype=torch.float32, device=x.device) if with_bias else None
     if T == 0:
         return (dw.zero_(), db.zero_()) if with_bias else dw.zero_()
-    nb = ctypes.c_int64(0)
-    _lib.check(L.msda_conv_wgrad_workspace_bytes(1, 1, T, cin, cout, 1, 1, 1, 0, ctypes.byref(nb)))
-    ws = torch.empty(nb.value // 4, dtype=torch.float32, device=x.device) if nb.value else None
-    with _lib.on_device(x.device):
-        _lib.check(L.msda_conv_wgrad_bf16(dy.data_ptr(), x.data_ptr(), 1, 1, T, cin, cout, 1, 1, 1, 0, dw.data_ptr(),
-                                          db.data_ptr() if db is not None else None, None, 0, ws.data_ptr() if ws is not None else None,
-                                          _lib.raw_stream(x.device)))
+    wgrad_launch(dy, x, (1, 1, T, cin, cout, 1, 1, 1, 0), dw, db, None, 0)      # a 1 x 1 convolution over a 1 x T image
     return (dw, db) if with_bias else dw
+
+
+def linear_bgrad(dy2):
+    """bias gradient alone: the column sums of dy2 (T, out) -> (out) float32"""
+    return dy2.sum(0, dtype=torch.float32)
+
+
+def linear_wgrad(dy2, x2, want_b, group=None):
+    """THE weight-gradient rule of a linear layer, for every autograd function of the package: dy2 (T, out), x2 (T, in) bf16 ->
+    (dW = dy2^T x2 (out, in) float32, db = column sums of dy2 (out) float32, or None unless ``want_b``).  The library's kernel
+    (:func:`linear_wgrad_bf16`, the bias gradient formed on the way) where both widths are multiples of 128 and there are at least
+    ``LinearBf16Function.MIN_TOKENS`` tokens to pay for it -- registered with ``group`` (a :class:`WgradGroup`, see :func:`deferrable`)
+    instead when one is given: the tensors returned are then EMPTY until its flush; else the library's transposed bf16 GEMM, whose bf16
+    result is cast (exactly) to float32, and a column sum.  The caller casts to its parameters' dtypes."""
+    if linear_wgrad_supported(dy2.shape[1], x2.shape[1]) and dy2.shape[0] >= LinearBf16Function.MIN_TOKENS:
+        x2 = x2.contiguous()
+        if group is not None:
+            return group.add(dy2, x2, want_b)
+        return linear_wgrad_bf16(dy2, x2, with_bias=True) if want_b else (linear_wgrad_bf16(dy2, x2), None)
+    return (dy2.t() @ x2).float(), (linear_bgrad(dy2) if want_b else None)
 
 
 class LinearBf16Function(torch.autograd.Function):
     """``F.linear`` on bf16 activations with fp32 parameters (cast per call): the forward and the input gradient are the library's bf16
-    GEMMs, the weight gradient is :func:`linear_wgrad_bf16` (for layer sizes it supports and enough tokens to pay: the library's
-    transposed GEMM otherwise), the bias gradient a column sum.  Gradients come back in the parameters' dtype."""
+    GEMMs, the weight and bias gradients are :func:`linear_wgrad`'s.  Gradients come back in the parameters' dtype."""
 
-    MIN_TOKENS = 1024
+    MIN_TOKENS = 1024      # the threshold of :func:`linear_wgrad`, for every function that calls it
 
     @staticmethod
     def forward(ctx, x, weight, bias):
@@ -71,18 +83,11 @@ class LinearBf16Function(torch.autograd.Function):
             dx = (dy2 @ w16).view(x.shape)
         want_b = bdt is not None and ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1]:
-            if linear_wgrad_supported(dy2.shape[1], x2.shape[1]) and dy2.shape[0] >= LinearBf16Function.MIN_TOKENS:
-                if want_b:
-                    dw, db = linear_wgrad_bf16(dy2, x2.contiguous(), with_bias=True)
-                    db = db.to(bdt)
-                else:
-                    dw = linear_wgrad_bf16(dy2, x2.contiguous())
-                dw = dw.to(wdt)
-            else:
-                dw = (dy2.t() @ x2).to(wdt)
-        if want_b and db is None:
-            db = dy2.sum(0, dtype=torch.float32).to(bdt)
-        return dx, dw, db
+            dw, db = linear_wgrad(dy2, x2, want_b)
+            dw = dw.to(wdt)
+        elif want_b:
+            db = linear_bgrad(dy2)
+        return dx, dw, db.to(bdt) if want_b else None
 
 
 def linear_bf16(x, weight, bias=None):
@@ -174,17 +179,8 @@ class LinearBf16CachedFunction(torch.autograd.Function):
         if not any(need):          # frozen projections, or only the input gradient is wanted: no token contraction at all
             return (dx, None, None, None) + (None,) * len(dts)
         nw = 1 if split is None else 2
-        want_w, want_b = any(need[:nw]), any(need[nw:])
-        dw = db = None
-        if want_w and linear_wgrad_supported(dy2.shape[1], x2.shape[1]) and dy2.shape[0] >= LinearBf16Function.MIN_TOKENS:
-            if want_b:
-                dw, db = linear_wgrad_bf16(dy2, x2.contiguous(), with_bias=True)
-            else:
-                dw = linear_wgrad_bf16(dy2, x2.contiguous())
-        elif want_w:
-            dw = (dy2.t() @ x2).float()
-        if want_b and db is None:
-            db = dy2.sum(0, dtype=torch.float32)
+        want_b = any(need[nw:])
+        dw, db = linear_wgrad(dy2, x2, want_b) if any(need[:nw]) else (None, linear_bgrad(dy2))
         if split is None:
             grads = (dw, db)
         else:
@@ -250,14 +246,6 @@ class Lin256NarrowFunction(torch.autograd.Function):
         dw, db = dwb[:n * 256].view(n, 256), dwb[n * 256:n * 256 + n]
         return (dx.view(ctx.shape) if dx is not None else None, None, dw.to(ctx.dts[0]) if ctx.needs_input_grad[2] else None,
                 db.to(ctx.dts[1]) if ctx.needs_input_grad[3] else None)
-
-
-def _mask_rows_(t, mask):
-    """zero the rows of ``t`` (T, C) bf16 where ``mask`` (T,) bool is set, in place (only those rows are touched)"""
-    with _lib.on_device(t.device):
-        _lib.check(_lib.load().msda_mask_rows_bf16(t.data_ptr(), mask.view(torch.uint8).data_ptr(), mask.numel(), t.numel() // mask.numel(),
-                                                   _lib.raw_stream(t.device)))
-    return t
 
 
 # ---- a layer's weight gradients in ONE launch ----------------------------------------------------------------------------------------
@@ -330,19 +318,13 @@ class WgradGroup:
 
     @staticmethod
     def _launch(pend):
-        L = _lib.load()
         for i0 in range(0, len(pend), 8):
             part = pend[i0:i0 + 8]
             arr = (_lib.WgradProblem * len(part))()
             for j, (dy2, x2, dw, db) in enumerate(part):
                 arr[j] = _lib.WgradProblem(dy2.data_ptr(), x2.data_ptr(), dw.data_ptr(), None, db.data_ptr() if db is not None else None,
                                            1, 1, x2.shape[0], x2.shape[1], dy2.shape[1], 1, 1, 1, 0)
-            nb = ctypes.c_int64(0)
-            _lib.check(L.msda_conv_wgrad_group_workspace_bytes(arr, len(part), ctypes.byref(nb)))
-            dev = part[0][1].device
-            ws = torch.empty(nb.value // 4, dtype=torch.float32, device=dev) if nb.value else None
-            with _lib.on_device(dev):
-                _lib.check(L.msda_conv_wgrad_group_bf16(arr, len(part), ws.data_ptr() if ws is not None else None, _lib.raw_stream(dev)))
+            wgrad_group_launch(arr, len(part), part[0][1].device)
 
 
 class WgradBoundary(torch.autograd.Function):
@@ -369,18 +351,16 @@ def wgrad_boundary(group, *params):
     return aliases
 
 
-def deferrable(group, dy2, x2, dts):
-    """``group`` (the :class:`WgradGroup` that was active in the forward, or None) if the product dy2^T x2 can be deferred to it: the
-    weight-gradient kernel's shapes, enough tokens, float32 parameters"""
-    if group is None or not linear_wgrad_supported(dy2.shape[1], x2.shape[1]) or dy2.shape[0] < LinearBf16Function.MIN_TOKENS:
-        return None
-    return group if all(dt == torch.float32 for dt in dts) else None
+def deferrable(group, dts):
+    """``group`` (the :class:`WgradGroup` that was active in the forward, or None) if gradients for parameters of dtypes ``dts`` may be
+    deferred to it -- float32 ones: its flush writes float32 into the very tensors autograd was handed -- else None.  What
+    :func:`linear_wgrad` takes as ``group``; the shapes and the token count are its part of the rule."""
+    return group if group is not None and all(dt == torch.float32 for dt in dts) else None
 
 
 class Lin256Function(torch.autograd.Function):
     """``x W^T + b`` for a 256-wide bf16 input on the library's own MFMA kernel (csrc/lin256_mfma.hip): forward, and the input gradient
-    too when the layer is 256 -> 256 (else the library's bf16 GEMM); the weight / bias gradients on the weight-gradient kernel where
-    there are enough tokens to pay (functions/linear.py: linear_wgrad_bf16), else the library's transposed GEMM.
+    too when the layer is 256 -> 256 (else the library's bf16 GEMM); the weight / bias gradients are :func:`linear_wgrad`'s.
     ``apply(x, pk, row_mask, relu, *params)``: ``pk`` from :func:`pack_linear256` (kept by the caller in a :class:`VersionCache`);
     ``row_mask`` (tokens,) bool or None zeroes the rows of masked tokens in the kernel's epilogue (and their gradient); ``relu``: the
     ReLU in the epilogue as well; ``params`` = the weights then the biases of the stacked layers, to which the gradients are routed."""
@@ -404,7 +384,7 @@ class Lin256Function(torch.autograd.Function):
         if out is not None:           # gradient at the ReLU's input
             dy2 = torch.ops.aten.threshold_backward(dy2.contiguous(), out, 0)
         if row_mask is not None:      # (a copy: the incoming gradient is not ours to modify)
-            dy2 = _mask_rows_(dy2.clone(memory_format=torch.contiguous_format), row_mask.reshape(-1))
+            dy2 = mask_rows_(dy2.clone(memory_format=torch.contiguous_format), row_mask.reshape(-1))
         elif not dy2.is_contiguous():
             dy2 = dy2.contiguous()
         x2 = x.reshape(-1, 256)
@@ -415,20 +395,11 @@ class Lin256Function(torch.autograd.Function):
         nl = len(pk["rows"])
         grads = [None] * (2 * nl)
         if any(need):
-            want_w, want_b = any(need[:nl]), any(need[nl:])
-            dw = db = None
-            grp = deferrable(ctx.group, dy2, x2, dts) if want_w else None
-            if grp is not None:      # registered with the layer's group: written when its WgradBoundary runs
-                dw, db = grp.add(dy2, x2.contiguous(), want_b)
-            elif want_w and linear_wgrad_supported(n, 256) and dy2.shape[0] >= LinearBf16Function.MIN_TOKENS:
-                if want_b:
-                    dw, db = linear_wgrad_bf16(dy2, x2.contiguous(), with_bias=True)
-                else:
-                    dw = linear_wgrad_bf16(dy2, x2.contiguous())
-            elif want_w:
-                dw = (dy2.t() @ x2).float()
-            if want_b and db is None:
-                db = dy2.sum(0, dtype=torch.float32)
+            want_b = any(need[nl:])
+            if any(need[:nl]):      # (with the layer's group: registered, and written when its WgradBoundary runs)
+                dw, db = linear_wgrad(dy2, x2, want_b, deferrable(ctx.group, dts))
+            else:
+                dw, db = None, linear_bgrad(dy2)
             r0 = 0
             for i, r in enumerate(pk["rows"]):
                 if need[i] and dw is not None:
@@ -476,15 +447,12 @@ class StackedValueProjFunction(torch.autograd.Function):
                 cols.append(dy.reshape(T, 256))
         dy_all = torch.cat(cols, 1)                                   # (T, 256 * layers): one copy, then two products
         if row_mask is not None:
-            _mask_rows_(dy_all, row_mask.reshape(-1))
+            mask_rows_(dy_all, row_mask.reshape(-1))
         dx = (dy_all @ pk["w16"]).view(ctx.shape) if ctx.needs_input_grad[0] else None
         need = ctx.needs_input_grad[3:]
         grads = [None] * (2 * nl)
         if any(need):
-            if linear_wgrad_supported(256 * nl, 256) and T >= LinearBf16Function.MIN_TOKENS:
-                dw, db = linear_wgrad_bf16(dy_all, x2, with_bias=True)
-            else:
-                dw, db = (dy_all.t() @ x2).float(), dy_all.sum(0, dtype=torch.float32)
+            dw, db = linear_wgrad(dy_all, x2, True)
             for i in range(nl):
                 if need[i]:
                     grads[i] = dw[256 * i:256 * (i + 1)].to(dts[i])
