@@ -26,7 +26,7 @@ from torch import nn
 
 from richsem_amd import workload as W
 from richsem_amd.backbone import InputProjection, ResNet50
-from richsem_amd.capture import quiet_gc
+from richsem_amd.capture import capture, capture_stream, graphed_callables, pin_grad_accumulators      # noqa: F401  (bench_step.pin_grad_accumulators: its old home)
 from richsem_amd.clip_resnet import ModifiedResNetTeacher
 from richsem_amd.dn import prepare_dn_layout
 from richsem_amd.distill import DistillKL
@@ -524,16 +524,6 @@ def synthetic_image_counts(C, seed=1203):
     return torch.cat((torch.zeros(1, dtype=torch.int64), 1 + 10000 // rank))
 
 
-def pin_grad_accumulators(params):
-    """Create every parameter's AccumulateGrad node NOW -- on the current stream -- and return the nodes; the caller keeps them alive.
-    The autograd engine runs an AccumulateGrad node on the stream that was current when the node was CREATED, and a node lives as long as
-    some graph (or this list) references it.  Round 4's harness let the first forward that happened to touch a parameter decide -- for
-    torch.cuda.make_graphed_callables that is its private warm-up stream -- and a later backward on the capture stream then synchronised
-    with that foreign stream on every step ("AccumulateGrad node's stream does not match ..."), the precondition of the
-    hipStreamEndCapture crash of profiles/r04_capture_probe.txt.  Pinned here, every later graph reuses these nodes."""
-    return [p.view_as(p).grad_fn.next_functions[0][0] for p in params if p.requires_grad]
-
-
 CLIP_MAX_NORM = 0.1      # reference config/RichSem/baseline_4scale.py:19 (clip_max_norm), engine.py:110-112
 
 
@@ -579,18 +569,9 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
             optimizer_step(opt, params)
         return loss, fwd
 
-    # Everything -- warm-up, the timed eager steps, the capture -- runs on ONE side stream (round 4).  An autograd graph pins every
-    # parameter's AccumulateGrad node to the stream it was built on; round 3 built the eager steps on the default stream and captured on
-    # another one with the last step's `loss` still referenced: the engine then synchronises the capture stream with the foreign stream
-    # inside the capture ("AccumulateGrad node's stream does not match ..."), and this ROCm build segfaults in hipStreamEndCapture instead
-    # of failing the capture (tools/capture_crash_probe.py, profiles/r04_capture_probe.txt: only the variants that keep `loss` alive crash,
-    # and none does when the eager phase already ran on the capture stream).  The library's workspaces are per (device, stream) as well:
-    # a capture on a cold stream records the fallback kernels (round 3's 31.0 ms against 27.1 ms on the warmed stream).
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
     rows, totals, bwds = {}, [], []
-    with torch.cuda.stream(side):
-        pinned = pin_grad_accumulators(params)      # (kept alive to the end of run(): every graph below reuses these nodes)
+    with capture_stream() as side:      # warm-up, the timed eager steps and the captures below: ONE stream
+        pinned = pin_grad_accumulators(params)      # noqa: F841  (kept alive to the end of run(): every graph below reuses these nodes)
         for _ in range(warmup):
             step()
         torch.cuda.synchronize()
@@ -604,7 +585,6 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
             bwds.append(fwd.elapsed_time(b))
             for k, v in model.section_ms().items():
                 rows.setdefault(k, []).append(v)
-    torch.cuda.current_stream().wait_stream(side)
     ms = sum(totals) / len(totals)
     out = {"what": "ONE composed training step on the library's rows at configs[1] sizes: ResNet-50 (layer2-4 trained) -> input projections "
                    "-> 6 encoder layers -> two-stage score + top-900 -> denoising layout -> 6 decoder layers -> heads -> frozen CLIP-RN50 "
@@ -630,9 +610,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
             for _ in range(2):
                 step(indices, optimize=False)
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with quiet_gc(), torch.cuda.graph(g, stream=side):      # the stream that was warmed up
-            step(indices, optimize=False)
+        g = capture(lambda: step(indices, optimize=False), side)[0]      # the stream that was warmed up; the step's result dropped
         g.replay()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -705,6 +683,42 @@ class _LossPart(nn.Module):
         return self.step[0].loss_part(*tensors)
 
 
+def _graphed_setup(n_img, dev, noise_seed, fed_seed, **step_kwargs):
+    """-> (model, images, mask, targets): an untimed Step prepared for its batch, noise and federated draws frozen where a seed is given"""
+    model = Step(n_img=n_img, dev=dev, **step_kwargs)
+    model.timing = False
+    images, mask, targets = model.batch()
+    model.prepare(mask, targets)
+    model._mask = mask
+    if noise_seed is not None:
+        model.freeze_noise(noise_seed)
+    if fed_seed is not None:
+        model.freeze_fed(fed_seed)
+    return model, images, mask, targets
+
+
+def _time_steps(step, steps, warmup):
+    """-> (ms per call of ``step`` over ``steps`` calls after ``warmup`` calls, host clock around a synchronise; the last loss)"""
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        loss = step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3, loss
+
+
+def _graphed_result(what, n_img, ms, loss, model, params, optimizer, grads_extra=None, model_extra=None):
+    """the dict of run_graphed / run_graphed_device; ``grads_extra`` / ``model_extra``: None, or the keys that go with "grads" / "model\""""
+    return {"what": what, "optimizer": "AdamW(fused) + clip_grad_norm_(0.1)" if optimizer else None,
+            "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
+            "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
+            **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
+                **grads_extra, "topk": model.last_topk.clone()} if grads_extra is not None else {}),
+            **({"model": model, **model_extra} if model_extra is not None else {})}
+
+
 def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, fed_seed=None,
                 device_matcher=False, **step_kwargs):
     """The composed step as a trainer can run it WITHOUT freezing the matcher: the two device-only parts -- everything up to the matcher,
@@ -718,95 +732,54 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
     if device_matcher:
         return run_graphed_device(n_img, dev, steps=steps, warmup=warmup, optimizer=optimizer, noise_seed=noise_seed, return_grads=return_grads, lr=lr,
                                   return_model=return_model, fed_seed=fed_seed, **step_kwargs)
-    model = Step(n_img=n_img, dev=dev, **step_kwargs)
-    model.timing = False
-    images, mask, targets = model.batch()
-    model.prepare(mask, targets)
-    model._mask = mask
-    if noise_seed is not None:
-        model.freeze_noise(noise_seed)
-    if fed_seed is not None:
-        model.freeze_fed(fed_seed)
+    model, images, mask, targets = _graphed_setup(n_img, dev, noise_seed, fed_seed, **step_kwargs)
     part_a, part_b = _ModelPart(model), _LossPart(model)
-    # ONE side stream for the eager warm-up, the captures and the training steps: torch captures on its class-wide capture stream, which is
-    # set to that stream here -- the library's workspaces are per (device, stream) and are not allocated during capture (on a cold stream
-    # the capture records the fallback kernels), and an autograd graph built on another stream pins the parameters' AccumulateGrad nodes
-    # there (the capture then synchronises with that stream from inside: wrong results at best, see run())
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    saved_capture_stream = torch.cuda.graph.default_capture_stream
-    torch.cuda.graph.default_capture_stream = side
-    try:
-        with torch.cuda.stream(side):
-            pinned = pin_grad_accumulators(model.parameters())      # on `side`, before anything touches a parameter; alive to the end
-            with torch.no_grad():
-                outs = model.model_part(images, mask)
-            idx = model.pack_indices(model.match(*outs[:4], targets), targets)
-            model.loss_part(*model.model_part(images, mask), *idx).backward()      # (eager once: workspaces of this stream, caches)
-            for p in model.parameters():
+    with capture_stream() as side:      # the eager warm-up, the captures and the training steps (richsem_amd/capture.py)
+        pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (before anything touches a parameter; alive to the end)
+        with torch.no_grad():
+            outs = model.model_part(images, mask)
+        idx = model.pack_indices(model.match(*outs[:4], targets), targets)
+        model.loss_part(*model.model_part(images, mask), *idx).backward()      # (eager once: workspaces of this stream, caches)
+        for p in model.parameters():
+            p.grad = None
+        sample_b = tuple(o.detach().clone().requires_grad_(i < 5) for i, o in enumerate(outs)) + tuple(idx)
+        torch.cuda.synchronize()
+        ga, gb = graphed_callables((part_a, part_b), ((images,), sample_b), allow_unused_input=True)
+        # the frozen teacher (no gradient, independent of the student) is a HIP graph of its own, replayed BETWEEN the two halves of the
+        # matching: the cost blocks and their copy to the host are enqueued first, the teacher's ~2 ms of GPU work run while the host
+        # waits for that copy and solves the seven assignments (scipy) -- the round trip costs the step nothing
+        for _ in range(2):
+            model.teacher_part(images)
+        torch.cuda.synchronize()
+        teacher_graph, t_static = capture(lambda: model.teacher_part(images), side)
+        params = [p for p in model.parameters() if p.requires_grad]
+        opt = make_optimizer(params, lr) if optimizer else None
+        last = {}
+
+        def step():
+            for p in params:
                 p.grad = None
-            sample_b = tuple(o.detach().clone().requires_grad_(i < 5) for i, o in enumerate(outs)) + tuple(idx)
-            torch.cuda.synchronize()
-            # (make_graphed_callables warms its callables up on a PRIVATE stream of its own making -- torch/cuda/graphs.py -- before it
-            # captures them on `side`: during those three iterations the gradients arrive at the pinned nodes from that other stream, by
-            # construction.  The engine's warning about it is switched off for this one call only; every training step below runs with it
-            # on, and tests/test_gpu_step.py fails on it)
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-            try:
-                with quiet_gc():      # (richsem_amd/capture.py: a collection inside a capture aborts the process)
-                    ga, gb = torch.cuda.make_graphed_callables((part_a, part_b), ((images,), sample_b), num_warmup_iters=3, allow_unused_input=True)
-            finally:
-                torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(True)
-            # the frozen teacher (no gradient, independent of the student) is a HIP graph of its own, replayed BETWEEN the two halves of the
-            # matching: the cost blocks and their copy to the host are enqueued first, the teacher's ~2 ms of GPU work run while the host
-            # waits for that copy and solves the seven assignments (scipy) -- the round trip costs the step nothing
-            for _ in range(2):
-                model.teacher_part(images)
-            torch.cuda.synchronize()
-            teacher_graph = torch.cuda.CUDAGraph()
-            with quiet_gc(), torch.cuda.graph(teacher_graph, stream=side):
-                t_static = model.teacher_part(images)
-            params = [p for p in model.parameters() if p.requires_grad]
-            opt = make_optimizer(params, lr) if optimizer else None
-            last = {}
+            outs = ga(images)
+            with torch.no_grad():
+                pending = model.match_begin(*outs[:4], targets)           # device cost blocks -> one host copy, enqueued
+                teacher_graph.replay()
+                assign = model.match_end(pending)                         # wait for the copy, scipy (matcher.py) -- under the teacher
+            last["assign"] = assign
+            loss = gb(*outs, t_static, *model.pack_indices(assign, targets))
+            loss.backward()
+            if opt is not None:
+                optimizer_step(opt, params)
+            return loss
 
-            def step():
-                for p in params:
-                    p.grad = None
-                outs = ga(images)
-                with torch.no_grad():
-                    pending = model.match_begin(*outs[:4], targets)           # device cost blocks -> one host copy, enqueued
-                    teacher_graph.replay()
-                    assign = model.match_end(pending)                         # wait for the copy, scipy (matcher.py) -- under the teacher
-                last["assign"] = assign
-                loss = gb(*outs, t_static, *model.pack_indices(assign, targets))
-                loss.backward()
-                if opt is not None:
-                    optimizer_step(opt, params)
-                return loss
-
-            for _ in range(warmup):
-                step()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                loss = step()
-            torch.cuda.synchronize()
-            ms = (time.perf_counter() - t0) / steps * 1e3
-    finally:
-        torch.cuda.graph.default_capture_stream = saved_capture_stream
-    torch.cuda.current_stream().wait_stream(side)
-    return {"what": "the same step with its two device-only parts (model up to the matcher; criterion) captured forward + backward by "
-                    "torch.cuda.make_graphed_callables and the Hungarian assignment live on the host between them every step, under the frozen "
-                    "teacher's forward (a HIP graph of its own, replayed while the host waits for the cost blocks and solves the assignments)"
-                    + ("; then gradient clipping (0.1) + fused AdamW step (reference engine.py:105-113): a TRAINING step, the same thing "
-                       "full_step_ddp measures at N > 1" if optimizer else "; no optimizer step"),
-            "optimizer": "AdamW(fused) + clip_grad_norm_(0.1)" if optimizer else None,
-            "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
-            "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
-            **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
-                "indices": last["assign"], "topk": model.last_topk.clone()} if return_grads else {}),
-            **({"model": model, "ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else {})}
+        ms, loss = _time_steps(step, steps, warmup)
+    return _graphed_result(
+        "the same step with its two device-only parts (model up to the matcher; criterion) captured forward + backward by "
+        "torch.cuda.make_graphed_callables and the Hungarian assignment live on the host between them every step, under the frozen "
+        "teacher's forward (a HIP graph of its own, replayed while the host waits for the cost blocks and solves the assignments)"
+        + ("; then gradient clipping (0.1) + fused AdamW step (reference engine.py:105-113): a TRAINING step, the same thing "
+           "full_step_ddp measures at N > 1" if optimizer else "; no optimizer step"),
+        n_img, ms, loss, model, params, optimizer, {"indices": last["assign"]} if return_grads else None,
+        {"ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else None)
 
 
 def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False,
@@ -816,72 +789,41 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
     gradient clipping + fused AdamW.  The assignment is live: every replay solves it for that replay's model outputs.  The solver's status
     is copied to pinned memory after the replay and read one step late (a non-zero entry raises ValueError then).  Returns what
     :func:`run_graphed` returns; with ``return_model`` also "query_of_target" / "status": the static tensors every replay rewrites."""
-    model = Step(n_img=n_img, dev=dev, device_matcher=True, **step_kwargs)
-    model.timing = False
-    images, mask, targets = model.batch()
-    model.prepare(mask, targets)
-    model._mask = mask
-    if noise_seed is not None:
-        model.freeze_noise(noise_seed)
-    if fed_seed is not None:
-        model.freeze_fed(fed_seed)
+    model, images, _, _ = _graphed_setup(n_img, dev, noise_seed, fed_seed, device_matcher=True, **step_kwargs)
     whole = _WholeStep(model)
-    side = torch.cuda.Stream()      # one stream for the warm-up, the capture and the training steps: see run_graphed
-    side.wait_stream(torch.cuda.current_stream())
-    saved_capture_stream = torch.cuda.graph.default_capture_stream
-    torch.cuda.graph.default_capture_stream = side
-    try:
-        with torch.cuda.stream(side):
-            pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (alive to the end)
-            whole(images).backward()      # (eager once: workspaces of this stream, caches, the solver's LDS attribute)
-            for p in model.parameters():
+    with capture_stream() as side:
+        pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (alive to the end)
+        whole(images).backward()      # (eager once: workspaces of this stream, caches, the solver's LDS attribute)
+        for p in model.parameters():
+            p.grad = None
+        torch.cuda.synchronize()
+        model.late_status.flush()
+        gw = graphed_callables(whole, (images,), allow_unused_input=True)
+        torch.cuda.synchronize()
+        model.late_status.flush()      # (the warm-up iterations ran eagerly and pushed theirs)
+        params = [p for p in model.parameters() if p.requires_grad]
+        opt = make_optimizer(params, lr) if optimizer else None
+
+        def step(batch_images=images):
+            for p in params:
                 p.grad = None
-            torch.cuda.synchronize()
-            model.late_status.flush()
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)      # (the private warm-up stream: see run_graphed)
-            try:
-                with quiet_gc():
-                    gw = torch.cuda.make_graphed_callables(whole, (images,), num_warmup_iters=3, allow_unused_input=True)
-            finally:
-                torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(True)
-            torch.cuda.synchronize()
-            model.late_status.flush()      # (the warm-up iterations ran eagerly and pushed theirs)
-            params = [p for p in model.parameters() if p.requires_grad]
-            opt = make_optimizer(params, lr) if optimizer else None
+            loss = gw(batch_images)
+            loss.backward()
+            model.late_status.push(model.last_status)      # (raises for the PREVIOUS step's status)
+            if opt is not None:
+                optimizer_step(opt, params)
+            return loss
 
-            def step(batch_images=images):
-                for p in params:
-                    p.grad = None
-                loss = gw(batch_images)
-                loss.backward()
-                model.late_status.push(model.last_status)      # (raises for the PREVIOUS step's status)
-                if opt is not None:
-                    optimizer_step(opt, params)
-                return loss
-
-            for _ in range(warmup):
-                step()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(steps):
-                loss = step()
-            torch.cuda.synchronize()
-            ms = (time.perf_counter() - t0) / steps * 1e3
-            model.late_status.flush()
-    finally:
-        torch.cuda.graph.default_capture_stream = saved_capture_stream
-    torch.cuda.current_stream().wait_stream(side)
-    return {"what": "the same training step with the Hungarian assignment solved on the device (msda_lsap_*): model, cost blocks, assignment, "
-                    "frozen teacher and criterion captured forward + backward as ONE graphed callable, no host wait between the step's first "
-                    "and last kernel; the solver's status is read one step late"
-                    + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"),
-            "optimizer": "AdamW(fused) + clip_grad_norm_(0.1)" if optimizer else None,
-            "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
-            "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
-            **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
-                "topk": model.last_topk.clone()} if return_grads else {}),
-            **({"model": model, "ga": gw, "images": images, "step": lambda *a: _on_stream(side, lambda: step(*a)),
-                "query_of_target": model.last_qot, "status": model.last_status} if return_model else {})}
+        ms, loss = _time_steps(step, steps, warmup)
+        model.late_status.flush()
+    return _graphed_result(
+        "the same training step with the Hungarian assignment solved on the device (msda_lsap_*): model, cost blocks, assignment, "
+        "frozen teacher and criterion captured forward + backward as ONE graphed callable, no host wait between the step's first "
+        "and last kernel; the solver's status is read one step late"
+        + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"),
+        n_img, ms, loss, model, params, optimizer, {} if return_grads else None,
+        {"ga": gw, "images": images, "step": lambda *a: _on_stream(side, lambda: step(*a)),
+         "query_of_target": model.last_qot, "status": model.last_status} if return_model else None)
 
 
 def _on_stream(stream, fn):

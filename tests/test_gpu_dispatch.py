@@ -32,7 +32,7 @@ import torch
 from oracle import msda_oracle as O
 from richsem_amd import _lib, workload as W
 from richsem_amd import MultiScaleDeformableAttention as MSDA
-from richsem_amd.capture import quiet_gc
+from richsem_amd.capture import capture
 from richsem_amd.functions import MSDeformAttnFunction, MSDeformAttnFusedFunction
 
 import test_gpu_bf16 as B
@@ -452,11 +452,11 @@ def test_bf16_scratch_and_stream_capture():
     marker = torch.zeros(4, device="cuda")
 
     def captured(tensors):
-        graph = torch.cuda.CUDAGraph()
-        with quiet_gc(), torch.cuda.graph(graph, stream=side):
+        def body():
             marker.add_(1.0)      # (the graph is never empty, whatever the library call does)
             rcs, _ = call_abi(name, sfx, {}, fwd=False, stream=side.cuda_stream, tensors=tensors)
-            text = _lib.last_error()
+            return rcs, _lib.last_error()
+        graph, (rcs, text) = capture(body, side)
         return graph, rcs, text
 
     def fresh():

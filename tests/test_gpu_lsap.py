@@ -13,6 +13,7 @@ from scipy.optimize import linear_sum_assignment
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+from richsem_amd.capture import capture  # noqa: E402
 from tests.test_oracle_matcher import make_case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -253,7 +254,7 @@ def test_device_solver_equals_the_reference_matcher_fixture():
 
 
 def test_match_many_device_is_graph_safe():
-    """captured in torch.cuda.graph after a warm-up; replayed on new logits / boxes written into the static inputs and on new per-image
+    """captured into a graph after a warm-up; replayed on new logits / boxes written into the static inputs and on new per-image
     counts under the same total (CostPlan.update_); every replay equals a fresh eager solve.  No host synchronisation inside the call."""
     from richsem_amd.matcher import CostPlan, HungarianMatcher
     nq, C, n_out = 300, 80, 3
@@ -282,9 +283,7 @@ def test_match_many_device_is_graph_safe():
         finally:
             torch.cuda.set_sync_debug_mode("default")
         torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            qot, status = m.match_many_device(static, plan)
+        g, (qot, status) = capture(lambda: m.match_many_device(static, plan), side)
     torch.cuda.current_stream().wait_stream(side)
     seen = []
     for seed, sizes in ((1, (20, 30)), (2, (20, 30)), (3, (41, 9)), (4, (0, 50))):

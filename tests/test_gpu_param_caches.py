@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import layer_params as LP
-from richsem_amd.capture import quiet_gc
+from richsem_amd.capture import capture, capture_stream, graphed_callables, pin_grad_accumulators
 
 pytestmark = pytest.mark.gpu
 
@@ -188,9 +188,7 @@ def test_captured_forward_follows_a_fused_adamw_step(kind):
         for _ in range(2):
             fwd(mod, x)
         torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with quiet_gc(), torch.cuda.graph(graph, stream=side):
-            static = fwd(mod, x)
+        graph, static = capture(lambda: fwd(mod, x), side)
         graph.replay()
         torch.cuda.synchronize()
         assert _mrel(static.float(), fwd(_fresh(make, mod.state_dict()), x).float()) <= OUT_TOL
@@ -226,54 +224,40 @@ class _Bound(torch.nn.Module):
 
 @pytest.mark.parametrize("kind", ["encoder", "bottleneck"])
 def test_graphed_callable_follows_a_fused_adamw_step(kind):
-    """forward AND backward captured by torch.cuda.make_graphed_callables (bench_step.run_graphed's protocol: one side stream for the
-    warm-up and the capture, AccumulateGrad nodes pinned on it); after a fused AdamW step the replayed output and input gradient (the
-    transposed packs of the backward) must equal a fresh module's"""
-    import bench_step
+    """forward AND backward captured by richsem_amd.capture.graphed_callables (one side stream for the warm-up and the capture,
+    AccumulateGrad nodes pinned on it); after a fused AdamW step the replayed output and input gradient (the transposed packs of the
+    backward) must equal a fresh module's"""
     make, fwd, x = _case(kind)
     mod = make()
     bound = _Bound(mod, fwd)
     params = [p for p in mod.parameters() if p.requires_grad]
     opt = torch.optim.AdamW(params, lr=LR, fused=True)
     go = torch.randn(fwd(make(), x).shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    saved = torch.cuda.graph.default_capture_stream
-    torch.cuda.graph.default_capture_stream = side
-    try:
-        with torch.cuda.stream(side):
-            pinned = bench_step.pin_grad_accumulators(params)      # noqa: F841  (alive to the end: the graphs reuse these nodes)
-            _out_and_dx(bound, lambda m, t: m(t), x, go)
+    with capture_stream():
+        pinned = pin_grad_accumulators(params)      # noqa: F841  (alive to the end: the graphs reuse these nodes)
+        _out_and_dx(bound, lambda m, t: m(t), x, go)
+        for p in params:
+            p.grad = None
+        torch.cuda.synchronize()
+        gbound = graphed_callables(bound, (x.detach().clone().requires_grad_(True),))
+        for step in range(2):
             for p in params:
                 p.grad = None
+            _out_and_dx(gbound, lambda m, t: m(t), x, go)      # real gradients from the replayed backward
+            _normalise_grads(params)
+            state0 = copy.deepcopy(mod.state_dict())
+            before = {n: p.detach().to(BF) for n, p in mod.named_parameters()}
+            opt.step()
+            assert _bf16_changed(mod, before) > 0.5
+            out, dx = _out_and_dx(gbound, lambda m, t: m(t), x, go)
             torch.cuda.synchronize()
-            torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
-            try:
-                with quiet_gc():
-                    gbound = torch.cuda.make_graphed_callables(bound, (x.detach().clone().requires_grad_(True),), num_warmup_iters=3)
-            finally:
-                torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(True)
-            for step in range(2):
-                for p in params:
-                    p.grad = None
-                _out_and_dx(gbound, lambda m, t: m(t), x, go)      # real gradients from the replayed backward
-                _normalise_grads(params)
-                state0 = copy.deepcopy(mod.state_dict())
-                before = {n: p.detach().to(BF) for n, p in mod.named_parameters()}
-                opt.step()
-                assert _bf16_changed(mod, before) > 0.5
-                out, dx = _out_and_dx(gbound, lambda m, t: m(t), x, go)
-                torch.cuda.synchronize()
-                want, want_dx = _out_and_dx(_fresh(make, mod.state_dict()), fwd, x, go)
-                stale, stale_dx = _out_and_dx(_fresh(make, state0), fwd, x, go)
-                err, ctl, derr, dctl = _mrel(out, want), _mrel(stale, want), _mrel(dx, want_dx), _mrel(stale_dx, want_dx)
-                _report(f"graphed callable {kind} step {step} out", err, ctl)
-                _report(f"graphed callable {kind} step {step} dx", derr, dctl)
-                assert ctl >= 10 * OUT_TOL and dctl >= 10 * DX_TOL, (ctl, dctl)
-                assert err <= OUT_TOL and derr <= DX_TOL, (kind, step, err, derr)
-    finally:
-        torch.cuda.graph.default_capture_stream = saved
-    torch.cuda.current_stream().wait_stream(side)
+            want, want_dx = _out_and_dx(_fresh(make, mod.state_dict()), fwd, x, go)
+            stale, stale_dx = _out_and_dx(_fresh(make, state0), fwd, x, go)
+            err, ctl, derr, dctl = _mrel(out, want), _mrel(stale, want), _mrel(dx, want_dx), _mrel(stale_dx, want_dx)
+            _report(f"graphed callable {kind} step {step} out", err, ctl)
+            _report(f"graphed callable {kind} step {step} dx", derr, dctl)
+            assert ctl >= 10 * OUT_TOL and dctl >= 10 * DX_TOL, (ctl, dctl)
+            assert err <= OUT_TOL and derr <= DX_TOL, (kind, step, err, derr)
 
 
 # ---- the composed step (bench_step.py) in its three training forms ---------------------------------------------------------------

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from richsem_amd.capture import capture
 from richsem_amd.postprocess import PostProcess, nms_padded, select
 
 import postprocess_ref as R
@@ -248,9 +249,7 @@ def test_graph_replays_equal_eager():
 
     run(static)                                  # (the workspace exists before the capture)
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        captured = run(static)
+    graph, captured = capture(lambda: run(static))      # (torch's own capture stream)
     for x in inputs:
         static.copy_(x.to(DEV))
         graph.replay()
@@ -277,9 +276,7 @@ def test_capture_without_rehearsal_owns_its_workspace():
     select(lg[:1], boxes[:1], sizes[:1], k)      # (the kernels have run once, on another shape)
     assert key not in postprocess._workspaces
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        captured = select(lg, boxes, sizes, k)
+    graph, captured = capture(lambda: select(lg, boxes, sizes, k))
     assert key not in postprocess._workspaces
     for _ in range(2):
         graph.replay()

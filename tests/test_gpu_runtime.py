@@ -2,14 +2,17 @@
 their own streams.  (The reference op launches on the current stream without synchronising and keeps no state,
 SURVEY.md section 8b; this library keeps a little -- the locality monitor, LDS-limit bookkeeping -- and must stay usable
 the same way.)"""
+import contextlib
+import gc
 import threading
+import warnings
 
 import numpy as np
 import pytest
 import torch
 
 from richsem_amd import _lib, workload as W
-from richsem_amd.capture import quiet_gc
+from richsem_amd.capture import capture, capture_stream, graphed_callables, pin_grad_accumulators
 from richsem_amd import MultiScaleDeformableAttention as MSDA
 
 pytestmark = pytest.mark.gpu
@@ -36,9 +39,7 @@ def test_calls_can_be_captured_into_a_graph(which):
         for _ in range(3):
             _run(t)
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with quiet_gc(), torch.cuda.graph(graph):
-        out, grads = _run(t)
+    graph, (out, grads) = capture(lambda: _run(t))
     out.zero_()
     for x in grads:
         x.fill_(float("nan"))
@@ -93,9 +94,8 @@ def test_routed_backward_replays_from_a_graph():
             for _ in range(2):
                 MSDA.ms_deform_attn_backward(t["value"], t["shapes"], t["lsi"], t["loc"], t["aw"], t["grad_out"], 64)
         torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with quiet_gc(), torch.cuda.graph(graph, stream=side):
-            grads = MSDA.ms_deform_attn_backward(t["value"], t["shapes"], t["lsi"], t["loc"], t["aw"], t["grad_out"], 64)
+        graph, grads = capture(lambda: MSDA.ms_deform_attn_backward(t["value"], t["shapes"], t["lsi"], t["loc"], t["aw"], t["grad_out"], 64),
+                               side)
         for rep in range(3):
             for x in grads:
                 x.fill_(float("nan"))
@@ -163,3 +163,80 @@ def test_profile_filter_brackets_only_the_calls_it_names():
         _lib.set_option("profile_filter", 0)
         _lib.set_option("fwd_variant", 0)
         _lib.set_option("locality_monitor", 1)
+
+
+# ---- richsem_amd/capture.py: the capture protocol's helpers ----------------------------------------------------------------------------
+def test_capture_stream_is_current_and_the_capture_stream_for_its_body_only():
+    before_stream, before_capture = torch.cuda.current_stream(), torch.cuda.graph.default_capture_stream
+    with capture_stream() as side:
+        assert side != before_stream
+        assert torch.cuda.current_stream() == side and torch.cuda.graph.default_capture_stream is side
+        filled = torch.zeros(64, device="cuda")
+        filled.fill_(7.0)
+    assert torch.cuda.current_stream() == before_stream and torch.cuda.graph.default_capture_stream is before_capture
+    doubled = filled * 2        # the caller's stream, no synchronise in between: it waits for the side stream
+    assert torch.equal(doubled.cpu(), torch.full((64,), 14.0))
+    with pytest.raises(RuntimeError, match="body"):
+        with capture_stream() as side:
+            assert torch.cuda.graph.default_capture_stream is side
+            raise RuntimeError("body")      # (plain Python, no capture active)
+    assert torch.cuda.current_stream() == before_stream and torch.cuda.graph.default_capture_stream is before_capture
+
+
+@pytest.mark.parametrize("on_side", [True, False])
+def test_capture_replays_follow_their_input(on_side):
+    """on a side stream of capture_stream(), and with stream=None on torch's own capture stream from the caller's stream"""
+    x = torch.arange(64, dtype=torch.float32, device="cuda")
+    assert gc.isenabled()
+    with (capture_stream() if on_side else contextlib.nullcontext()) as side:
+        x * 2 + 1      # (eager once on the stream)
+        torch.cuda.synchronize()
+        graph, y = capture(lambda: x * 2 + 1, side)
+        assert gc.isenabled()
+        for seed in (1, 2):
+            new = torch.randn(64, generator=torch.Generator().manual_seed(seed))
+            x.copy_(new)
+            graph.replay()
+            torch.cuda.synchronize()
+            assert torch.equal(y.cpu(), new * 2 + 1)
+
+
+def test_graphed_callables_equal_eager_and_leave_the_mismatch_warning_on():
+    """Every warning outside the helper is an error here, so a mismatch warning leaking from a replayed backward fails the test.  That the
+    helper switched the warning back ON is read from torch's own flag, not shown by provoking the warning: the engine emits it once per
+    process, and tests/test_gpu_step.py, which runs later in the same process, must still be able to see a first one."""
+    flag = torch._C._warn_on_accumulate_grad_stream_mismatch
+    torch.manual_seed(5)
+    mod = torch.nn.Sequential(torch.nn.Linear(8, 8), torch.nn.Linear(8, 8)).cuda()
+    x = torch.randn(4, 8, device="cuda")
+    go = torch.randn(4, 8, device="cuda")
+
+    def out_and_dx(m):
+        xi = x.clone().requires_grad_(True)
+        out = m(xi)
+        out.backward(go)
+        return out.detach().clone(), xi.grad.clone()
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        with capture_stream():
+            pinned = pin_grad_accumulators(mod.parameters())      # noqa: F841  (alive to the end)
+            want = out_and_dx(mod)
+            torch.cuda.synchronize()
+            assert flag()
+            with warnings.catch_warnings():
+                warnings.simplefilter("default")
+                graphed = graphed_callables(mod, (x.clone().requires_grad_(True),))
+            assert flag()
+            for step in range(2):
+                got = out_and_dx(graphed)
+                torch.cuda.synchronize()
+                # the same two GEMMs on the same operands, fp32, 8-term sums of O(1) values: 1e-5 absolute covers any reordering of them
+                # (8 * 2^-24 * |terms| ~ 5e-7 per product, two layers) and a TF32-free GEMM of another tile shape
+                assert torch.allclose(got[0], want[0], rtol=0, atol=1e-5) and torch.allclose(got[1], want[1], rtol=0, atol=1e-5), step
+                with torch.no_grad():
+                    mod[0].weight.mul_(-0.5)      # in place: the next replay must read the new weight
+                new = out_and_dx(mod)
+                assert (new[0] - want[0]).abs().max() > 1e-2      # (the change is far above the tolerance)
+                want = new
+    torch.cuda.synchronize()

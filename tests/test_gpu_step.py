@@ -10,7 +10,7 @@ import os
 import pytest
 import torch
 
-from richsem_amd.capture import quiet_gc
+from richsem_amd.capture import capture
 
 pytestmark = pytest.mark.gpu
 
@@ -96,9 +96,7 @@ def test_step_captures_on_the_stream_it_ran_on_with_its_loss_alive():
         for _ in range(2):
             step(indices)
     torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with quiet_gc(), torch.cuda.graph(graph, stream=side):
-        loss = step(indices)
+    graph, loss = capture(lambda: step(indices), side)
     for _ in range(2):
         graph.replay()
     torch.cuda.synchronize()

@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench_step      # noqa: E402
+from richsem_amd.capture import capture_stream, pin_grad_accumulators      # noqa: E402
 
 warnings.filterwarnings("error", message=".*AccumulateGrad.*")
 kw = dict(height=256, width=320, boxes_per_image=5, seed=0)
@@ -22,10 +23,8 @@ try:
         model.timing = False
         images, mask, targets = model.batch()
         model.prepare(mask, targets)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            pinned = bench_step.pin_grad_accumulators(model.parameters())
+        with capture_stream():
+            pinned = pin_grad_accumulators(model.parameters())
             for _ in range(3):
                 model(images, mask, targets).backward()
         torch.cuda.synchronize()

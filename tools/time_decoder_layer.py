@@ -13,7 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from richsem_amd import workload as W   # noqa: E402
-from richsem_amd.capture import quiet_gc   # noqa: E402
+from richsem_amd.capture import capture, capture_stream   # noqa: E402
 from richsem_amd.modules import MLP, DeformableTransformerDecoderLayer, TransformerDecoder   # noqa: E402
 
 
@@ -32,16 +32,11 @@ def timeit(fn, reps):
 
 def timeit_graph(fn, reps):
     """the same work captured once into a HIP graph and replayed: GPU time without the host's launch gaps"""
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
+    with capture_stream() as side:
         for _ in range(3):
             fn()
-    torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with quiet_gc(), torch.cuda.graph(g, stream=side):      # (the warmed stream: the library's workspaces are per stream)
-        fn()
+    g, _ = capture(fn, side)      # (the warmed stream: the library's workspaces are per stream)
     g.replay()
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
