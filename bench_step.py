@@ -30,6 +30,7 @@ from richsem_amd.capture import capture, capture_stream, graphed_callables, pin_
 from richsem_amd.clip_resnet import ModifiedResNetTeacher
 from richsem_amd.dn import prepare_dn_layout
 from richsem_amd.distill import DistillKL
+from richsem_amd.geometry import batch_geometry, sizes_from_targets
 from richsem_amd.fed_loss import FedClassSampler, MaskedFocalNegativeSum, class_weights_from_image_counts
 from richsem_amd.functions.linear import Lin256Function, VersionCache, pack_linear256
 from richsem_amd.matcher import (BoxPairLoss, CostPlan, FocalNegativeSum, FocalPositiveSum, HungarianMatcher, LateStatus,
@@ -103,7 +104,7 @@ class Step(nn.Module):
     """the rows with their (synthetic) parameters; ``forward`` = model forward + criterion, returns the loss and section times"""
 
     def __init__(self, n_img=2, height=800, width=1333, boxes_per_image=12, seed=0, dev="cuda", fed_loss=False, fed_num_sample_cats=50,
-                 class_image_counts=None, device_matcher=False, keep_match_outputs=False, device_distill=False):
+                 class_image_counts=None, device_matcher=False, keep_match_outputs=False, device_distill=False, device_geometry=False):
         super().__init__()
         torch.manual_seed(seed)
         self.n_img, self.H, self.Wimg, self.K = n_img, height, width, boxes_per_image
@@ -162,6 +163,11 @@ class Step(nn.Module):
         self.last_qot = self.last_status = None
         self.keep_match_outputs = bool(keep_match_outputs)      # (tests: the logits / boxes the solver saw stay referenced as last_match_outputs)
         self.last_match_outputs = None
+        # the batch's geometry tensors (level masks, valid ratios, reference points, sine position, anchors) from ONE kernel inside the step
+        # (richsem_amd/geometry.py) instead of torch ops in prepare(): opt-in.  They are then part of every captured form of the step and
+        # follow the static ``sizes`` tensor at each replay, instead of staying those of the batch the graph was captured on
+        self.device_geometry = bool(device_geometry)
+        self.sizes = self._geometry = self.last_geometry = None      # (N, 2) int32 (h, w); the static buffers; the dict of the last forward
 
     # synthetic LVIS-shaped batch
     def batch(self, seed=0):
@@ -196,21 +202,31 @@ class Step(nn.Module):
     def prepare(self, mask, targets):
         """what depends on the batch's geometry only (level shapes, padding masks, valid ratios, encoder reference points, denoising
         layout) and the two-stage scorer's binding to the projection and the frozen text side: built once per batch shape -- a few small
-        launches and host -> device copies a trainer repeats per step; kept out of the step so that it can be captured into a graph"""
+        launches and host -> device copies a trainer repeats per step; kept out of the step so that it can be captured into a graph.
+        With ``device_geometry`` only what the canvas and the targets fix is built here; the image sizes go into the static ``self.sizes``
+        and ``forward`` derives the geometry from them on the device (``mask`` is then not read)"""
         dev = mask.device
         shapes = list(W.pyramid_shapes(self.H, self.Wpad))
-        masks = [F.interpolate(mask[None].float(), size=s).to(torch.bool)[0] for s in shapes]
         spatial = torch.tensor(shapes, dtype=torch.int64, device=dev)
-        st = {"shapes": shapes, "masks": masks, "spatial": spatial,
-              "lsi": torch.cat((spatial.new_zeros(1), spatial.prod(1).cumsum(0)[:-1])),
-              "mask_flat": torch.cat([m.flatten(1) for m in masks], 1),
-              "valid_ratios": torch.stack([torch.stack([(~m[:, 0, :]).sum(1) / m.shape[2], (~m[:, :, 0]).sum(1) / m.shape[1]], -1)
-                                           for m in masks], 1).float()}
-        st["ref"] = get_reference_points(shapes, st["valid_ratios"], dev)
-        st["pos_sine"] = torch.cat([sine_position(m) for m in masks], 1)                               # (N, S, 256): the masks' part of pos
+        st = {"shapes": shapes, "spatial": spatial, "lsi": torch.cat((spatial.new_zeros(1), spatial.prod(1).cumsum(0)[:-1]))}
+        if self.device_geometry:
+            sizes = sizes_from_targets(targets, dev)
+            if self.sizes is None or self.sizes.shape != sizes.shape:
+                self.sizes, self._geometry = sizes, None
+            else:
+                self.sizes.copy_(sizes)
+            if self._geometry is None:      # the buffers every forward writes again: allocated once
+                self._geometry = batch_geometry(self.sizes, (self.H, self.Wpad), shapes)
+        else:
+            masks = [F.interpolate(mask[None].float(), size=s).to(torch.bool)[0] for s in shapes]
+            st.update({"masks": masks, "mask_flat": torch.cat([m.flatten(1) for m in masks], 1),
+                       "valid_ratios": torch.stack([torch.stack([(~m[:, 0, :]).sum(1) / m.shape[2], (~m[:, :, 0]).sum(1) / m.shape[1]], -1)
+                                                    for m in masks], 1).float()})
+            st["ref"] = get_reference_points(shapes, st["valid_ratios"], dev)
+            st["pos_sine"] = torch.cat([sine_position(m) for m in masks], 1)                           # (N, S, 256): the masks' part of pos
+            st["proposals"], st["zeroed"] = encoder_output_proposals(st["mask_flat"], shapes)
         level_of = torch.cat([torch.full((h * w,), l, dtype=torch.int64, device=dev) for l, (h, w) in enumerate(shapes)])
         st["level_onehot"] = F.one_hot(level_of, len(shapes)).float()      # (S, L): the level embedding as a product (its backward a 4-row GEMM, not 22 k serialised row adds)
-        st["proposals"], st["zeroed"] = encoder_output_proposals(st["mask_flat"], shapes)
         st["known_num"] = [len(t["labels"]) for t in targets]
         st["lay"] = prepare_dn_layout(st["known_num"], DN_NUMBER, NUM_QUERIES, use_cdn=True)
         st["scale"] = self.logit_scale.detach().clone()
@@ -229,8 +245,10 @@ class Step(nn.Module):
         self._events = []
         self._mark("start")
         N, dev = images.shape[0], images.device
-        st = self.static
-        shapes, masks, spatial, lsi, mask_flat, valid_ratios = (st[k] for k in ("shapes", "masks", "spatial", "lsi", "mask_flat", "valid_ratios"))
+        st = geo = self.static
+        if self.device_geometry:      # the step's first device work: the geometry of the batch whose sizes ``self.sizes`` holds NOW
+            geo = self.last_geometry = batch_geometry(self.sizes, (self.H, self.Wpad), st["shapes"], out=self._geometry)
+        shapes, spatial, lsi, mask_flat, valid_ratios = st["shapes"], st["spatial"], st["lsi"], geo["mask_flat"], geo["valid_ratios"]
         # ---- backbone + input projections (richsem.py:581-612) -------------------------------------------------------------------
         feats = self.backbone(images)
         self._mark("backbone")
@@ -239,12 +257,12 @@ class Step(nn.Module):
         srcs, got_shapes = self.input_proj(feats, out_dtype=adt)
         assert got_shapes == shapes
         src = torch.cat(srcs, 1)
-        pos_flat = (st["pos_sine"] + st["level_onehot"] @ self.level_embed).to(adt)           # sine part + level embedding (:596-612)
+        pos_flat = (geo["pos_sine"] + st["level_onehot"] @ self.level_embed).to(adt)           # sine part + level embedding (:596-612)
         self._mark("input_proj")
         if self.stop_at == "input_proj":
             return src.float().sum() + pos_flat.float().sum()
         # ---- encoder (deformable_transformer.py:319) -------------------------------------------------------------------------------
-        ref = st["ref"]
+        ref = geo["ref"]
         memory = src
         for layer in self.encoder:
             memory = layer(memory, pos_flat, ref, spatial, lsi, mask_flat)
@@ -255,15 +273,15 @@ class Step(nn.Module):
         eo = self.enc_output
         if adt == torch.bfloat16:
             pk = self._eo_pack.get((eo.weight, eo.bias), lambda: pack_linear256([eo.weight], [eo.bias]))
-            output_memory = Lin256Function.apply(memory.masked_fill(st["zeroed"], 0.0), pk, None, False, eo.weight, eo.bias)   # bf16, lin256
+            output_memory = Lin256Function.apply(memory.masked_fill(geo["zeroed"], 0.0), pk, None, False, eo.weight, eo.bias)   # bf16, lin256
         else:
-            output_memory = eo(memory.masked_fill(st["zeroed"], 0.0))
+            output_memory = eo(memory.masked_fill(geo["zeroed"], 0.0))
         output_memory = F.layer_norm(output_memory, (256,), self.enc_output_norm.weight.to(adt), self.enc_output_norm.bias.to(adt),
                                      self.enc_output_norm.eps)
         if topk is None:
             topk = self.scorer.topk_proposals(output_memory, NUM_QUERIES)                              # no logit tensor (two_stage.py)
         self.last_topk = topk
-        coord_unselected = self.enc_out_bbox_embed(output_memory).float() + st["proposals"]
+        coord_unselected = self.enc_out_bbox_embed(output_memory).float() + geo["proposals"]
         refpoint_undetach = torch.gather(coord_unselected, 1, topk[..., None].expand(-1, -1, 4))
         tgt_undetach = torch.gather(output_memory, 1, topk[..., None].expand(-1, -1, 256)).float()
         interm = {"pred_logits": self.class_logits(tgt_undetach), "pred_boxes": refpoint_undetach.sigmoid()}
@@ -643,7 +661,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
     try:
         del model
         torch.cuda.empty_cache()
-        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill")}
+        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill", "device_geometry")}
         out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
@@ -924,13 +942,16 @@ if __name__ == "__main__":
     ap.add_argument("--boxes-per-image", type=int, default=12, help="targets per synthetic image (default 12)")
     ap.add_argument("--device-distill", action="store_true", help="the criterion's KL distillation term as one row kernel (distill.DistillKL) "
                                                                    "instead of the PyTorch composition: Step.loss_part")
+    ap.add_argument("--device-geometry", action="store_true", help="the batch's geometry tensors (masks, valid ratios, reference points, sine position, "
+                                                                    "anchors) from one kernel inside the step (richsem_amd/geometry.py) instead of "
+                                                                    "torch ops in prepare(): Step.forward")
     ap.add_argument("--device-matcher", action="store_true", help="time the graphed training step in both forms: the Hungarian assignment on the "
                                                                   "host between two captured parts (twice, to show its spread) and on the device "
                                                                   "inside one captured step")
     a_ = ap.parse_args()
     if a_.device_matcher:
         kw = dict(steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
-                  **({"device_distill": True} if a_.device_distill else {}))
+                  **({"device_distill": True} if a_.device_distill else {}), **({"device_geometry": True} if a_.device_geometry else {}))
         res = {"boxes_per_image": a_.boxes_per_image}
         for name, dm in (("host_matcher", False), ("host_matcher_again", False), ("device_matcher", True)):
             r = run_graphed(a_.images, torch.device("cuda", 0), device_matcher=dm, **kw)
@@ -941,5 +962,6 @@ if __name__ == "__main__":
         sys.exit(0)
     print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at,
                          **({"fed_loss": True} if a_.fed_loss else {}), **({"device_distill": True} if a_.device_distill else {}),
+                         **({"device_geometry": True} if a_.device_geometry else {}),
                          **({"boxes_per_image": a_.boxes_per_image} if a_.boxes_per_image != 12 else {})),
                      indent=1))

@@ -54,7 +54,7 @@
 extern "C" {
 #endif
 
-#define RICHSEM_MSDA_ABI_VERSION 12
+#define RICHSEM_MSDA_ABI_VERSION 13
 
 /* Return codes: 0 = success; negative = argument error detected on the host (nothing was
  * launched); positive = hipError_t reported by the runtime. */
@@ -372,6 +372,32 @@ int msda_distill_kl_bf16(const uint16_t *pred, int64_t pred_rows, const float *t
 int msda_distill_l1_f32(const float *pred, int64_t pred_rows, const float *tgt, int64_t tgt_rows, int D, const int64_t *pred_row,
                         const int64_t *tgt_row, const float *row_weight, int64_t K, int normalize_target, double *workspace, float *loss,
                         float *grad_rows, msda_stream_t stream);
+
+/* ---- the batch-geometry tensors (ABI v13): everything the reference derives from the padding mask at the start of a forward -- the per-level
+ * masks (F.interpolate of the image mask, models/richsem/richsem.py:593-612), get_valid_ratio (deformable_transformer.py:253-260), the
+ * encoder's reference points (:513-525), PositionEmbeddingSineHW (position_encoding.py:46-92, normalize=True, scale 2 pi) and the geometry
+ * half of gen_encoder_output_proposals (utils.py:10-65) -- from the image sizes, in ONE launch.  Every padding mask the reference builds is a
+ * bottom / right rectangle (pixel (y, x) of image n is padding iff y >= h_n or x >= w_n), so all of it is a closed form of the sizes.
+ *   sizes (N, 2) int32 ON THE DEVICE: (h_n, w_n), clamped there to [1, canvas_h] x [1, canvas_w]; shapes (L, 2) int32 ON THE HOST: (h_l, w_l)
+ *   of the pyramid's levels, 1 <= L <= 8; S = sum_l h_l w_l.  A level's pixel (y, x) is padding iff src_y(y) >= h_n or src_x(x) >= w_n with
+ *   src(i) = min(int(floorf(i * (float(in) / out))), in - 1), the nearest-neighbour rule of F.interpolate; vh_l / vw_l = the level's count of
+ *   valid rows / columns under that rule.
+ *   mask_flat (N, S) u8         1 = padding                                                                         (always written)
+ *   valid_ratios (N, L, 2) f32  (float(vw_l) / w_l, float(vh_l) / h_l)                                              (always written)
+ *   ref (N, S, L, 2) f32        [.., k, :] = ((x + 0.5) / (ratio_w_l * w_l) * ratio_w_k, (y + 0.5) / (ratio_h_l * h_l) * ratio_h_k)   (or NULL)
+ *   pos_sine (N, S, 2 F) f32    F = num_pos_feats (even, <= 256); channels [0, F) from y_embed with temperature_h, [F, 2 F) from x_embed
+ *                               with temperature_w: y_embed = (x < vw) ? min(y + 1, vh) : 0 over (vh or 0) + 1e-6, times 2 pi, over
+ *                               dim_t[i] = temperature ** (2 * (i / 2) / F); even channels sin, odd channels cos                         (or NULL)
+ *   proposals (N, S, 4) f32     log(p / (1 - p)) of p = ((x + 0.5) / vw, (y + 0.5) / vh, 0.05 * 2^l, 0.05 * 2^l); +inf in all four where
+ *   zeroed (N, S) u8            the pixel is padding or one of the four lies outside (0.01, 0.99) -- 1 there        (both, or both NULL)
+ * float32 arithmetic in the reference's operation order with IEEE division.  Alignment: valid_ratios and ref 8 bytes, pos_sine and proposals
+ * 16 (MSDA_ERR_MISALIGNED).  N * S and the workgroup count (N * sum_l ceil(h_l w_l / 32)) below 2^31 (MSDA_ERR_TOO_LARGE).  A null required
+ * pointer, proposals without zeroed or the reverse (MSDA_ERR_NULL_POINTER); N < 1, a canvas < 1, L outside 1..8, a non-positive shape,
+ * num_pos_feats odd, < 2 or > 256, 2 * num_pos_feats not a multiple of 4, a temperature <= 0 (MSDA_ERR_BAD_DIMS): refused before any launch.
+ * No host synchronisation, no allocation, no atomic: capturable; a replay follows the sizes tensor's current contents. */
+int msda_batch_geometry_f32(const int32_t *sizes, int N, int canvas_h, int canvas_w, const int32_t *shapes, int L, int num_pos_feats,
+                            float temperature_h, float temperature_w, uint8_t *mask_flat, float *valid_ratios, float *ref, float *pos_sine,
+                            float *proposals, uint8_t *zeroed, msda_stream_t stream);
 
 /* The criterion's per-pair tails, one launch each (K pairs, float32): loss[0] <- the weighted sum, grad <- its gradient w.r.t. the
  * predictions (multiply by the incoming scalar gradient).  msda_box_pair_loss_f32: sum_k w[k] (c_l1 |p_k - t_k|_1 + c_giou (1 - GIoU(p_k,

@@ -17,6 +17,9 @@ def __getattr__(name):      # PostProcess is exported from the package without i
     if name == "PostProcess":
         from .postprocess import PostProcess
         return PostProcess
+    if name in ("batch_geometry", "sizes_from_targets"):      # the batch-geometry tensors from the image sizes (geometry.py), likewise
+        from . import geometry
+        return getattr(geometry, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -7,6 +7,7 @@
 #include <hip/hip_bf16.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 
 #include "msda_host.h"
@@ -262,6 +263,7 @@ __global__ __launch_bounds__(256) void focal_neg_grad_kernel(const float *__rest
 
 #include "msda_fed.h"      // (the federated loss: class sampler + the masked form of the two kernels above, which it shares focal_neg with)
 #include "msda_distill.h"  // (the distillation term: KL of class distributions / L1 of unit vectors over gathered rows)
+#include "msda_geometry.h" // (the batch-geometry tensors from the image sizes: masks, valid ratios, reference points, sine position, anchors)
 
 namespace {
 
@@ -505,6 +507,46 @@ int msda_distill_l1_f32(const float *pred, int64_t pred_rows, const float *tgt, 
         hipLaunchKernelGGL(msda::distill_l1_kernel, dim3(grid), dim3(msda::kDistillThreads), 0, s, pred, (long long)pred_rows, tgt,
                            (long long)tgt_rows, D, pred_row, tgt_row, row_weight, (long long)K, normalize_target, workspace, loss, grad_rows);
     });
+}
+
+/* The batch-geometry tensors from the image sizes, one launch (msda_geometry.h; semantics in include/richsem_msda.h).  `shapes` is read on
+ * the host, `sizes` on the device only: nothing is read back and nothing allocated. */
+int msda_batch_geometry_f32(const int32_t *sizes, int N, int canvas_h, int canvas_w, const int32_t *shapes, int L, int num_pos_feats,
+                            float temperature_h, float temperature_w, uint8_t *mask_flat, float *valid_ratios, float *ref, float *pos_sine,
+                            float *proposals, uint8_t *zeroed, msda_stream_t stream)
+{
+    if (!sizes || !shapes || !mask_flat || !valid_ratios || ((proposals != nullptr) != (zeroed != nullptr)))
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (N < 1 || canvas_h < 1 || canvas_w < 1 || L < 1 || L > msda::kGeoMaxLevels || num_pos_feats < 2 || (num_pos_feats & 1) ||
+        (2 * (int64_t)num_pos_feats) % 4 != 0 || num_pos_feats > msda::kGeoMaxPosFeats || !(temperature_h > 0.f) || !(temperature_w > 0.f))
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    msda::GeoParams p = {};
+    p.N = N, p.L = L, p.canvas_h = canvas_h, p.canvas_w = canvas_w, p.F = num_pos_feats;
+    int64_t S = 0, blocks = 0;
+    for (int l = 0; l < L; ++l) {
+        const int h = shapes[2 * l], w = shapes[2 * l + 1];
+        if (h < 1 || w < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+        if ((int64_t)h * w >= ((int64_t)1 << 31)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
+        const int64_t tiles = ((int64_t)h * w + msda::kGeoTile - 1) / msda::kGeoTile;
+        p.h[l] = h, p.w[l] = w, p.start[l] = S, p.tiles[l] = (int)tiles, p.first_block[l] = (int)blocks;
+        S += (int64_t)h * w;
+        blocks += tiles * N;
+        if (blocks >= ((int64_t)1 << 31) || S * N >= ((int64_t)1 << 31)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
+    }
+    p.S = S;
+    p.first_block[L] = (int)blocks;
+    if (!msda::aligned(4, {sizes}) || !msda::aligned(8, {valid_ratios, ref}) || !msda::aligned(16, {pos_sine, proposals}))
+        return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
+    // dim_t[i] = temperature ** (2 * (i // 2) / num_pos_feats): the exponent formed in float32 as the reference forms it, the power
+    // correctly rounded
+    for (int i = 0; i < num_pos_feats; ++i) {
+        const float e = (2.f * (float)(i / 2)) / (float)num_pos_feats;
+        p.dim_h[i] = (float)std::pow((double)temperature_h, (double)e);
+        p.dim_w[i] = (float)std::pow((double)temperature_w, (double)e);
+    }
+    hipLaunchKernelGGL(msda::batch_geometry_kernel, dim3((unsigned)blocks), dim3(msda::kGeoThreads), 0, static_cast<hipStream_t>(stream), p, sizes,
+                       mask_flat, valid_ratios, ref, pos_sine, proposals, zeroed);
+    return msda::launched(__func__);
 }
 
 /* The criterion's per-pair tails, one launch each (K pairs, float32, one workgroup): loss[0] <- the weighted sum, grad (K, 4) / (K) <- its
