@@ -28,7 +28,7 @@ from richsem_amd import workload as W
 from richsem_amd.backbone import InputProjection, ResNet50
 from richsem_amd.capture import capture, capture_stream, graphed_callables, pin_grad_accumulators      # noqa: F401  (bench_step.pin_grad_accumulators: its old home)
 from richsem_amd.clip_resnet import ModifiedResNetTeacher
-from richsem_amd.dn import prepare_dn_layout
+from richsem_amd.dn import denoising_queries, dn_buffers, prepare_dn_layout
 from richsem_amd.distill import DistillKL
 from richsem_amd.geometry import batch_geometry, sizes_from_targets
 from richsem_amd.fed_loss import FedClassSampler, MaskedFocalNegativeSum, class_weights_from_image_counts
@@ -104,7 +104,7 @@ class Step(nn.Module):
     """the rows with their (synthetic) parameters; ``forward`` = model forward + criterion, returns the loss and section times"""
 
     def __init__(self, n_img=2, height=800, width=1333, boxes_per_image=12, seed=0, dev="cuda", fed_loss=False, fed_num_sample_cats=50,
-                 class_image_counts=None, device_matcher=False, keep_match_outputs=False, device_distill=False, device_geometry=False):
+                 class_image_counts=None, device_matcher=False, keep_match_outputs=False, device_distill=False, device_geometry=False, device_dn=False):
         super().__init__()
         torch.manual_seed(seed)
         self.n_img, self.H, self.Wimg, self.K = n_img, height, width, boxes_per_image
@@ -168,6 +168,11 @@ class Step(nn.Module):
         # follow the static ``sizes`` tensor at each replay, instead of staying those of the batch the graph was captured on
         self.device_geometry = bool(device_geometry)
         self.sizes = self._geometry = self.last_geometry = None      # (N, 2) int32 (h, w); the static buffers; the dict of the last forward
+        # the denoising queries -- label / box noise, label embedding, padded query block, mask -- from ONE kernel that reads the target
+        # counts on the device (richsem_amd/dn.py denoising_queries) instead of ~25 torch ops on the host's layout: opt-in.  The buffers
+        # have the exact capacity of the batch prepare() saw (the criterion still indexes the layout on the host)
+        self.device_dn = bool(device_dn)
+        self._dn = self.last_dn = None      # the static inputs / buffers; what the last forward's denoising part produced (tests)
 
     # synthetic LVIS-shaped batch
     def batch(self, seed=0):
@@ -229,6 +234,11 @@ class Step(nn.Module):
         st["level_onehot"] = F.one_hot(level_of, len(shapes)).float()      # (S, L): the level embedding as a product (its backward a 4-row GEMM, not 22 k serialised row adds)
         st["known_num"] = [len(t["labels"]) for t in targets]
         st["lay"] = prepare_dn_layout(st["known_num"], DN_NUMBER, NUM_QUERIES, use_cdn=True)
+        if self.device_dn:      # (host -> device copies: here, not in the step)
+            cum = torch.tensor([0] + list(torch.tensor(st["known_num"]).cumsum(0).tolist()), dtype=torch.int64, device=dev)
+            self._dn = {"cum": cum, "labels": torch.cat([t["labels"] for t in targets]).to(torch.int64).contiguous(),
+                        "boxes": torch.cat([t["boxes"] for t in targets]).float().contiguous(),
+                        "out": dn_buffers(len(targets), st["lay"]["pad_size"], NUM_QUERIES, 256, dev)}
         st["scale"] = self.logit_scale.detach().clone()
         self.scorer.prepare(self.dino_visual_proj.weight, self.text_embed, self.logit_scale)      # (its operand follows the weight's updates)
         self.static = st
@@ -291,31 +301,17 @@ class Step(nn.Module):
         # ---- denoising queries (dn_components.py:11-193): layout on the library's kernels, noise as torch ops -----------------------
         known_num, lay = st["known_num"], st["lay"]
         pad, groups = lay["pad_size"], lay["num_dn_group"]
-        labels, boxes = torch.cat([t["labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
-        known_labels, known_boxes = labels.repeat(2 * groups), boxes.repeat(2 * groups, 1)
-        fz = self.frozen_noise      # (tests: the same draws in every step and in every form of the step -- see freeze_noise)
-        p = torch.rand(known_labels.shape, device=dev) if fz is None else fz["p"]
-        rnd_lab = torch.randint(0, NUM_CLASSES, known_labels.shape, device=dev) if fz is None else fz["labels"]
-        noised = torch.where(p < 0.25, rnd_lab, known_labels)
-        xyxy = box_cxcywh_to_xyxy(known_boxes)
-        diff = torch.cat((known_boxes[:, 2:] / 2, known_boxes[:, 2:] / 2), 1)
-        sign = (torch.randint(0, 2, xyxy.shape, device=dev).float() * 2 - 1) if fz is None else fz["sign"]
-        rand_part = torch.rand(xyxy.shape, device=dev) if fz is None else fz["rand"]
-        neg = (torch.arange(known_labels.numel(), device=dev) // labels.numel()) % 2 == 1
-        rand_part = torch.where(neg[:, None], rand_part + 1.0, rand_part) * sign
-        xyxy = (xyxy + rand_part * diff).clamp(0.0, 1.0)
-        nb = torch.cat(((xyxy[:, :2] + xyxy[:, 2:]) / 2, xyxy[:, 2:] - xyxy[:, :2]), 1)
-        q_label = torch.zeros(N, pad, 256, device=dev)
-        q_bbox = torch.zeros(N, pad, 4, device=dev)
-        q_label[lay["known_bid"], lay["map_known_indice"]] = self.label_enc(noised)
-        q_bbox[lay["known_bid"], lay["map_known_indice"]] = inverse_sigmoid(nb)
+        if self.device_dn:      # (one launch: noise, embedding, block and mask)
+            q_label, q_bbox, tgt_mask = self._device_dn_queries(N, pad, dev)
+        else:
+            (q_label, q_bbox), tgt_mask = self._torch_dn_queries(N, pad, groups, targets, dev), lay["attn_mask"]
         tgt = torch.cat((q_label, self.tgt_embed.weight[None].expand(N, -1, -1)), 1)                   # embed_init_tgt
         refpoints = torch.cat((q_bbox, refpoint_undetach.detach()), 1)
         self._mark("dn")
         if self.stop_at == "dn":
             return tgt.sum() + refpoints.sum() + interm['pred_logits'].sum() + interm['pred_boxes'].sum()
         # ---- decoder (:427) -----------------------------------------------------------------------------------------------------------
-        hs, refs = self.decoder(tgt=tgt.transpose(0, 1).to(adt), memory=memory.transpose(0, 1), tgt_mask=lay["attn_mask"],
+        hs, refs = self.decoder(tgt=tgt.transpose(0, 1).to(adt), memory=memory.transpose(0, 1), tgt_mask=tgt_mask,
                                 memory_key_padding_mask=mask_flat, refpoints_unsigmoid=refpoints.transpose(0, 1), level_start_index=lsi,
                                 spatial_shapes=spatial, valid_ratios=valid_ratios)
         self._mark("decoder")
@@ -352,6 +348,41 @@ class Step(nn.Module):
         self._mark("criterion")
         return loss
 
+    def _torch_dn_queries(self, N, pad, groups, targets, dev):
+        """the noise, the embedding and the scatter as torch ops on the host's layout (the default)"""
+        lay = self.static["lay"]
+        fz = self.frozen_noise      # (tests: the same draws in every step and in every form of the step -- see freeze_noise)
+        labels, boxes = torch.cat([t["labels"] for t in targets]), torch.cat([t["boxes"] for t in targets])
+        known_labels, known_boxes = labels.repeat(2 * groups), boxes.repeat(2 * groups, 1)
+        p = torch.rand(known_labels.shape, device=dev) if fz is None else fz["p"]
+        rnd_lab = torch.randint(0, NUM_CLASSES, known_labels.shape, device=dev) if fz is None else fz["labels"]
+        noised = torch.where(p < 0.25, rnd_lab, known_labels)
+        xyxy = box_cxcywh_to_xyxy(known_boxes)
+        diff = torch.cat((known_boxes[:, 2:] / 2, known_boxes[:, 2:] / 2), 1)
+        sign = (torch.randint(0, 2, xyxy.shape, device=dev).float() * 2 - 1) if fz is None else fz["sign"]
+        rand_part = torch.rand(xyxy.shape, device=dev) if fz is None else fz["rand"]
+        neg = (torch.arange(known_labels.numel(), device=dev) // labels.numel()) % 2 == 1
+        rand_part = torch.where(neg[:, None], rand_part + 1.0, rand_part) * sign
+        xyxy = (xyxy + rand_part * diff).clamp(0.0, 1.0)
+        nb = torch.cat(((xyxy[:, :2] + xyxy[:, 2:]) / 2, xyxy[:, 2:] - xyxy[:, :2]), 1)
+        q_label = torch.zeros(N, pad, 256, device=dev)
+        q_bbox = torch.zeros(N, pad, 4, device=dev)
+        q_label[lay["known_bid"], lay["map_known_indice"]] = self.label_enc(noised)
+        q_bbox[lay["known_bid"], lay["map_known_indice"]] = inverse_sigmoid(nb)
+        self.last_dn = {"noised_label": noised, "noised_box": nb}
+        return q_label, q_bbox
+
+    def _device_dn_queries(self, N, pad, dev):
+        """the same from one launch that reads the counts on the device (richsem_amd/dn.py); fresh uniforms every step -- drawn here, so a
+        replay of a captured step draws anew --, or the frozen draws in the kernel's encoding"""
+        d, fz = self._dn, self.frozen_noise
+        uniform = torch.rand((N, pad, 10), device=dev) if fz is None else fz["uniform"]
+        q_label, q_bbox, tgt_mask, noised_label, meta = denoising_queries(
+            d["cum"], d["labels"], d["boxes"], self.label_enc.weight, uniform, pad_cap=pad, num_queries=NUM_QUERIES, num_classes=NUM_CLASSES,
+            dn_number=DN_NUMBER, label_noise_ratio=0.5, box_noise_scale=1.0, use_cdn=True, out=d["out"])
+        self.last_dn = {"noised_label": noised_label, "noised_box": d["out"]["noised_box"], "meta": meta}
+        return q_label, q_bbox, tgt_mask
+
     _model_only = False
     frozen_noise = None
     frozen_fed = None
@@ -366,6 +397,15 @@ class Step(nn.Module):
         self.frozen_noise = {"p": torch.rand(n, device=dev, generator=g), "labels": torch.randint(0, NUM_CLASSES, (n,), device=dev, generator=g),
                              "sign": torch.randint(0, 2, (n, 4), device=dev, generator=g).float() * 2 - 1,
                              "rand": torch.rand((n, 4), device=dev, generator=g)}
+        if self.device_dn:
+            # the same draws as the kernel takes them: row g * total + cum[b] + j of the reference's order is slot (b, g * single_pad + j) --
+            # the pair (known_bid, map_known_indice) --, sign -1 / +1 is 0.25 / 0.75 and class k is (k + 0.5) / num_classes, which floors back to k
+            fz, lay = self.frozen_noise, st["lay"]
+            u = torch.zeros((len(st["known_num"]), lay["pad_size"], 10), device=dev)
+            rows = torch.cat((fz["p"][:, None], ((fz["labels"].float() + 0.5) / NUM_CLASSES)[:, None],
+                              torch.where(fz["sign"] > 0, 0.75, 0.25).float(), fz["rand"]), 1)
+            u[lay["known_bid"], lay["map_known_indice"]] = rows
+            fz["uniform"] = u
 
     def fed_groups(self):
         """how many class draws a step of the federated loss makes: one per reference loss_labels call -- the matching part of every
@@ -661,7 +701,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
     try:
         del model
         torch.cuda.empty_cache()
-        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill", "device_geometry")}
+        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill", "device_geometry", "device_dn")}
         out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
@@ -942,6 +982,9 @@ if __name__ == "__main__":
     ap.add_argument("--boxes-per-image", type=int, default=12, help="targets per synthetic image (default 12)")
     ap.add_argument("--device-distill", action="store_true", help="the criterion's KL distillation term as one row kernel (distill.DistillKL) "
                                                                    "instead of the PyTorch composition: Step.loss_part")
+    ap.add_argument("--device-dn", action="store_true", help="the denoising queries (label / box noise, label embedding, padded query block, mask) from "
+                                                              "one kernel that reads the target counts on the device (richsem_amd/dn.py) instead "
+                                                              "of torch ops on the host's layout: Step.forward")
     ap.add_argument("--device-geometry", action="store_true", help="the batch's geometry tensors (masks, valid ratios, reference points, sine position, "
                                                                     "anchors) from one kernel inside the step (richsem_amd/geometry.py) instead of "
                                                                     "torch ops in prepare(): Step.forward")
@@ -949,8 +992,9 @@ if __name__ == "__main__":
                                                                   "host between two captured parts (twice, to show its spread) and on the device "
                                                                   "inside one captured step")
     a_ = ap.parse_args()
+    dn_kw = {"device_dn": True} if a_.device_dn else {}
     if a_.device_matcher:
-        kw = dict(steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
+        kw = dict(**dn_kw, steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
                   **({"device_distill": True} if a_.device_distill else {}), **({"device_geometry": True} if a_.device_geometry else {}))
         res = {"boxes_per_image": a_.boxes_per_image}
         for name, dm in (("host_matcher", False), ("host_matcher_again", False), ("device_matcher", True)):
@@ -962,6 +1006,6 @@ if __name__ == "__main__":
         sys.exit(0)
     print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at,
                          **({"fed_loss": True} if a_.fed_loss else {}), **({"device_distill": True} if a_.device_distill else {}),
-                         **({"device_geometry": True} if a_.device_geometry else {}),
+                         **({"device_geometry": True} if a_.device_geometry else {}), **dn_kw,
                          **({"boxes_per_image": a_.boxes_per_image} if a_.boxes_per_image != 12 else {})),
                      indent=1))

@@ -420,6 +420,44 @@ int msda_dn_indices_i64(const int64_t *cum, int batch, int64_t total, int groups
                         int64_t *map_known_indice, msda_stream_t stream);
 int msda_dn_attn_mask_u8(uint8_t *mask, int64_t tgt_size, int64_t pad_size, int64_t group_pad, msda_stream_t stream);
 
+/* ---- the denoising queries from the target counts ON THE DEVICE (reference models/richsem/dn_components.py:11-193 with
+ * check_pos_dn=False): the reference's input_query_label, input_query_bbox, attn_mask and dn_meta in ONE launch, into buffers of a fixed
+ * capacity pad_cap, and the label table's gradient in one more.  (Additions within ABI v13: nothing existing changes.)
+ *   cum (N + 1) int64     exclusive prefix of the per-image target counts (what msda_dn_indices_i64 takes; here read on the device)
+ *   labels int64, boxes (., 4) f32 cxcywh: target_cap rows each (the caller's capacity; the first cum[N] are read)
+ *   uniform (N, pad_cap, 10) f32 in [0, 1): per slot p, u_label, u_sign[4], u_part[4] -- the caller draws it, so a replay draws anew
+ *   table (V, D) f32      what label_enc looks up (nn.Embedding, LabelEnc(weight), CLIPAlign.get_label_enc: a row lookup all three)
+ * Layout: single_pad = the largest count; groups from dn_number, single_pad and add_gt as :27-41; pad_size = single_pad * 2 * groups,
+ * halved when use_cdn = 0.  Slot s of image b: gi = s / single_pad, j = s % single_pad, group-half g2 = gi (use_cdn) or 2 gi (the positive
+ * halves only); filled iff s < pad_size and j < count_b; its target is cum[b] + j.
+ *   label: p < label_noise_ratio * 0.5 takes min(floor(u_label * num_classes), num_classes - 1), otherwise the target's label;
+ *   box:   rand_part = (u_part + (g2 odd ? 1 : 0)) * (u_sign < 0.5 ? -1 : 1); xyxy + rand_part * (w/2, h/2, w/2, h/2) * box_noise_scale,
+ *          clamped to [0, 1], back to cxcywh -- float32 operation by operation without contraction: equal to torch's bit for bit;
+ *          box_noise_scale = 0 keeps the target's box (:73);
+ *   add_gt: group-half 0 keeps label and box (:60-61, :86-87).
+ *   q_label (N, pad_cap, D) f32       table[label] in a filled slot, zeros elsewhere (and for a label outside [0, V))
+ *   q_bbox (N, pad_cap, 4) f32        inverse_sigmoid (eps 1e-3, util/misc.py:605-609) of the noised box; zeros in an empty slot
+ *   noised_label (N, pad_cap) int64   -1 in an empty slot
+ *   noised_box (N, pad_cap, 4) f32    the noised box before inverse_sigmoid; zeros in an empty slot                          (or NULL)
+ *   attn_mask (T, T) u8, T = pad_cap + num_queries, 1 = masked: on rows / columns [0, pad_size) and [pad_cap, T) the reference's mask
+ *          (:157-179); the tail columns [pad_size, pad_cap) are masked for every row; a tail row sees the matching queries only
+ *   meta int64[5]                     single_pad, num_dn_group, pad_size, total = cum[N], overflow
+ * Overflow (a graph cannot raise): if pad_size > pad_cap or cum[N] > target_cap, overflow = 1, pad_size = 0 and every slot is empty.
+ * Every element of every output is written: no memset, no atomic, no host synchronisation, no allocation -- capturable; a replay follows
+ * the current contents of cum, labels, boxes and uniform.  Alignment: boxes, table, q_label, q_bbox, noised_box, attn_mask 16 bytes, the
+ * int64 arguments 8, uniform 4 (MSDA_ERR_MISALIGNED).  N < 1, pad_cap < 0, D < 4 or not a multiple of 4, V < 1, num_classes < 1, a negative
+ * num_queries / dn_number / target_cap / ratio / scale, use_cdn or add_gt outside {0, 1} (MSDA_ERR_BAD_DIMS); a null pointer to a buffer
+ * that has elements (MSDA_ERR_NULL_POINTER): refused before any launch.
+ * msda_dn_queries_backward_f32: grad_table (V, D) <- per class v the sum over rows r = 0 .. rows - 1, in that order, of grad_q_label[r]
+ *   where noised_label[r] == v; every row is written (zeros where no slot hits); no atomic, bitwise reproducible.  Labels, boxes and the
+ *   uniforms get no gradient, as in the reference. */
+int msda_dn_queries_f32(const int64_t *cum, const int64_t *labels, const float *boxes, int64_t target_cap, const float *uniform,
+                        const float *table, int N, int pad_cap, int D, int V, int num_classes, int num_queries, int dn_number,
+                        float label_noise_ratio, float box_noise_scale, int use_cdn, int add_gt, float *q_label, float *q_bbox,
+                        int64_t *noised_label, float *noised_box, uint8_t *attn_mask, int64_t *meta, msda_stream_t stream);
+int msda_dn_queries_backward_f32(const float *grad_q_label, const int64_t *noised_label, int64_t rows, int D, int V, float *grad_table,
+                                 msda_stream_t stream);
+
 /* Top-k query selection (reference models/richsem/deformable_transformer.py:370-372: torch.topk(scores, k, dim=1)[1]): for every
  * row of `scores` (rows x n, float32) the indices -- and, if `values` is non-NULL, the scores -- of its k largest elements in
  * descending order; equal scores lowest index first.  n <= 36864, k <= 1024 (one workgroup holds a row in LDS). */

@@ -20,6 +20,9 @@ def __getattr__(name):      # PostProcess is exported from the package without i
     if name in ("batch_geometry", "sizes_from_targets"):      # the batch-geometry tensors from the image sizes (geometry.py), likewise
         from . import geometry
         return getattr(geometry, name)
+    if name in ("denoising_queries", "dn_capacity", "DenoisingQueriesFunction"):      # the denoising queries from the counts on the device (dn.py)
+        from . import dn
+        return getattr(dn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

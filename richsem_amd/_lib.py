@@ -69,7 +69,7 @@ SYMBOLS = [
     "msda_attn_workspace_bytes", "msda_attn_forward_bf16", "msda_attn_backward_bf16",
     "msda_matcher_cost_f32", "msda_matcher_cost_f64", "msda_matcher_cost_tm_f32", "msda_matcher_cost_tm_f64",
     "msda_lsap_workspace_bytes", "msda_lsap_f32", "msda_lsap_f64", "msda_focal_neg_sum_f32", "msda_focal_neg_grad_f32", "msda_fed_class_mask_f32", "msda_focal_neg_sum_masked_f32", "msda_focal_neg_grad_masked_f32",
-    "msda_distill_kl_f32", "msda_distill_kl_bf16", "msda_distill_l1_f32", "msda_batch_geometry_f32",
+    "msda_distill_kl_f32", "msda_distill_kl_bf16", "msda_distill_l1_f32", "msda_batch_geometry_f32", "msda_dn_queries_f32", "msda_dn_queries_backward_f32",
     "msda_attnpool_core_f32", "msda_attnpool_core_f64",
     "msda_postprocess_workspace_bytes", "msda_postprocess_select", "msda_nms_f32",
     "msda_cls_packed_elems", "msda_cls_pack", "msda_cls_max_scores",
@@ -174,6 +174,10 @@ def load():
     L.msda_distill_l1_f32.restype = ci
     L.msda_batch_geometry_f32.argtypes = [vp, ci, ci, ci, vp, ci, ci, ctypes.c_float, ctypes.c_float] + [vp] * 7
     L.msda_batch_geometry_f32.restype = ci
+    L.msda_dn_queries_f32.argtypes = [vp, vp, vp, i64, vp, vp] + [ci] * 7 + [ctypes.c_float, ctypes.c_float, ci, ci] + [vp] * 7
+    L.msda_dn_queries_f32.restype = ci
+    L.msda_dn_queries_backward_f32.argtypes = [vp, vp, i64, ci, ci, vp, vp]
+    L.msda_dn_queries_backward_f32.restype = ci
     for sfx in ("f32", "f64"):
         f = getattr(L, "msda_attnpool_core_" + sfx)
         f.argtypes = [vp] * 4 + [ci] * 5 + [vp, vp]

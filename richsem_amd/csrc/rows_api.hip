@@ -264,6 +264,7 @@ __global__ __launch_bounds__(256) void focal_neg_grad_kernel(const float *__rest
 #include "msda_fed.h"      // (the federated loss: class sampler + the masked form of the two kernels above, which it shares focal_neg with)
 #include "msda_distill.h"  // (the distillation term: KL of class distributions / L1 of unit vectors over gathered rows)
 #include "msda_geometry.h" // (the batch-geometry tensors from the image sizes: masks, valid ratios, reference points, sine position, anchors)
+#include "msda_dn_noise.h" // (the denoising queries from the target counts on the device: label / box noise, embedding, mask; the table's gradient)
 
 namespace {
 
@@ -546,6 +547,53 @@ int msda_batch_geometry_f32(const int32_t *sizes, int N, int canvas_h, int canva
     }
     hipLaunchKernelGGL(msda::batch_geometry_kernel, dim3((unsigned)blocks), dim3(msda::kGeoThreads), 0, static_cast<hipStream_t>(stream), p, sizes,
                        mask_flat, valid_ratios, ref, pos_sine, proposals, zeroed);
+    return msda::launched(__func__);
+}
+
+/* The denoising queries from the per-image target counts on the device, one launch (msda_dn_noise.h; semantics in include/richsem_msda.h):
+ * nothing is read back and nothing allocated, every element of every output is written.  A buffer that has no elements may be null. */
+int msda_dn_queries_f32(const int64_t *cum, const int64_t *labels, const float *boxes, int64_t target_cap, const float *uniform,
+                        const float *table, int N, int pad_cap, int D, int V, int num_classes, int num_queries, int dn_number,
+                        float label_noise_ratio, float box_noise_scale, int use_cdn, int add_gt, float *q_label, float *q_bbox,
+                        int64_t *noised_label, float *noised_box, uint8_t *attn_mask, int64_t *meta, msda_stream_t stream)
+{
+    if (N < 1 || pad_cap < 0 || D < 4 || D % 4 != 0 || V < 1 || num_classes < 1 || num_queries < 0 || dn_number < 0 || target_cap < 0 ||
+        (use_cdn != 0 && use_cdn != 1) || (add_gt != 0 && add_gt != 1) || !(label_noise_ratio >= 0.f) || !(box_noise_scale >= 0.f))
+        return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    const int64_t rows = (int64_t)N * pad_cap, T = (int64_t)pad_cap + num_queries;
+    if (!cum || !table || !meta || (target_cap > 0 && (!labels || !boxes)) || (rows > 0 && (!uniform || !q_label || !q_bbox || !noised_label)) ||
+        (T > 0 && !attn_mask))
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    const int64_t row_blocks = (rows + msda::kDnRows - 1) / msda::kDnRows;
+    const int64_t mask_blocks = (T * T + msda::kDnMaskBytes - 1) / msda::kDnMaskBytes;
+    if (T >= ((int64_t)1 << 31) || rows >= ((int64_t)1 << 31) || rows * D >= ((int64_t)1 << 40) || (int64_t)V * D >= ((int64_t)1 << 40) ||
+        row_blocks + mask_blocks >= ((int64_t)1 << 31))
+        return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
+    if (!msda::aligned(16, {boxes, table, q_label, q_bbox, noised_box, attn_mask}) || !msda::aligned(8, {cum, labels, noised_label, meta}) ||
+        !msda::aligned(4, {uniform}))
+        return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
+    msda::DnParams p = {};
+    p.N = N, p.pad_cap = pad_cap, p.D = D, p.V = V, p.num_classes = num_classes, p.num_queries = num_queries, p.dn_number = dn_number;
+    p.use_cdn = use_cdn, p.add_gt = add_gt, p.target_cap = target_cap;
+    p.label_thr = label_noise_ratio * 0.5f, p.box_noise_scale = box_noise_scale, p.row_blocks = (int)row_blocks;
+    const int64_t grid = std::max<int64_t>(row_blocks + mask_blocks, 1);      // (the first workgroup also writes meta)
+    hipLaunchKernelGGL(msda::dn_queries_kernel, dim3((unsigned)grid), dim3(msda::kDnThreads), 0, static_cast<hipStream_t>(stream), p, cum, labels,
+                       boxes, uniform, table, q_label, q_bbox, noised_label, noised_box, attn_mask, meta);
+    return msda::launched(__func__);
+}
+
+/* The embedding table's gradient of the call above: grad_table (V, D) <- per class the sum, in row order, of the rows of grad_q_label
+ * (rows, D) whose noised_label is that class; every row of grad_table is written, zeros where no slot hits.  No atomic. */
+int msda_dn_queries_backward_f32(const float *grad_q_label, const int64_t *noised_label, int64_t rows, int D, int V, float *grad_table,
+                                 msda_stream_t stream)
+{
+    if (rows < 0 || D < 4 || D % 4 != 0 || V < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
+    if (!grad_table || (rows > 0 && (!grad_q_label || !noised_label))) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    if (rows * D >= ((int64_t)1 << 40) || (int64_t)V * D >= ((int64_t)1 << 40)) return msda::arg_fail(MSDA_ERR_TOO_LARGE, __func__);
+    if (!msda::aligned(16, {grad_q_label, grad_table}) || !msda::aligned(8, {noised_label})) return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
+    const int per = msda::kDnThreads / 64;
+    hipLaunchKernelGGL(msda::dn_queries_backward_kernel, dim3((unsigned)((V + per - 1) / per)), dim3(msda::kDnThreads), 0,
+                       static_cast<hipStream_t>(stream), grad_q_label, noised_label, (long long)rows, D, V, grad_table);
     return msda::launched(__func__);
 }
 
