@@ -65,6 +65,13 @@ def ffn_ln_backward_bf16(grad_out, yhat, rstd, ln_weight):
     return dz, sums[0], sums[1], sums[2]
 
 
+def relu_input_grad(grad_h, h):
+    """Gradient at a ReLU's input from the gradient at its output ``h``, op by op, with the rule of lin256's mask epilogue: kept where
+    ``h > 0``, else exactly zero.  (``aten.threshold_backward`` keeps the gradient where ``h`` is NaN -- it zeroes where ``h <= 0`` --
+    so the two branches of :class:`FusedFFNFunction`'s backward disagreed there.)"""
+    return torch.where(h > 0, grad_h, torch.zeros((), dtype=grad_h.dtype, device=grad_h.device))
+
+
 class FusedFFNFunction(Function):
     """apply(x, w1, b1, w2, b2, ln_weight, ln_bias, eps): x, w1, w2 bf16; the rest float32."""
 
@@ -91,7 +98,7 @@ class FusedFFNFunction(Function):
         else:
             h = torch.relu(torch.addmm(b1.to(torch.bfloat16), x2, w1.t()))
             grad_w2 = linear_wgrad(dz, h, False)[0].to(w2.dtype)
-            gh = torch.ops.aten.threshold_backward(dz @ w2, h, 0)
+            gh = relu_input_grad(dz @ w2, h)
         grad_w1, grad_b1 = linear_wgrad(gh, x2, True)
         grad_w1 = grad_w1.to(w1.dtype)
         grad_x = torch.addmm(dz, gh, w1).view(x.shape)                          # residual + first product's input gradient

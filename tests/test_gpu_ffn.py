@@ -82,13 +82,20 @@ def test_bad_arguments_are_rejected():
         ffn_forward_bf16(x.cpu(), w1.cpu(), b1.cpu(), w2.cpu(), b2.cpu(), gw.cpu(), gb.cpu())
 
 
-def test_function_gradients_match_fp32_autograd():
-    """FusedFFNFunction (fused forward, recomputing GEMM backward in bf16) against fp32 autograd of the op-by-op block."""
-    x, w1, b1, w2, b2, gw, gb = make(512, 256, seed=3)
+@pytest.mark.parametrize("T,Fh", [(512, 256), (193, 96), (385, 64), (193, 2048)])
+def test_function_gradients_match_fp32_autograd(T, Fh, monkeypatch):
+    """FusedFFNFunction (fused forward, recomputing GEMM backward in bf16) against fp32 autograd of the op-by-op block; d_ffn % 64 != 0
+    takes the backward's op-by-op branch, every other width lin256 (twice: the hidden activation and the gradient at the ReLU's input)."""
+    from richsem_amd.functions import ffn as ffn_mod
+    calls = []
+    real = ffn_mod.lin256
+    monkeypatch.setattr(ffn_mod, "lin256", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    x, w1, b1, w2, b2, gw, gb = make(T, Fh, seed=3)
     leaves = [t.clone().requires_grad_(True) for t in (x, w1, b1, w2, b2, gw, gb)]
     out = FusedFFNFunction.apply(*leaves, 1e-5)
-    go = torch.randn(512, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9)).to(torch.bfloat16)
+    go = torch.randn(T, D, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9)).to(torch.bfloat16)
     out.backward(go)
+    assert len(calls) == (2 if Fh % 64 == 0 else 0), (Fh, len(calls))
     refl = [t.float().clone().requires_grad_(True) for t in (x, w1, b1, w2, b2, gw, gb)]
     ref_fp32(*refl).backward(go.float())
     for a, b, name in zip(leaves, refl, ("x", "w1", "b1", "w2", "b2", "ln_w", "ln_b")):
