@@ -559,8 +559,11 @@ int msda_conv_dgrad_ws_bf16(const uint16_t *dy, const uint16_t *packed_weight_t,
                             int stride, int pad, int H, int W, uint16_t *dx, void *workspace, msda_stream_t stream);
 /* ... with the element-wise work that follows an input gradient in a residual network in its epilogue: dx = mask(conv_dgrad(dy) + add).
  * add (N, H, W, Cin) bf16 or NULL: a second gradient of the same tensor (the identity branch of a bottleneck); relu_out (N, H, W, Cin)
- * bf16 or NULL: the tensor whose gradient this is, when it is the output of a ReLU -- dx is zeroed where it is not positive, i.e. dx is
- * the gradient at that ReLU's INPUT (what aten::threshold_backward would make of it in a pass of its own). */
+ * bf16 or NULL: the tensor whose gradient this is, when it is the output of a ReLU -- dx is the gradient at that ReLU's INPUT: an element
+ * is kept iff relu_out > 0 and is +0 otherwise.  The comparison is made on the bits: kept iff the bf16, read as a signed 16-bit integer,
+ * is > 0.  For every non-NaN value (+-0, subnormals, +-inf included) that is relu_out > 0 and what aten::threshold_backward(dx, relu_out, 0)
+ * gives; a NaN keeps the element when its sign bit is clear and zeroes it when set, where aten::threshold_backward keeps both
+ * (msda_conv_forward_bf16's ReLU is fmaxf(y, 0), which never returns NaN, so a ReLU output of this library holds none). */
 int msda_conv_dgrad_fused_bf16(const uint16_t *dy, const uint16_t *packed_weight_t, int N, int Ho, int Wo, int Cout, int Cin, int KH, int KW,
                                int stride, int pad, int H, int W, const uint16_t *add, const uint16_t *relu_out, uint16_t *dx,
                                void *workspace, msda_stream_t stream);

@@ -66,10 +66,15 @@ def test_conv_against_fp32_definition(case, epilogue):
 
 @pytest.mark.parametrize("co_tiles,pixel_tiles", [(1, 1), (2, 3), (4, 2), (8, 1), (16, 3), (16, 1), (8, 2)])
 def test_every_tile_shape_gives_the_same_result(co_tiles, pixel_tiles):
+    """C_out = 256 (groups of four row tiles) takes CO_TILES 4, 8 and 16 only; 1 needs single-tile groups (C_out = 48), 2 groups of two (96):
+    the host keeps the automatic tile, silently, where a forced one does not fit"""
+    from conv_ref import forced_tile_is_taken
     from richsem_amd.conv import ConvAffine, set_tiling, to_nhwc_bf16
     torch.manual_seed(5)
+    Cout = {1: 48, 2: 96}.get(co_tiles, 256)
+    assert forced_tile_is_taken(Cout, co_tiles)
     x = torch.randn(2, 64, 19, 23).to(torch.bfloat16)
-    w = (torch.randn(256, 64, 3, 3) * 576 ** -0.5).to(torch.bfloat16).float()
+    w = (torch.randn(Cout, 64, 3, 3) * 576 ** -0.5).to(torch.bfloat16).float()
     ref = torch.relu(F.conv2d(x.float(), w, stride=1, padding=1))
     conv = ConvAffine(w.cuda(), None, None, 1, 1, relu=True)
     try:
@@ -90,6 +95,7 @@ RING_CASES = [  # N, H, W, Cin, Cout, k, stride, pad: C_in % 64 == 0 (the ring k
     (1, 50, 84, 1024, 256, 1, 1, 0),
     (1, 13, 21, 512, 512, 3, 1, 1),
     (1, 5, 7, 2048, 512, 1, 1, 0),
+    (2, 13, 17, 128, 96, 3, 1, 1),       # C_out = 96: groups of two row tiles, the only kind that takes CO_TILES = 2
 ]
 
 
@@ -97,6 +103,7 @@ RING_CASES = [  # N, H, W, Cin, Cout, k, stride, pad: C_in % 64 == 0 (the ring k
 @pytest.mark.parametrize("slots", [3, 4, 6])
 def test_ring_kernel_is_bit_identical_to_the_register_staged_kernel(case, slots):
     """conv_ring_kernel (both operands prefetched through LDS rings by LDS DMA) takes the products in conv_fwd_kernel's order: the same bits"""
+    from conv_ref import forced_tile_is_taken
     from richsem_amd.conv import ConvAffine, set_ring, set_tiling, to_nhwc_bf16
     N, H, W, Cin, Cout, k, stride, pad = case
     torch.manual_seed(hash(case) % 1000)
@@ -105,9 +112,13 @@ def test_ring_kernel_is_bit_identical_to_the_register_staged_kernel(case, slots)
     conv = ConvAffine(w, (1 + 0.3 * torch.randn(Cout)).cuda(), torch.randn(Cout).cuda(), stride, pad, relu=True)
     Ho, Wo = conv.out_hw(H, W)
     res = torch.randn(N, Ho, Wo, Cout, device="cuda").to(torch.bfloat16)
+    forced = 0
     for ct, pt in ((0, 0), (2, 1), (4, 2), (8, 1), (16, 2)):
         if ct and (Cout // 16) % ct:
             continue
+        # (a tile the host does not take for this C_out runs the automatic tile without the k split: still a bit-identity check, but
+        # not of the tile named -- at least one tile of every case must be taken, and (2, 1) is at C_out = 32 and 96)
+        forced += ct > 0 and forced_tile_is_taken(Cout, ct)
         try:
             set_tiling(ct, pt)
             set_ring(-1)
@@ -121,6 +132,7 @@ def test_ring_kernel_is_bit_identical_to_the_register_staged_kernel(case, slots)
             assert torch.equal(got, want), (ct, pt, float((got.float() - want.float()).abs().max()))
         else:      # (the automatic choice may split k over workgroups that add their sums with atomics: the order of that sum is not fixed)
             assert float(((got.float() - want.float()).abs() / (want.float().abs() + 1.0)).max()) < 2 ** -7
+    assert forced >= 1 and (Cout not in (32, 96) or forced_tile_is_taken(Cout, 2))
 
 
 @pytest.mark.parametrize("case", [(2, 15, 14, 256, 128, 3, 2, 1), (2, 13, 17, 64, 64, 3, 1, 1), (1, 7, 9, 512, 256, 1, 2, 0), (2, 9, 11, 128, 512, 1, 1, 0),
