@@ -409,6 +409,47 @@ int msda_box_pair_loss_f32(const float *pred, const float *target, const float *
                            msda_stream_t stream);
 int msda_focal_pos_sum_f32(const float *x, const float *weight, int K, float alpha, float *loss, float *grad_x, msda_stream_t stream);
 
+/* ---- the criterion's pair terms over CAPACITY buffers (csrc/msda_criterion.h; reference SetCriterion.forward, models/richsem/richsem.py:
+ * 1124-1298 with prep_for_dn :1300-1306): which pairs carry a loss is read ON THE DEVICE, so a captured launch serves every batch that fits
+ * the capacities.  The two per-pair formulas are those of the two entry points above.
+ *   logits (nl, N, pad_cap + Q, C), coords (nl, N, pad_cap + Q, 4)   the nl decoder outputs: pad_cap denoising rows, then Q matching rows
+ *   il (N, Qi, C), ib (N, Qi, 4)                                     the two-stage output
+ *   cum (N + 1) int64             exclusive prefix of the per-image target counts; cum[N] <= capacity targets are live
+ *   tgt_ids (capacity) int64, tgt_boxes (capacity, 4) cxcywh        rows past cum[N] are not read
+ *   query_of_target (nl + 1, capacity) int64                        as msda_lsap_* writes it for the nl + 1 outputs; columns past cum[N] are not read
+ *   dn_meta int64[5] or NULL      (single_pad, num_dn_group, pad_size, total, overflow) of msda_dn_queries_f32; NULL: no denoising part
+ *   num_boxes float[1] or NULL    the normaliser; NULL: max(1, live pairs of the last decoder output), counted in the kernel
+ * Matched slot (o, t): live iff t < cum[N] and 0 <= q = query_of_target[o][t] < Q (Qi for o == nl); prediction row pad_cap + q of the target's
+ * image; weight 1 / num_boxes.  Denoising slot (l, b, s), s < pad_cap: stride = pad_size / num_dn_group; live iff overflow == 0, s < pad_size and
+ * j = s % stride < T_b; target cum[b] + j; prediction row s; weight 1 / (num_boxes * num_dn_group).  Weights are formed in float64 and rounded once.
+ * Outputs:
+ *   row_weight (nl, N, pad_cap + Q), row_weight_int (N, Qi)   the row_weight of msda_focal_neg_*: denoising rows below pad_size 1 / (num_boxes *
+ *                                 num_dn_group), rows in [pad_size, pad_cap) 0 (all of them 0 on overflow or without dn_meta), matching rows 1 / num_boxes
+ *   terms (2 nl + 1, 3) f32       per get_loss call -- the matching part of layers 0..nl-1, their denoising parts, the two-stage output -- the sums
+ *                                 of (the positive entries' focal correction, |p - t|_1, 1 - GIoU), each divided by the call's normaliser
+ *   status int32[4]               [0] the denoising layout does not fit (overflow set, pad_size > pad_cap or not a multiple of num_dn_group): the
+ *                                 denoising part is left out; [1] live targets without a query (-1, or outside the output's queries), over the
+ *                                 nl + 1 outputs; [2] live targets with a label outside [0, C): their pairs are left out, nothing is read through
+ *                                 the label; [3] cum does not start at 0, decreases or exceeds capacity: every pair is left out
+ *   workspace                     msda_criterion_workspace_bytes() bytes, 16-byte aligned: the backward's per-slot records and the partial sums;
+ *                                 contents irrelevant on entry, every byte the backward reads is written by this call
+ * Sums: wave shuffles, one float64 partial per workgroup, added in workgroup order by a second small launch: no floating-point atomic, results
+ * are bitwise reproducible.  No host synchronisation, no allocation: capturable.
+ * msda_criterion_pairs_backward_f32 (after msda_criterion_pairs_f32 on the same workspace and cum): grad_coords (nl, N, pad_cap + Q, 4) and
+ * grad_ib (N, Qi, 4) <- gscale[0] * d(c_l1 * L1 + c_giou * (1 - GIoU) terms) / d box, written whole (zero where no pair points);
+ * grad_logits / grad_il += gscale[0] * c_cls * d(focal correction) / d logit at the positive entries -- ADDED to what msda_focal_neg_grad_f32
+ * wrote there before on the same stream; every entry is touched by one slot, no atomic.
+ * Limits: N <= 1024, capacity < 2^24, rows and slots below 2^31 (MSDA_ERR_TOO_LARGE); nl, N, Q, Qi, C, capacity >= 1, pad_cap >= 0
+ * (MSDA_ERR_BAD_DIMS); boxes, box gradients and workspace 16-byte aligned, int64 inputs 8 (MSDA_ERR_MISALIGNED). */
+int msda_criterion_workspace_bytes(int nl, int N, int Q, int Qi, int64_t capacity, int pad_cap, int64_t *bytes);
+int msda_criterion_pairs_f32(const float *logits, const float *coords, const float *il, const float *ib, const int64_t *cum, const int64_t *tgt_ids,
+                             const float *tgt_boxes, const int64_t *query_of_target, const int64_t *dn_meta, const float *num_boxes, int nl, int N,
+                             int Q, int Qi, int C, int64_t capacity, int pad_cap, float alpha, float c_cls, float c_l1, float c_giou,
+                             float *row_weight, float *row_weight_int, float *terms, int32_t *status, void *workspace, msda_stream_t stream);
+int msda_criterion_pairs_backward_f32(const void *workspace, const int64_t *cum, const float *gscale, int nl, int N, int Q, int Qi, int C,
+                                      int64_t capacity, int pad_cap, float *grad_logits, float *grad_il, float *grad_coords, float *grad_ib,
+                                      msda_stream_t stream);
+
 /* ---- integer part of the contrastive-denoising set-up (reference
  * models/richsem/dn_components.py:42-71, 131-179): bit-exact int64 / bool results ---------------------------------
  * msda_dn_indices_i64: cum = exclusive prefix of the per-image box counts (batch + 1 int64 on the device), total = cum[batch],
@@ -630,8 +671,9 @@ int msda_attnpool_core_f64(const double *u, const double *feat, const double *po
  * for query q of image b against target t of THE SAME image only (the blocks the reference keeps, matcher.py:76-77), with the
  * reference's arithmetic in the reference's order.  logits (B, Q, C); boxes (B, Q, 4) cxcywh; tgt_ids (n_targets) int64;
  * tgt_boxes (n_targets, 4) cxcywh; tgt_offsets (B + 1) int64 ON THE DEVICE = exclusive prefix of the per-image target counts
- * (tgt_offsets[B] == n_targets).  cost: Q * n_targets elements; image b's (Q x T_b) row-major block starts at element
- * Q * tgt_offsets[b].  Several decoder outputs are matched by calling this once per output into consecutive slices of one buffer
+ * (tgt_offsets[B] <= n_targets: n_targets is the CAPACITY of tgt_ids / tgt_boxes / cost, of which the first tgt_offsets[B] targets are
+ * live; the kernel writes Q * tgt_offsets[B] elements and neither reads the target rows nor writes the cost elements past them).
+ * cost: Q * n_targets elements; image b's (Q x T_b) row-major block starts at element Q * tgt_offsets[b].  Several decoder outputs are matched by calling this once per output into consecutive slices of one buffer
  * and copying that buffer to the host once.  A label outside [0, C) gives NaN in its column. */
 int msda_matcher_cost_f32(const float *logits, const float *boxes, const int64_t *tgt_ids, const float *tgt_boxes,
                           const int64_t *tgt_offsets, int B, int Q, int C, int64_t n_targets, double w_class, double w_bbox,
@@ -654,9 +696,10 @@ int msda_matcher_cost_tm_f64(const double *logits, const double *boxes, const in
  * as in Crouse 2016, the algorithm of scipy's rectangular_lsap), float64 arithmetic whatever the cost type, one wave per block.
  *   cost             n_out consecutive buffers of Q * n_targets elements, each as msda_matcher_cost_* (target_major = 0) or
  *                    msda_matcher_cost_tm_* (target_major = 1) writes it: image b's Q x T_b block at element Q * tgt_offsets[b]
- *   tgt_offsets      (B + 1) int64 ON THE DEVICE, tgt_offsets[B] == n_targets.  The block sizes are read from it by the kernel: the
- *                    launch depends on n_out, B, Q and n_targets only, so a captured launch stays valid when the per-image counts change
- *                    under the same total
+ *   tgt_offsets      (B + 1) int64 ON THE DEVICE, tgt_offsets[B] <= n_targets (n_targets is the capacity of a cost buffer and of a row
+ *                    of query_of_target).  The block sizes are read from it by the kernel: the launch depends on n_out, B, Q and n_targets
+ *                    only, so a captured launch stays valid when the per-image counts AND their total change under the same capacity;
+ *                    query_of_target[o][t] for t >= tgt_offsets[B] is not written
  *   query_of_target  (n_out, n_targets) int64: the query assigned to target t of output o, -1 for a target left without one (T_b > Q:
  *                    exactly Q targets of the block are assigned) and for every target of a block that was not solved
  *   status           (n_out, B) int32: 0 solved; 1 the block holds a non-finite cost (found by a scan before the solve; scipy raises

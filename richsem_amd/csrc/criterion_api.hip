@@ -1,0 +1,89 @@
+// criterion_api.hip -- the C ABI of the criterion over capacity buffers (csrc/msda_criterion.h; include/richsem_msda.h for the contract):
+// msda_criterion_workspace_bytes, msda_criterion_pairs_f32, msda_criterion_pairs_backward_f32.  A translation unit of its own.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "msda_host.h"
+#include "msda_criterion.h"
+
+extern "C" {
+
+/* ---- the criterion over capacity buffers (csrc/msda_criterion.h; include/richsem_msda.h for the contract) ------------------------------- */
+static int criterion_dims(int nl, int N, int Q, int Qi, int C, int64_t capacity, int pad_cap)
+{
+    if (nl < 1 || N < 1 || N > msda::kCritMaxImages || Q < 1 || Qi < 1 || C < 1 || capacity < 1 || pad_cap < 0) return MSDA_ERR_BAD_DIMS;
+    // rows and slots are counted in 32 bits
+    const int64_t lim = (int64_t)1 << 31;
+    if (capacity >= ((int64_t)1 << 24) || (int64_t)nl * N * ((int64_t)pad_cap + Q) >= lim || (int64_t)N * Qi >= lim ||
+        (int64_t)(nl + 1) * capacity + (int64_t)nl * N * pad_cap >= lim)
+        return MSDA_ERR_TOO_LARGE;
+    return MSDA_OK;
+}
+int msda_criterion_workspace_bytes(int nl, int N, int Q, int Qi, int64_t capacity, int pad_cap, int64_t *bytes)
+{
+    if (!bytes) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    const int rc = criterion_dims(nl, N, Q, Qi, 1, capacity, pad_cap);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
+    *bytes = (int64_t)msda::crit_layout(nl, N, Q, Qi, capacity, pad_cap).bytes;
+    return MSDA_OK;
+}
+int msda_criterion_pairs_f32(const float *logits, const float *coords, const float *il, const float *ib, const int64_t *cum, const int64_t *tgt_ids,
+                             const float *tgt_boxes, const int64_t *query_of_target, const int64_t *dn_meta, const float *num_boxes, int nl, int N,
+                             int Q, int Qi, int C, int64_t capacity, int pad_cap, float alpha, float c_cls, float c_l1, float c_giou,
+                             float *row_weight, float *row_weight_int, float *terms, int32_t *status, void *workspace, msda_stream_t stream)
+{
+    if (!logits || !coords || !il || !ib || !cum || !tgt_ids || !tgt_boxes || !query_of_target || !row_weight || !row_weight_int || !terms ||
+        !status || !workspace)
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    const int rc = criterion_dims(nl, N, Q, Qi, C, capacity, pad_cap);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
+    if (!msda::aligned(16, {coords, ib, tgt_boxes, workspace}) || !msda::aligned(8, {cum, tgt_ids, query_of_target, dn_meta}) ||
+        !msda::aligned(4, {logits, il, num_boxes, row_weight, row_weight_int, terms, status}))
+        return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
+    const msda::CritLayout L = msda::crit_layout(nl, N, Q, Qi, capacity, pad_cap);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    msda::CritArgs a;
+    a.logits = logits; a.coords = coords; a.il = il; a.ib = ib;
+    a.cum = cum; a.tgt_ids = tgt_ids; a.tgt_boxes = tgt_boxes; a.qot = query_of_target; a.meta = dn_meta; a.num_boxes_in = num_boxes;
+    a.nl = nl; a.N = N; a.Q = Q; a.Qi = Qi; a.C = C; a.pad_cap = pad_cap; a.cap = capacity;
+    a.alpha = alpha; a.c_cls = c_cls; a.c_l1 = c_l1; a.c_giou = c_giou;
+    a.row_weight = row_weight; a.row_weight_int = row_weight_int;
+    a.rec_gb = reinterpret_cast<float4 *>(ws + L.off_gb);
+    a.rec_gx = reinterpret_cast<float *>(ws + L.off_gx);
+    a.rec_row = reinterpret_cast<int32_t *>(ws + L.off_row);
+    a.rec_label = reinterpret_cast<int32_t *>(ws + L.off_label);
+    a.partial = reinterpret_cast<double *>(ws + L.off_partial);
+    a.stat = reinterpret_cast<int32_t *>(ws + L.off_stat);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(msda::criterion_pairs_kernel, dim3(L.grid_pairs + L.blocks_r), dim3(msda::kCritThreads), 0, st, a, L);
+    hipLaunchKernelGGL(msda::criterion_reduce_kernel, dim3(1), dim3(64), 0, st, (const double *)a.partial, (const int32_t *)a.stat, nl, L, terms, status);
+    return msda::launched(__func__);
+}
+int msda_criterion_pairs_backward_f32(const void *workspace, const int64_t *cum, const float *gscale, int nl, int N, int Q, int Qi, int C,
+                                      int64_t capacity, int pad_cap, float *grad_logits, float *grad_il, float *grad_coords, float *grad_ib,
+                                      msda_stream_t stream)
+{
+    if (!workspace || !cum || !gscale || !grad_logits || !grad_il || !grad_coords || !grad_ib) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
+    const int rc = criterion_dims(nl, N, Q, Qi, C, capacity, pad_cap);
+    if (rc != MSDA_OK) return msda::arg_fail(rc, __func__);
+    if (!msda::aligned(16, {workspace, grad_coords, grad_ib}) || !msda::aligned(8, {cum}) || !msda::aligned(4, {gscale, grad_logits, grad_il}))
+        return msda::arg_fail(MSDA_ERR_MISALIGNED, __func__);
+    const msda::CritLayout L = msda::crit_layout(nl, N, Q, Qi, capacity, pad_cap);
+    const unsigned char *ws = static_cast<const unsigned char *>(workspace);
+    msda::CritBackArgs a;
+    a.rec_gb = reinterpret_cast<const float4 *>(ws + L.off_gb);
+    a.rec_gx = reinterpret_cast<const float *>(ws + L.off_gx);
+    a.rec_row = reinterpret_cast<const int32_t *>(ws + L.off_row);
+    a.rec_label = reinterpret_cast<const int32_t *>(ws + L.off_label);
+    a.cum = cum; a.gscale = gscale;
+    a.nl = nl; a.N = N; a.Q = Q; a.Qi = Qi; a.C = C; a.pad_cap = pad_cap; a.cap = capacity;
+    a.grad_logits = grad_logits; a.grad_il = grad_il;
+    a.grad_coords = reinterpret_cast<float4 *>(grad_coords);
+    a.grad_ib = reinterpret_cast<float4 *>(grad_ib);
+    const int grid = (nl + 1) * N + (int)((L.slots_d + msda::kCritThreads - 1) / msda::kCritThreads);
+    hipLaunchKernelGGL(msda::criterion_pairs_backward_kernel, dim3(grid), dim3(msda::kCritThreads), 0, static_cast<hipStream_t>(stream), a, L);
+    return msda::launched(__func__);
+}
+
+}  // extern "C"

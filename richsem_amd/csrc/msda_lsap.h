@@ -44,7 +44,8 @@ __device__ __forceinline__ double lsap_wave_min(double x)
 
 // cost: n_out x (Q * Ttot) elements, output o's blocks as msda_matcher_cost_* lays them (image b's block at Q * tgt_offsets[b]), each
 // block query-major (entry (q, t) at q * T_b + t) or, target_major != 0, target-major (t * Q + q).  cols_cap / rows_cap: what the LDS
-// was sized for (the host knows Q and Ttot only).
+// was sized for (the host knows Q and Ttot only).  Ttot is a capacity: with tgt_offsets[B] < Ttot the columns of query_of_target past
+// tgt_offsets[B] are not written and the cost elements past Q * tgt_offsets[B] are not read.
 template <typename T>
 __global__ __launch_bounds__(64) void lsap_kernel(const T *__restrict__ cost, int target_major, const int64_t *__restrict__ tgt_offsets, int B,
                                                   int Q, int64_t Ttot, int cols_cap, int rows_cap, int64_t *__restrict__ query_of_target,

@@ -35,7 +35,8 @@ template <>
 __device__ __forceinline__ double matcher_exp<double>(double x) { return exp(x); }
 
 // logits (B, Q, C); boxes (B, Q, 4) cxcywh; tgt_ids (Ttot) int64; tgt_boxes (Ttot, 4) cxcywh; tgt_offsets (B + 1) int64 prefix
-// of the per-image target counts; cost: Q * Ttot elements.  A label outside [0, C) gives NaN in its column (the reference
+// of the per-image target counts; cost: Q * Ttot elements, Ttot >= tgt_offsets[B] the buffers' capacity: Q * tgt_offsets[B] elements are
+// written, the target rows and cost elements past them are left alone.  A label outside [0, C) gives NaN in its column (the reference
 // raises an index error there).  TM: the same entries with every block stored target-major (entry (q, t) at t * Q + q inside the block), the
 // layout the on-device solver (msda_lsap.h) scans with unit stride; the arithmetic per entry is the same.
 template <typename T, bool TM = false>

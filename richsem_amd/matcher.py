@@ -72,6 +72,57 @@ class CostPlan:
         return self
 
 
+class TargetBuffers:
+    """The capacity form of :class:`CostPlan`: device buffers for ``n_images`` images and up to ``capacity`` targets in all, filled by
+    :meth:`update_`.  ``total`` is the CAPACITY -- the size every launch that takes this plan is shaped by --; how many targets are live
+    is ``offsets_dev[-1]``, which the kernels read on the device (``msda_matcher_cost_*`` writes ``nq * offsets_dev[-1]`` cost elements,
+    ``msda_lsap_*`` the first ``offsets_dev[-1]`` columns of ``query_of_target``, ``msda_criterion_pairs_f32`` reads no further).  So a
+    graph captured with these buffers serves any batch that fits them, whatever its per-image counts and their total.  Rows past the
+    live targets hold label 0 and box (0.5, 0.5, 1, 1).  ``cost_blocks``, ``solve_blocks`` and ``match_many_device`` take it as a plan."""
+
+    def __init__(self, n_images, capacity, device, dtype=torch.float32, max_per_image=None):
+        n_images, capacity = int(n_images), int(capacity)
+        if n_images < 1 or capacity < 1:
+            raise ValueError(f"TargetBuffers: n_images and capacity must be >= 1, got {n_images} and {capacity}")
+        self.device, self.dtype = torch.device(device), dtype
+        self.num_queries = None
+        self.capacity = self.total = capacity
+        self.max_per_image = None if max_per_image is None else int(max_per_image)
+        self.sizes = [0] * n_images
+        self.offsets = [0] * (n_images + 1)
+        self.live = 0
+        self.offsets_dev = torch.zeros(n_images + 1, dtype=torch.int64, device=device)
+        self.tgt_ids = torch.zeros(capacity, dtype=torch.int64, device=device)
+        self.tgt_boxes = torch.tensor([0.5, 0.5, 1.0, 1.0], dtype=dtype).repeat(capacity, 1).to(device)
+
+    @torch.no_grad()
+    def update_(self, targets):
+        """write a batch -- a list over the images of dicts with "labels" (T_b) and "boxes" (T_b, 4) -- into the buffers: host -> device
+        copies on the current stream, between replays and not in a capture, as :meth:`CostPlan.update_`.  Another image count, more
+        targets than ``capacity``, or an image with more than ``max_per_image`` of them raise ValueError and leave the buffers alone."""
+        sizes = [int(v["boxes"].shape[0]) for v in targets]
+        if len(sizes) != len(self.sizes):
+            raise ValueError(f"TargetBuffers.update_: {len(sizes)} images, the buffers were built for {len(self.sizes)}")
+        if sum(sizes) > self.capacity:
+            raise ValueError(f"TargetBuffers.update_: {sum(sizes)} targets in all, the capacity is {self.capacity}")
+        if self.max_per_image is not None and max(sizes) > self.max_per_image:
+            raise ValueError(f"TargetBuffers.update_: an image with {max(sizes)} targets, at most {self.max_per_image} are allowed")
+        offsets = [0]
+        for n in sizes:
+            offsets.append(offsets[-1] + n)
+        live = offsets[-1]
+        ids = torch.zeros(self.capacity, dtype=torch.int64)
+        boxes = torch.tensor([0.5, 0.5, 1.0, 1.0], dtype=self.dtype).repeat(self.capacity, 1)
+        if live:
+            ids[:live] = torch.cat([v["labels"].detach().cpu().to(torch.int64).reshape(-1) for v in targets])
+            boxes[:live] = torch.cat([v["boxes"].detach().cpu().to(self.dtype).reshape(-1, 4) for v in targets])
+        self.sizes, self.offsets, self.live = sizes, offsets, live
+        self.offsets_dev.copy_(torch.tensor(offsets, dtype=torch.int64), non_blocking=True)
+        self.tgt_ids.copy_(ids, non_blocking=True)
+        self.tgt_boxes.copy_(boxes, non_blocking=True)
+        return self
+
+
 def cost_blocks(pred_logits, pred_boxes, plan, cost_class, cost_bbox, cost_giou, focal_alpha, out=None, target_major=False):
     """Diagonal cost blocks of one decoder output on the device: a flat tensor of nq * plan.total elements, image b's (nq x T_b)
     block starting at nq * plan.offsets[b].  ``out``: slice of a larger buffer to write into.  ``target_major``: every block stored
