@@ -450,6 +450,54 @@ int msda_criterion_pairs_backward_f32(const void *workspace, const int64_t *cum,
                                       int64_t capacity, int pad_cap, float *grad_logits, float *grad_il, float *grad_coords, float *grad_ib,
                                       msda_stream_t stream);
 
+/* ---- the distillation term over CAPACITY buffers (csrc/msda_roi_targets.h, csrc/msda_distill_pairs.h; reference models/richsem/richsem.py:
+ * 745-761 for the teacher's box targets, :967-1024 with :1158-1180 for the term): the teacher's ROI rows, the (student row, teacher row)
+ * pairs and the gradient's scatter, all shaped by the capacities and read ON THE DEVICE, so a captured launch serves every batch that fits.
+ *
+ * msda_roi_align_targets_f32: ROIAlign forward (aligned) of the target boxes.
+ *   input (N, C, H, W) f32; cum (N + 1) int64; tgt_boxes (capacity, 4) cxcywh normalised f32; sizes (N, 2) int32 (h, w) of the images
+ *   output (capacity, C, pooled_h, pooled_w) f32, every element written; status int32[4]: [3] = 1 when cum does not start at 0, decreases
+ *   or exceeds capacity (every slot is then dead), [0..2] = 0
+ * Slot t is live iff t < cum[N]; its image is the b with cum[b] <= t < cum[b + 1].  A dead slot is exact zeros and reads nothing through
+ * its box.  The pixel box (x1, y1, x2, y2) = (w_b (cx - 0.5 w), h_b (cy - 0.5 h), w_b (cx + 0.5 w), h_b (cy + 0.5 h)) is formed in float32
+ * with one rounding per operation and no contraction, as clip_box_targets forms it in torch; from there the algorithm of
+ * msda_roi_align_forward_f32.  A live slot whose pixel box is not finite, or whose sampling grid would exceed 4096 per axis, is zeros.
+ * Limits: N <= 1024, capacity < 2^24, the workgroup count capacity * ceil(C / 64) below 2^31 (MSDA_ERR_TOO_LARGE); N, C, H, W, capacity,
+ * pooled_h, pooled_w >= 1, sampling_ratio <= 4096 (<= 0: adaptive) (MSDA_ERR_BAD_DIMS); tgt_boxes 16-byte aligned, cum 8 (MSDA_ERR_MISALIGNED).
+ *
+ * msda_distill_pairs: ONE launch that writes, for K = n_d * capacity + n_d * N * pad_cap slots, the arguments msda_distill_kl_f32 / _bf16 /
+ * msda_distill_l1_f32 take -- those run unchanged over all K slots and skip the dead ones.  layer_mask: bit l set = decoder layer l is
+ * distilled (0 < layer_mask < 2^nl); n_d = its popcount; the student tensor is (n_d, N, pad_cap + Q, C), the selected layers stacked in
+ * increasing order.  cum, query_of_target (nl + 1, capacity), dn_meta, num_boxes: as for msda_criterion_pairs_f32.  objective 0 = 'gt', 1 = 'pred'.
+ *   matched slot k = i * capacity + t: live iff t < cum[N] and 0 <= q = query_of_target[layer_i][t] < Q; pred_row = (i N + b)(pad_cap + Q) +
+ *     pad_cap + q; tgt_row = t ('gt') or pred_row ('pred'); row_weight = 1 / num_boxes; row_group = i
+ *   denoising slot k = n_d * capacity + (i N + b) pad_cap + s: live iff overflow == 0, s < pad_size and j = s % (pad_size / num_dn_group) < T_b;
+ *     pred_row = (i N + b)(pad_cap + Q) + s; tgt_row = cum[b] + j or pred_row; row_weight = 1 / (num_boxes * num_dn_group); row_group = n_d + i
+ *   a dead slot: pred_row = tgt_row = -1, row_weight = 0
+ *   pred_row, tgt_row (K) int64; row_weight (K) f32 (formed in float64, rounded once); row_group (K) int32: the get_loss call of the slot,
+ *   for a class_mask (2 n_d, C); num_boxes NULL: max(1, live pairs of the LAST decoder output), counted in the kernel
+ *   status int32[4], the words of msda_criterion_pairs_f32: [0] the denoising layout does not fit, [1] live targets without a query over the
+ *   n_d selected layers, [2] = 0, [3] bad cum: every slot dead
+ * Integer results and single roundings: exact and reproducible.  No atomic, no workspace, no host synchronisation: capturable.
+ *
+ * msda_distill_scatter_f32 / _bf16 (the backward; after msda_distill_pairs and a row kernel on the same slots): grad_pred (n_d, N, pad_cap + Q,
+ * C) f32 / bf16 <- gscale[0] * grad_rows[k] at row pred_row[k] for every live slot, written WHOLE (zeros elsewhere) with plain stores; dead
+ * slots' gradient rows are not read.  The product is formed in float32 and, for bf16, rounded to nearest even once.  The assignment is
+ * one-to-one per image and output, as msda_lsap_* writes it; if query_of_target sends two live targets of an image to one query, which of
+ * their rows lands is unspecified.
+ * Limits of both: nl <= 63, N <= 1024, capacity < 2^24, rows and slots below 2^31 (MSDA_ERR_TOO_LARGE); nl, N, Q, C, capacity >= 1,
+ * pad_cap >= 0, layer_mask within (0, 2^nl) (MSDA_ERR_BAD_DIMS); objective not 0 / 1 (MSDA_ERR_BAD_OPTION); int64 arguments 8-byte aligned. */
+int msda_roi_align_targets_f32(const float *input, const int64_t *cum, const float *tgt_boxes, const int32_t *sizes, int N, int C, int H, int W,
+                               int64_t capacity, int pooled_h, int pooled_w, double spatial_scale, int sampling_ratio, float *output,
+                               int32_t *status, msda_stream_t stream);
+int msda_distill_pairs(const int64_t *cum, const int64_t *query_of_target, const int64_t *dn_meta, const float *num_boxes, int nl, int N, int Q,
+                       int pad_cap, int64_t capacity, int64_t layer_mask, int objective, int64_t *pred_row, int64_t *tgt_row, float *row_weight,
+                       int32_t *row_group, int32_t *status, msda_stream_t stream);
+int msda_distill_scatter_f32(const float *grad_rows, const int64_t *pred_row, const int64_t *cum, const float *gscale, int n_d, int N, int Q,
+                             int pad_cap, int64_t capacity, int C, float *grad_pred, msda_stream_t stream);
+int msda_distill_scatter_bf16(const float *grad_rows, const int64_t *pred_row, const int64_t *cum, const float *gscale, int n_d, int N, int Q,
+                              int pad_cap, int64_t capacity, int C, uint16_t *grad_pred, msda_stream_t stream);
+
 /* ---- integer part of the contrastive-denoising set-up (reference
  * models/richsem/dn_components.py:42-71, 131-179): bit-exact int64 / bool results ---------------------------------
  * msda_dn_indices_i64: cum = exclusive prefix of the per-image box counts (batch + 1 int64 on the device), total = cum[batch],

@@ -225,3 +225,152 @@ class DistillLoss:
         else:
             row_group = class_mask = None
         return DistillKL.apply(pred, tgt, pred_row, tgt_row, row_weight, row_group, class_mask, self.dynamic_weight)
+
+
+# ---- the term over CAPACITY buffers: pairs found on the device (csrc/msda_distill_pairs.h) ---------------------------------------------------
+
+def _capacity_checked(pred, teacher, targets, query_of_target, dn_meta, pad_cap, layers, distill_type, objective, class_mask, num_boxes):
+    """the argument checks of :func:`device_distill`: -> ``cfg`` = (nl, N, Q, pad_cap, capacity, C, layer_mask, n_d, kl, objective index)"""
+    if distill_type not in DISTILL_TYPES:
+        raise NotImplementedError(f"distill_type {distill_type!r}: one of {DISTILL_TYPES}")
+    if objective == "pred_all":
+        raise ValueError("device_distill: objective 'pred_all' pairs every query with the teacher's row for it -- no per-batch shape, nothing "
+                         "to find on the device: use DistillLoss('...', 'pred_all')")
+    if objective not in ("gt", "pred"):
+        raise NotImplementedError(f"clip_distill_objective {objective!r}: one of {OBJECTIVES}")
+    kl = distill_type == "clip_logits"
+    if pred.dtype not in ((torch.float32, torch.bfloat16) if kl else (torch.float32,)):
+        raise TypeError(f"device_distill: the student's tensor is float32{' or bfloat16' if kl else ''}, not {pred.dtype}")
+    if teacher.dtype != torch.float32:
+        raise TypeError("device_distill: the teacher's rows are float32")
+    if query_of_target.dtype != torch.int64 or targets.offsets_dev.dtype != torch.int64:
+        raise TypeError("device_distill: query_of_target and the target prefix are int64 tensors")
+    tensors = (pred, teacher, query_of_target, targets.offsets_dev)
+    if not all(t.is_cuda for t in tensors) or any(t is not None and not t.is_cuda for t in (dn_meta, num_boxes, class_mask)):
+        raise RuntimeError("Not implemented on the CPU")
+    pad_cap, cap = int(pad_cap), int(targets.total)
+    if pred.dim() != 4 or pad_cap < 0 or pred.shape[2] <= pad_cap or cap < 1:
+        raise ValueError("device_distill: pred is (n_d, N, pad_cap + Q, C) with Q >= 1, the target capacity >= 1")
+    n_d, N, QT, C = pred.shape
+    if query_of_target.dim() != 2 or query_of_target.shape[1] != cap or query_of_target.shape[0] < 2 or not query_of_target.is_contiguous():
+        raise ValueError(f"device_distill: query_of_target is a contiguous (nl + 1, {cap}) tensor: one row per output, one column per target slot")
+    nl = query_of_target.shape[0] - 1
+    layers = sorted(set(int(l) for l in layers))
+    if len(layers) != n_d or not layers or layers[0] < 0 or layers[-1] >= nl or nl > 63:
+        raise ValueError(f"device_distill: layers names {len(layers)} distinct decoder layers in 0..{nl - 1}, pred stacks {n_d}")
+    if targets.offsets_dev.numel() != N + 1:
+        raise ValueError("device_distill: the target buffers were built for another image count")
+    want = (cap, C) if objective == "gt" else tuple(pred.shape)
+    if tuple(teacher.shape) != want:
+        raise ValueError(f"device_distill: objective {objective!r} takes a teacher of shape {want}, not {tuple(teacher.shape)}")
+    if dn_meta is not None and (dn_meta.dtype != torch.int64 or dn_meta.numel() != 5 or not dn_meta.is_contiguous()):
+        raise TypeError("device_distill: dn_meta is the contiguous int64[5] meta of denoising_queries")
+    if num_boxes is not None and (num_boxes.dtype != torch.float32 or num_boxes.numel() != 1):
+        raise TypeError("device_distill: num_boxes is a (1,) float32 tensor")
+    if class_mask is not None:
+        if not kl:
+            raise ValueError("device_distill: class_mask (use_fed_on_kd) acts on the KL form only")
+        if class_mask.dtype != torch.float32 or tuple(class_mask.shape) != (2 * n_d, C):
+            raise ValueError(f"device_distill: class_mask is a float32 ({2 * n_d}, {C}) tensor: one class subset per get_loss call")
+    return nl, N, QT - pad_cap, pad_cap, cap, C, sum(1 << l for l in layers), n_d, kl, OBJECTIVES.index(objective)
+
+
+def distill_pairs(targets, query_of_target, dn_meta, num_boxes, cfg):
+    """the one call of ``msda_distill_pairs``: -> (pred_row (K) int64, tgt_row (K) int64, row_weight (K) float32, row_group (K) int32, status
+    int32[4]) for the K = n_d * capacity + n_d * N * pad_cap slots of ``cfg`` (:func:`_capacity_checked`)"""
+    nl, N, Q, pad_cap, cap, _, mask, n_d, _, obj = cfg
+    dev = query_of_target.device
+    K = n_d * (cap + N * pad_cap)
+    pred_row, tgt_row = torch.empty(K, dtype=torch.int64, device=dev), torch.empty(K, dtype=torch.int64, device=dev)
+    w, grp = torch.empty(K, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.int32, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.load().msda_distill_pairs(targets.offsets_dev.data_ptr(), query_of_target.data_ptr(), _ptr(dn_meta), _ptr(num_boxes), nl, N, Q,
+                                                  pad_cap, cap, mask, obj, pred_row.data_ptr(), tgt_row.data_ptr(), w.data_ptr(), grp.data_ptr(),
+                                                  status.data_ptr(), _lib.raw_stream(dev)))
+    return pred_row, tgt_row, w, grp, status
+
+
+def distill_capacity_forward(pred, teacher, targets, query_of_target, dn_meta, num_boxes, class_mask, dynamic_weight, cfg):
+    """the forward half on checked tensors: pairs launch + the existing row kernel -> (loss (1) float32, status, saved); ``saved`` is what
+    :func:`distill_capacity_backward` takes"""
+    kl, obj = cfg[8], cfg[9]
+    pred_row, tgt_row, w, grp, status = distill_pairs(targets, query_of_target, dn_meta, num_boxes, cfg)
+    x = pred.detach().contiguous()
+    if kl:
+        loss, grad_rows, _ = kl_rows(x, teacher, pred_row, tgt_row, w, grp if class_mask is not None else None, class_mask, dynamic_weight)
+    else:
+        loss, grad_rows, _ = l1_rows(x, teacher, pred_row, tgt_row, w, normalize_target=obj != 0)
+    return loss, status, (grad_rows, pred_row, targets.offsets_dev, cfg, pred.dtype)
+
+
+def distill_capacity_backward(saved, g):
+    """the backward half (``msda_distill_scatter_f32`` / ``_bf16``): ``g`` = d / d loss (a float32 device scalar) -> the gradient of ``pred``,
+    written whole by one launch"""
+    grad_rows, pred_row, cum, cfg, dtype = saved
+    _, N, Q, pad_cap, cap, C, _, n_d, _, _ = cfg
+    dev = grad_rows.device
+    gs = g.detach().reshape(1).float().contiguous()
+    gp = torch.empty((n_d, N, pad_cap + Q, C), dtype=dtype, device=dev)
+    fn = _lib.load().msda_distill_scatter_bf16 if dtype == torch.bfloat16 else _lib.load().msda_distill_scatter_f32
+    with _lib.on_device(dev):
+        _lib.check(fn(grad_rows.data_ptr(), pred_row.data_ptr(), cum.data_ptr(), gs.data_ptr(), n_d, N, Q, pad_cap, cap, C, gp.data_ptr(),
+                      _lib.raw_stream(dev)))
+    return gp
+
+
+class DeviceDistillFunction(torch.autograd.Function):
+    """:func:`device_distill` as one autograd node: gradient for ``pred`` only"""
+
+    @staticmethod
+    def forward(ctx, pred, teacher, targets, query_of_target, dn_meta, num_boxes, class_mask, dynamic_weight, cfg):
+        loss, status, saved = distill_capacity_forward(pred, teacher, targets, query_of_target, dn_meta, num_boxes, class_mask, dynamic_weight, cfg)
+        ctx.save_for_backward(*saved[:3])
+        ctx.rest = saved[3:]
+        ctx.mark_non_differentiable(status)
+        return loss[0], status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_status):
+        return (distill_capacity_backward(tuple(ctx.saved_tensors) + ctx.rest, g),) + (None,) * 8
+
+
+def device_distill(pred, teacher, targets, query_of_target, dn_meta=None, *, pad_cap, layers, distill_type, objective, dynamic_weight=False,
+                   class_mask=None, num_boxes=None, late_status=None):
+    """The distillation term of the criterion over all distilled outputs of a step, pairs found on the device: what
+    :meth:`DistillLoss.stacked` returns on the index rows of ``pairs_from_query_of_target`` and the denoising positives, without a tensor whose
+    shape follows the batch -- so ONE captured graph serves every batch that fits the capacities.  The caller adds it to
+    ``criterion.device_criterion``'s loss (times its coefficient).
+
+    ``pred`` (n_d, N, pad_cap + Q, C) float32 (KL: or bfloat16): the student's CLIP-space output of the ``n_d`` decoder layers ``layers``
+    names (distinct, stacked in increasing order), ``pad_cap`` denoising rows before the Q matching rows; ``teacher`` float32: for objective
+    'gt' (targets.total, C), the target slots' teacher rows (``clip_box_targets_capacity``: logits for 'clip_logits', prompts for 'clip_l1'),
+    for 'pred' the teacher's output for every query, shaped like ``pred``; ``targets``: a ``matcher.TargetBuffers`` (or ``CostPlan``);
+    ``query_of_target`` (nl + 1, targets.total) int64 and ``dn_meta``: as for ``device_criterion``; ``class_mask`` (2 n_d, C) float32: the
+    class subsets of ``use_fed_on_kd``, one per get_loss call -- the matching parts of the distilled layers, then their denoising parts;
+    ``num_boxes``: a (1,) float32 device tensor instead of the kernel's own count.  'pred_all' raises ValueError (:class:`DistillLoss`).
+
+    -> ``(loss, status)``: the 0-dim float32 sum over the 2 n_d calls, each normalised as the reference does (num_boxes, num_boxes *
+    num_dn_group); ``status`` int32[4] = ``criterion.STATUS`` (word 2 stays 0), pushed to ``late_status`` outside a capture.  Launches:
+    the pair kernel, the row kernel and its total; backward: one scatter that writes the gradient whole with plain stores.  Nothing waits,
+    no atomic, bitwise reproducible.  CPU tensors raise: there is no CPU fallback."""
+    cfg = _capacity_checked(pred, teacher, targets, query_of_target, dn_meta, pad_cap, layers, distill_type, objective, class_mask, num_boxes)
+    loss, status = DeviceDistillFunction.apply(pred, teacher.contiguous(), targets, query_of_target, dn_meta, num_boxes,
+                                               None if class_mask is None else class_mask.contiguous(), bool(dynamic_weight), cfg)
+    if late_status is not None and not torch.cuda.is_current_stream_capturing():
+        late_status.push(status.view(1, 4))
+    return loss, status
+
+
+@torch.no_grad()
+def device_distill_and_grads(pred, teacher, targets, query_of_target, dn_meta=None, *, pad_cap, layers, distill_type, objective,
+                             dynamic_weight=False, class_mask=None, num_boxes=None, grad_loss=None):
+    """:func:`device_distill` and its backward in one call, WITHOUT the autograd engine: -> (loss, status, grad_pred) for d / d loss =
+    ``grad_loss`` (a device scalar; default 1).  For a caller that schedules the backward itself -- a whole step captured into one graph on
+    the capturing thread (``criterion.device_criterion_and_grads``).  Same arguments, checks and launches."""
+    cfg = _capacity_checked(pred, teacher, targets, query_of_target, dn_meta, pad_cap, layers, distill_type, objective, class_mask, num_boxes)
+    loss, status, saved = distill_capacity_forward(pred, teacher.contiguous(), targets, query_of_target, dn_meta, num_boxes,
+                                                   None if class_mask is None else class_mask.contiguous(), bool(dynamic_weight), cfg)
+    g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
+    return loss[0], status, distill_capacity_backward(saved, g)

@@ -109,3 +109,22 @@ def clip_box_targets(clip_features, targets, attnpool, text_embed, logit_scale, 
     logits = (prompt @ te.t()) * torch.as_tensor(logit_scale, dtype=dt, device=dev).exp()
     sizes = [len(t["labels"]) for t in targets]
     return list(prompt.split(sizes, dim=0)), list(logits.split(sizes, dim=0))
+
+
+@torch.no_grad()
+def clip_box_targets_capacity(clip_features, targets, sizes, attnpool, text_embed, logit_scale, patch_size=32, grid_size=7):
+    """:func:`clip_box_targets` over CAPACITY buffers: ``targets`` is a ``matcher.TargetBuffers`` (or ``CostPlan``), ``sizes`` the (N, 2)
+    int32 (h, w) device tensor of ``geometry.sizes_from_targets``; clip_features (N, C, H/32, W/32) float32.  -> ``(prompt (capacity, D),
+    logits (capacity, classes))``: row t < ``targets.offsets_dev[-1]`` is the teacher's embedding / text logits of target t -- the rows
+    :func:`clip_box_targets` returns, concatenated --, the rows past the live targets are the pool of an all-zero map (finite, never read by
+    ``distill.device_distill``).  The attention pool runs over all ``capacity`` rows.  No host synchronisation, no shape that depends on the
+    counts: capturable after one eager call (``logit_scale`` a device tensor, as for :func:`clip_box_targets`)."""
+    from ..roi import roi_align_targets
+    dt, dev = clip_features.dtype, clip_features.device
+    roi_features = roi_align_targets(clip_features, targets, sizes, grid_size, 1.0 / patch_size, 0)
+    prompt = attnpool(roi_features)
+    prompt = prompt / prompt.norm(dim=-1, keepdim=True)
+    te = text_embed.to(dt)
+    te = te / te.norm(dim=-1, keepdim=True)
+    logits = (prompt @ te.t()) * torch.as_tensor(logit_scale, dtype=dt, device=dev).exp()
+    return prompt, logits
