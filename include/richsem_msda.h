@@ -104,7 +104,8 @@ const char *msda_last_error(void);
  *                     profiles/r02_locality.md).  0 = auto always takes the window forward kernel when it applies.  Setting
  *                     it forgets what was learnt.  "locality_share_ppm" (get only): last measured share in parts per
  *                     million, -1 = none.  (The backward needs no monitor.)
- *   "rps_tile"        routed backward: largest tile side + 1 (4..16, default 16: tile + one row / column <= 256 pixels)
+ *   "rps_tile"        routed backward: 4..15 = largest tile side + 1; 16 (default) = the planner's choice: rectangles of up to
+ *                     30 pixels a side, tile + one row / column <= 312 pixels
  *   "rps_max_chunks"  routed backward: chunks of 1536 points one workgroup takes before a tile's points are dealt over
  *                     several workgroups (default 12)
  *   "rps_route_wgs"   routed backward: workgroups per CU of the route pass (default 2: what is resident)

@@ -2,9 +2,10 @@
 //
 // The reference's backward (ms_deform_im2col_cuda.cuh:87-159, 301-403) is query-stationary: every bilinear corner of every
 // sampling point is ADDED to grad_value with a global float atomic -- 2.9 GB of atomics per encoder call, ~2.3 ms at the
-// chip's atomic rate.  Here the OUTPUT owns the work: grad_value is cut into tiles of <= 15x15 pixels per (image, head,
-// level) -- the tile plus one apron row / column is a grid of at most kRpsMaxPx = 256 pixels --, and a tile's workgroup pulls in
-// exactly the sampling points that land on it.
+// chip's atomic rate.  Here the OUTPUT owns the work: grad_value is cut into tiles per (image, head, level) -- rectangles of up
+// to 30 pixels a side whose grid, the tile plus one apron row / column, has at most kRpsMaxPx = 312 pixels (25 x 11 on the finest
+// level of the 800 x 1344 pyramid, the whole 13 x 21 map on its coarsest: plan_rps) --, and a tile's workgroup pulls in exactly
+// the sampling points that land on it.
 //
 //   route   (rps_route_kernel, ONE pass)  one lane per sampling point: where does its corner (h_low, w_low) fall?  The point is
 //           appended -- a 16-byte record: position code, bilinear fractions, attention weight -- to the bin of THAT tile only
@@ -30,6 +31,12 @@
 // Coarse levels whose tile is the whole map split their bin into slabs over several workgroups; those add their rows to
 // the (pre-zeroed) level with 128-B row atomics -- a few MB per call.  So do all tiles for their first row / column and their apron (the
 // pixels they share with their neighbours: 13 % of the rows).
+//
+// LDS of a tile workgroup (RpsLds, 160 KB): 416 B per grid pixel -- 36 f64 sums and the 128-B value row -- and 18 B per record of a
+// chunk -- the sorted entry and the arrival index -> slot map --, plus ~6 KB of tables (run table, list offsets, walk units).  The
+// records themselves are NOT kept: the gradient stage, which needs them in arrival order, reads them from the pool a second time
+// (24.5 KB that went into the tile grid: 256 -> 312 pixels, 120 -> 93 work items and 282 -> 249 chunks per (image, head) of the
+// 800 x 1344 pyramid).  Chunks of 2304 records with a grid of 278 pixels fit as well and measured slower (profiles/r21_rps_recut.md).
 #pragma once
 
 #include <algorithm>
@@ -42,7 +49,9 @@ namespace msda {
 
 constexpr int kRpsThreads = 768;               // 12 waves = 3 per SIMD, 168 registers per lane (1024 threads at 128 registers spilled; 512 threads: same speed)
 constexpr int kRpsWaves = kRpsThreads / 64;
-constexpr int kRpsMaxPx = 256;                  // pixel grid of a tile (tile + one row / column): bound by LDS (f64 sums + value rows)
+constexpr int kRpsMaxPx = 312;                  // pixel grid of a tile (tile + one row / column): bound by LDS (f64 sums + value rows, 416 B per pixel)
+constexpr int kRpsMaxSide = 31;                 // rows / columns of a tile's grid: the route pass's tables hold them in 5 bits
+constexpr int kRpsScanThreads = (kRpsMaxPx + 63) / 64 * 64, kRpsScanWaves = kRpsScanThreads / 64;   // whole waves scan the per-list counts, one list per lane
 constexpr int kRpsPpq = (kRpsMaxPx + kRpsThreads / 4 - 1) / (kRpsThreads / 4);   // pixels per quad where a quad stands for a pixel
 constexpr int kRpsRpl = 2;                      // records per lane and chunk
 constexpr int kRpsChunk = kRpsRpl * kRpsThreads;   // sampling points per chunk
@@ -59,7 +68,10 @@ constexpr int kRpsMaxRuns = 320;               // runs per bin the tile kernel c
 constexpr int kRpsRunSearch = 256;             // first step of the binary search over a bin's runs: the largest power of two below kRpsMaxRuns
 static_assert(kRpsRunSearch < kRpsMaxRuns && 2 * kRpsRunSearch >= kRpsMaxRuns, "run search");
 constexpr int kRpsQpBits = 19;                  // entry code: query * P + point below this bit (plan: Lq * P < 2^19)
-static_assert(kRpsMaxPx <= 256, "record code: the base-grid index has 8 bits (bits 19..26), the tile kernel masks it with 0xFF");
+constexpr int kRpsPxBits = 9;                   // ... then the base-grid index, then the four corner flags
+static_assert(kRpsMaxPx <= 1 << kRpsPxBits && kRpsQpBits + kRpsPxBits + 4 == 32, "record code: qp | base-grid index | corners");
+static_assert(kRpsMaxPx <= kRpsMaxSide * kRpsMaxSide && kRpsScanThreads <= kRpsThreads && kRpsScanWaves * 4 <= 32, "tile grid");
+static_assert(kRpsChunk < 1 << 16, "a list's length and a chunk's unit count share a 32-bit word in the scan; slot[] is 16 bits wide");
 
 struct RpsLevel {
     int H, W, start;
@@ -72,9 +84,8 @@ struct RpsLevel {
 };
 
 // Routed sampling point, as the route pass writes it and the tile kernel streams it.
-//   code = (query * P + point)  |  base-grid index in the tile << 19 (8 bits: < kRpsMaxPx)  |  corners inside the map << 27 (4 bits)  |  1 << 31
-// (bit 31: this tile forms the point's gradients -- every record since round 5, when a point stopped being sent to the neighbouring tiles
-// as well).  The bin fixes (image, head, level).
+//   code = (query * P + point)  |  base-grid index in the tile << 19 (9 bits: < kRpsMaxPx)  |  corners inside the map << 28 (4 bits)
+// (a point has ONE record, in the bin of the tile that owns it: that tile forms the point's gradients).  The bin fixes (image, head, level).
 struct alignas(16) RpsRec {
     unsigned code;
     float lh, lw, a;   // bilinear fractions, attention weight
@@ -116,20 +127,21 @@ struct RpsLds {
     int item_slot[2];                   // work-queue draws (current / next), double-buffered
     int wave_tot[16];
     int n_segs, pad[3];
-    int uhist[16];                      // walk units per (wave of the scan, length class), longest class first
+    int uhist[32];                      // walk units per (wave of the scan, length class), longest class first
     uint2 runs[kRpsMaxRuns];            // the work item's bin as the route pass left it: {first record, position inside the bin} per run
     unsigned long long stamp_last, stamp_acc[14];
-    int offs[kRpsMaxPx + 4];            // histogram, then exclusive prefix: where a base pixel's list starts
-    unsigned short seg[kRpsMaxSegs + 16];   // walk units of the chunk: list | segment of the list << 8
+    int offs[kRpsScanThreads + 4];      // histogram, then exclusive prefix: where a base pixel's list starts
+    unsigned seg[kRpsMaxSegs + 16];     // walk units of the chunk: list | segment of the list << 16
     RpsEnt ent[kRpsChunk];              // sorted points of the chunk, then their corner dots
-    RpsRec meta[kRpsChunk];             // the routed records in ARRIVAL order (for the gradient combine)
     unsigned short slot[kRpsChunk];     // arrival index -> sorted slot (where the point's four corner dots are found)
+    // (the records themselves -- code, fractions, weight, which the gradient stage needs in ARRIVAL order -- are not kept here: a lane
+    // reads its records of the chunk from the pool a second time, behind its last walk unit; see stage (4))
     // grad_value of the tile's pixel grid: f64 sums (ds_add_f64), stored once per work item.  A pixel's row is 36 doubles and
     // channel 4*j + i of a half sits in slot 4*i + j: the four lanes of a quad then add to four consecutive doubles, and the
     // 16 quads of a wave -- consecutive pixels, usually -- spread over all 32 bank pairs (a 256-B row stride would put every
     // quad on the same banks: 16-way conflicts on every atomic)
-    double sum[kRpsMaxPx * kRpsSumStride];
-    float vtile[kRpsMaxPx * kRpsD];     // value rows of the pixel grid
+    alignas(16) double sum[kRpsMaxPx * kRpsSumStride];
+    alignas(16) float vtile[kRpsMaxPx * kRpsD];     // value rows of the pixel grid
 };
 static_assert(sizeof(RpsLds) <= 160 * 1024, "rps: LDS budget");
 
@@ -436,7 +448,7 @@ __global__ __launch_bounds__(kRpsRouteThreads, 4) void rps_route_kernel(const fl
             const unsigned w = word[l];
             if (w != ~0u) {
                 const unsigned slot = min(slot0[l] + ((w >> 9) & 16383u), g.entries_cap - 1u);
-                const unsigned code = qp | (w >> 23) << kRpsQpBits | inmap[l] << 27 | 0x80000000u;
+                const unsigned code = qp | (w >> 23) << kRpsQpBits | inmap[l] << (kRpsQpBits + kRpsPxBits);
                 g.entries[slot] = RpsRec{code, lh[l], lw[l], at[l]};
             }
         }
@@ -639,6 +651,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
         if (tid < kRpsMaxRuns) S->runs[tid] = run_reg;
     };
     RpsRec n_rec[kRpsRpl];   // this lane's records of the chunk in flight (lanes past the end of the bin: a copy of its last record)
+    unsigned n_idx[kRpsRpl];  // ... and where in the pool they are: the gradient stage reads them again (two registers across the walk, not eight)
     // The run of record k = the last run that starts at or before it (the runs' positions ascend with their slots).  A binary search over
     // the table is nine DEPENDENT LDS reads per record -- 2.2 k cycles per call with every wave of the workgroup in the same chain, ~20 calls
     // per workgroup: 9 % of the kernel (round 5, stage stamps).  A wave's 64 records are consecutive, so the wave searches together: every
@@ -663,7 +676,8 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                 if (cand < rb && S->runs[cand].y <= k) r = cand;
             }
             const uint2 run = S->runs[r];
-            n_rec[u] = g.entries[n > 0 ? min(run.x + (k - run.y), g.entries_cap - 1u) : 0u];
+            n_idx[u] = n > 0 ? min(run.x + (k - run.y), g.entries_cap - 1u) : 0u;
+            n_rec[u] = g.entries[n_idx[u]];
         }
     };
     // value rows of a work item's pixel grid: 32 B per lane and pixel, pixels `quad` and `quad + 192` (the second only where
@@ -742,12 +756,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
             for (int i = tid; i <= npx; i += kRpsThreads) S->offs[i] = 0;
             int pbase[kRpsRpl], pos[kRpsRpl];
 #pragma unroll
-            for (int u = 0; u < kRpsRpl; ++u) {
-                pos[u] = -1;
-                // the record stays in the order the route pass wrote it: neighbouring lanes hold neighbouring points of a query, and the
-                // gradient stores of stage (5) -- taken in this order -- fall into 16 / 32 contiguous bytes per (query, level)
-                S->meta[u * kRpsThreads + tid] = n_rec[u];
-            }
+            for (int u = 0; u < kRpsRpl; ++u) pos[u] = -1;
             // (the next queue draw goes out here, in the item's first chunk: returning atomics and loads come back in order, and the three
             // sort stages that follow touch LDS only -- at the top of the item it delayed the value rows, behind the walk the next records)
             if (ch == 0) draw = atomicAdd(draw_at, draw_by);
@@ -755,20 +764,20 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
             RPS_STAMP(1)
 #pragma unroll
             for (int u = 0; u < kRpsRpl; ++u) {
-                pbase[u] = (int)((n_rec[u].code >> kRpsQpBits) & 0xFFu);
+                pbase[u] = min((int)((n_rec[u].code >> kRpsQpBits) & ((1u << kRpsPxBits) - 1u)), kRpsMaxPx - 1);      // (clamped like the record indices: never an LDS access outside the tables)
                 if (u * kRpsThreads + tid < n_here) pos[u] = atomicAdd(&S->offs[pbase[u]], 1);
             }
             __syncthreads();
             RPS_STAMP(2)
 
-            // ---- (2) exclusive scan of the per-list counts (<= 256: one per thread of the first 4 waves) and of the lists' unit
+            // ---- (2) exclusive scan of the per-list counts (one per thread of the first kRpsScanWaves waves) and of the lists' unit
             //      counts, both in one packed word (count | units << 16); every list writes its units -------------------------------
             //      The units are listed by LENGTH CLASS, longest first: a wave walks 16 units side by side for as long as the longest
             //      of them, so units of like length (four classes) go together (lists vary from 1 to 16+ points around a mean of ~6).
             {
                 const int sh = g.seg_shift;      // a unit's length -> quarter of the full length it falls into -> slot (0 = longest)
                 int c = 0, v = 0, incl = 0, n_full = 0, part = 0, pslot = 0, n0 = 0, incl0 = 0, rank = 0, mycnt = 0;
-                if (tid < kRpsMaxPx) {
+                if (tid < kRpsScanThreads) {
                     c = tid < npx ? S->offs[tid] : 0;
                     v = c | ((c + (1 << sh) - 1) >> sh) << 16;
                     n_full = c >> sh;
@@ -790,14 +799,14 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                     if (lane < 4) S->uhist[wave * 4 + lane] = mycnt;
                 }
                 __syncthreads();
-                if (tid < kRpsMaxPx) {
+                if (tid < kRpsScanThreads) {
                     int base = 0;
 #pragma unroll
-                    for (int w = 0; w < kRpsMaxPx / kWave; ++w) base += w < wave ? S->wave_tot[w] : 0;
+                    for (int w = 0; w < kRpsScanWaves; ++w) base += w < wave ? S->wave_tot[w] : 0;
                     const int excl = base + incl - v;
                     if (tid <= npx) S->offs[tid] = excl & 0xFFFF;      // tid == npx: the total (c = 0 there)
-                    if (tid == kRpsMaxPx - 1) {
-                        if (npx == kRpsMaxPx) S->offs[npx] = (base + incl) & 0xFFFF;
+                    if (tid == kRpsScanThreads - 1) {
+                        if (npx == kRpsScanThreads) S->offs[npx] = (base + incl) & 0xFFFF;
                         S->n_segs = (base + incl) >> 16;
                     }
                     // where this wave's units of slot k start: the slots before k of all waves + slot k of the waves before this one --
@@ -807,7 +816,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                     for (int k = 0; k < 4; ++k) {
                         int tot = 0, mine_before = 0;
 #pragma unroll
-                        for (int w = 0; w < kRpsMaxPx / kWave; ++w) {
+                        for (int w = 0; w < kRpsScanWaves; ++w) {
                             const int x = S->uhist[w * 4 + k];
                             tot += x;
                             mine_before += w < wave ? x : 0;
@@ -817,9 +826,9 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                     }
                     const int at0 = sbk[0] + incl0 - n0;
                     const int atp = (pslot == 1 ? sbk[1] : (pslot == 2 ? sbk[2] : sbk[3])) + rank;
-                    for (int sgm = 0; sgm < n_full; ++sgm) S->seg[at0 + sgm] = (unsigned short)(tid | sgm << 8);
-                    if (pslot == 0) S->seg[at0 + n_full] = (unsigned short)(tid | n_full << 8);
-                    else if (pslot > 0) S->seg[atp] = (unsigned short)(tid | n_full << 8);
+                    for (int sgm = 0; sgm < n_full; ++sgm) S->seg[at0 + sgm] = (unsigned)(tid | sgm << 16);
+                    if (pslot == 0) S->seg[at0 + n_full] = (unsigned)(tid | n_full << 16);
+                    else if (pslot > 0) S->seg[atp] = (unsigned)(tid | n_full << 16);
                 }
             }
             __syncthreads();
@@ -848,8 +857,8 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                 const int un = u0 + (lane >> 2);
                 if (un < n_segs) {
                     const unsigned sc = S->seg[un];
-                    const int my_p = (int)(sc & 0xFFu);
-                    int e = S->offs[my_p] + (int)((sc >> 8) << g.seg_shift);
+                    const int my_p = (int)(sc & 0xFFFFu);
+                    int e = S->offs[my_p] + (int)((sc >> 16) << g.seg_shift);
                     const int e1 = min(e + (1 << g.seg_shift), S->offs[my_p + 1]);
                     // value rows of the four corner pixels (clamped into the grid: a corner above / left of row / column 0 of
                     // the grid lies outside the map or belongs to a point this tile does not form gradients for)
@@ -969,6 +978,19 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                     S->stamp_acc[12] += 1;
                 }
             }
+            // The gradient stage (5) wants the chunk's records -- code, fractions, weight -- once more, in ARRIVAL order.  They are not kept
+            // in LDS (24.5 KB that buy larger tiles instead) nor in registers across the walk (it has none to spare): a lane reads its
+            // 16 B per record from the pool again, at the addresses fetch_recs formed (n_idx: two registers across the walk, not eight) --
+            // from the L2 now.  The request goes out here, behind the wave's last walk unit, where the walk's registers are free, and comes
+            // back under the next chunk's run search and the wait for the slowest wave at the barrier.
+            // (the index passes through an opaque asm: a load the compiler can move in front of the walk would be held across it)
+            RpsRec c_rec[kRpsRpl];
+#pragma unroll
+            for (int u = 0; u < kRpsRpl; ++u) {
+                unsigned ix = n_idx[u];
+                asm volatile("" : "+v"(ix));
+                c_rec[u] = g.entries[ix];
+            }
             // the next chunk -- or the first chunk of the next work item -- is requested now, behind the walk (held across it,
             // the eight registers would spill) and AHEAD of this chunk's gradient stores
             // (both requests are issued whatever the chunk -- the run table of the NEXT item is parked in LDS only behind the last chunk's
@@ -991,9 +1013,9 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
 #pragma unroll
             for (int u = 0; u < kRpsRpl; ++u) {
                 const int k = min(u * kRpsThreads + tid, n_here - 1);
-                const RpsRec r = S->meta[k];
+                const RpsRec r = c_rec[u];
                 float4 d = *reinterpret_cast<const float4 *>(S->ent + S->slot[k]);
-                const unsigned in = r.code >> 27;
+                const unsigned in = r.code >> (kRpsQpBits + kRpsPxBits);
                 if (!(in & 1u)) d.x = 0.f;
                 if (!(in & 2u)) d.y = 0.f;
                 if (!(in & 4u)) d.z = 0.f;
@@ -1005,7 +1027,7 @@ __global__ __launch_bounds__(kRpsThreads, kRpsThreads / 256) void rps_tile_kerne
                 const unsigned qp = r.code & ((1u << kRpsQpBits) - 1u);
                 const unsigned q = P4 ? qp >> 2 : qp / (unsigned)P, pp = qp - q * (unsigned)P;
                 pt_[u] = (unsigned)((bq0 + (int)q) * g.M + m) * (unsigned)LP + (unsigned)(l * P) + pp;
-                mine_[u] = u * kRpsThreads + tid < n_here && (r.code >> 31);
+                mine_[u] = u * kRpsThreads + tid < n_here;
                 ga_[u] = s_a;
                 gx_[u] = (float)W * s_w * r.a;
                 gy_[u] = (float)H * s_h * r.a;
@@ -1132,7 +1154,7 @@ __global__ __launch_bounds__(256) void rps_round_kernel(const float *__restrict_
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 struct RpsOptions {
-    std::atomic<int> tile{16};         // largest tile side + 1 (tile + one row / column <= kRpsMaxPx = 256 pixels)
+    std::atomic<int> tile{16};         // 16: the planner's choice (sides up to kRpsMaxSide - 1, tile + one row / column <= kRpsMaxPx pixels); below: largest tile side + 1
     std::atomic<int> max_chunks{12};   // expected chunks of one workgroup before a tile is split into slabs (MI355X, call E: 6 -> 12 = 463 -> 447 us on uniform locations, equal at the init pattern)
     std::atomic<int> route_wgs{2};     // route pass: workgroups per CU (persistent over the query blocks): two are resident at its 102 registers (MI355X, call E: 2 -> 55.9 us, 3 -> 61.7, 4 -> 58.1, 6 -> 63.1)
     std::atomic<int> order{0};         // work-queue order of the tile kernel: 0 = heaviest tile first, 1 = region-major (see plan_rps)
@@ -1169,25 +1191,46 @@ inline RpsPlan plan_rps(int N, int S, int M, int D, int L, int Lq, int P, const 
     g.N = N; g.S = S; g.M = M; g.Lq = Lq; g.L = L; g.P = P;
     g.seg_shift = std::max(kRpsSegShift, std::min(11, rps_options().seg_shift.load()));
     g.ppx = (N * M + kXcds - 1) / kXcds;
-    const int tmax = std::max(1, rps_options().tile.load() - 1), max_chunks = std::max(1, rps_options().max_chunks.load());
+    const int tile_opt = rps_options().tile.load();
+    const int tmax = tile_opt >= 16 ? kRpsMaxSide - 1 : std::max(1, tile_opt - 1), max_chunks = std::max(1, rps_options().max_chunks.load());
     struct U { unsigned code; int64_t cost; };
     std::vector<U> units;
     int bins = 0;
     for (int l = 0; l < L; ++l) {
         RpsLevel &v = g.lv[l];
         v.H = (int)shapes[2 * l]; v.W = (int)shapes[2 * l + 1]; v.start = (int)lsi[l];
-        for (int t = tmax; t >= 1; --t) {   // balanced tiles of at most t x t pixels whose grid (+1 row / column) fits the lane groups
-            v.nty = (v.H + t - 1) / t; v.ntx = (v.W + t - 1) / t;
-            v.TH = (v.H + v.nty - 1) / v.nty; v.TW = (v.W + v.ntx - 1) / v.ntx;
-            v.nty = (v.H + v.TH - 1) / v.TH; v.ntx = (v.W + v.TW - 1) / v.TW;
-            if ((v.TH + 1) * (v.TW + 1) <= kRpsMaxPx) break;
+        // Balanced tiles of at most tmax x tmax pixels whose grid (+1 row / column) fits kRpsMaxPx; they need not be square.  Among the
+        // splits that fit, the one that costs least by the stage stamps' model (profiles/r21_rps_recut.md): outside the walk a work
+        // item spends ~5 parts per item (header, value rows, fold + flush) and ~2 per chunk (entries, ranks, scan, placement, combine).
+        // Chunks are counted from the points a tile receives if they spread evenly over the level, with the slab rule's 5 % margin --
+        // so a fine level gets the largest tile whose points still fit ONE chunk, not a larger one that opens a second, nearly empty
+        // chunk.  For every row split the widest columns that fit are tried, and the three splits after them.
+        const double per_px = (double)Lq * P / ((double)v.H * v.W);
+        auto chunks_of = [&](int th, int tw) { return (int)(per_px * th * tw * 1.05 / kRpsChunk) + 1; };
+        auto slabs_of = [&](int nchunks) { return std::min(255, std::max(1, (nchunks + max_chunks - 1) / max_chunks)); };
+        int64_t best = -1;
+        v.TH = v.TW = v.nty = v.ntx = 0;
+        for (int nty = 1; nty <= std::min(64, v.H); ++nty) {
+            const int th = (v.H + nty - 1) / nty;
+            if (th > tmax || (v.H + th - 1) / th != nty) continue;      // (too tall, or the rows of a split already seen)
+            int tried = 0;
+            for (int ntx = 1; ntx <= std::min(64, v.W) && tried < 4; ++ntx) {
+                const int tw = (v.W + ntx - 1) / ntx;
+                if (tw > tmax || (th + 1) * (tw + 1) > kRpsMaxPx || (v.W + tw - 1) / tw != ntx) continue;
+                ++tried;
+                const int nch = chunks_of(th, tw);
+                const int64_t cost = (int64_t)nty * ntx * (5 * slabs_of(nch) + 2 * nch);
+                if (best < 0 || cost < best) {
+                    best = cost;
+                    v.TH = th; v.TW = tw; v.nty = nty; v.ntx = ntx;
+                }
+            }
         }
-        if ((v.TH + 1) * (v.TW + 1) > kRpsMaxPx || v.nty > 64 || v.ntx > 64) return pl;
+        if (best < 0) return pl;      // (more than 64 tiles along a side)
         // slabs per tile, from the points a tile receives if they spread evenly over the level (they need not: a slab just
         // takes what lands in its bin)
-        const double per_px = (double)Lq * P / ((double)v.H * v.W);
-        const int nchunks = (int)(per_px * v.TH * v.TW * 1.05 / kRpsChunk) + 1;
-        v.nslab = std::min(255, std::max(1, (nchunks + max_chunks - 1) / max_chunks));
+        const int nchunks = chunks_of(v.TH, v.TW);
+        v.nslab = slabs_of(nchunks);
         v.atomic = v.nslab > 1 ? 1 : 0;
         v.inv_TH = 1.0f / (float)v.TH;
         v.inv_TW = 1.0f / (float)v.TW;
@@ -1201,12 +1244,13 @@ inline RpsPlan plan_rps(int N, int S, int M, int D, int L, int Lq, int P, const 
     }
     if (units.size() > (size_t)kRpsMaxUnits) return pl;
     g.lut_n = 0;
-    for (int l = 0; l < L; ++l) {      // (H, W <= 64 tiles of <= 15 pixels: at most 4 x 2 x 962 words = 30 KB of LDS)
+    for (int l = 0; l < L; ++l) {
         g.lut_r[l] = g.lut_n;
         g.lut_n += g.lv[l].H + 1;
         g.lut_c[l] = g.lut_n;
         g.lut_n += g.lv[l].W + 1;
     }
+    if (g.lut_n > kRpsMaxL * 2 * 962) return pl;      // (the route pass's tables: at most 30 KB of LDS, what 64 tiles of 15 pixels per side took)
     if (rps_options().order.load() == 0) {
         std::stable_sort(units.begin(), units.end(), [](const U &a, const U &b) { return a.cost > b.cost; });      // heaviest first
     } else {
