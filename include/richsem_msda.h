@@ -579,7 +579,10 @@ int msda_sine_embed_bf16(const float *boxes, int ld, int tokens, int dims, int p
 /* ROIAlign forward (reference models/richsem/richsem.py:750, :878:
  * detectron2.layers.ROIAlign(output_size, spatial_scale, sampling_ratio = 0, aligned = True) on the frozen CLIP feature map).
  * input (N, C, H, W) contiguous; rois (K, 5) = (batch index, x1, y1, x2, y2) in input pixels; output (K, C, pooled_h, pooled_w).
- * detectron2's published algorithm (= torchvision.ops.roi_align); no gradient (the teacher is frozen). */
+ * detectron2's published algorithm (= torchvision.ops.roi_align); no gradient (the teacher is frozen).
+ * Refusals: a ROI whose batch index is outside [0, N), whose coordinates are not finite, or whose adaptive sampling grid
+ * (sampling_ratio = 0: ceil(roi / bins)) would exceed 4096 per axis is written as exact zeros, the other ROIs unaffected;
+ * sampling_ratio > 4096 is MSDA_ERR_BAD_DIMS.  A ROI inside these limits is computed as the published algorithm does. */
 int msda_roi_align_forward_f32(const float *input, const float *rois, int K, int N, int C, int H, int W, int pooled_h,
                                int pooled_w, double spatial_scale, int sampling_ratio, int aligned, float *output,
                                msda_stream_t stream);

@@ -7,6 +7,11 @@
 //   * every output bin averages a grid of sampling_ratio^2 (or ceil(roi / bins)^2 when sampling_ratio = 0) bilinear samples;
 //   * a sample more than one pixel outside the map contributes 0, coordinates are clamped into [0, size - 1] otherwise.
 // Forward only: the teacher features carry no gradient.
+//
+// Refusals (they keep a launch finite whatever the roi buffer holds; the published algorithm has none): a ROI whose batch index is
+// outside [0, N), whose scaled start or size is not finite (an infinite or NaN coordinate), or whose adaptive sampling grid
+// ceil(roi / bins) would exceed kRoiTgtMaxGrid per axis -- one thread would loop grid_h * grid_w times -- is written as exact zeros; the
+// other ROIs of the call are unaffected.  Every ROI inside the cap is computed by the same operations as before the cap existed.
 #pragma once
 
 #include <stdint.h>
@@ -14,6 +19,8 @@
 #include "msda_common.h"
 
 namespace msda {
+
+constexpr int kRoiTgtMaxGrid = 4096;      // samples per bin and axis (this kernel and msda_roi_targets.h)
 
 template <typename T>
 __device__ __forceinline__ T roi_bilinear(const T *__restrict__ plane, int height, int width, T y, T x)
@@ -54,8 +61,15 @@ __global__ __launch_bounds__(256) void roi_align_fwd_kernel(const T *__restrict_
             roi_h = roi_h > (T)1 ? roi_h : (T)1;
         }
         const T bin_h = roi_h / (T)PH, bin_w = roi_w / (T)PW;
-        const int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)ceil(roi_h / (T)PH);
-        const int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)ceil(roi_w / (T)PW);
+        const T adaptive_h = ceil(roi_h / (T)PH), adaptive_w = ceil(roi_w / (T)PW);
+        bool ok = isfinite(start_w) && isfinite(start_h) && isfinite(roi_w) && isfinite(roi_h);      // (every sample position is finite then)
+        if (sampling_ratio <= 0) ok = ok && adaptive_h <= (T)kRoiTgtMaxGrid && adaptive_w <= (T)kRoiTgtMaxGrid;
+        if (!ok) {
+            output[index] = (T)0;
+            continue;
+        }
+        const int grid_h = sampling_ratio > 0 ? sampling_ratio : (int)adaptive_h;
+        const int grid_w = sampling_ratio > 0 ? sampling_ratio : (int)adaptive_w;
         const T count = (T)(grid_h * grid_w > 1 ? grid_h * grid_w : 1);
         const T *plane = input + ((int64_t)b * C + c) * H * W;
         T acc = (T)0;

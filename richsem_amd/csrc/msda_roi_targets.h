@@ -10,7 +10,7 @@
 // Arithmetic of a live slot: the pixel box is formed with the float32 roundings clip_box_targets makes in torch, one per operation and no
 // contraction -- hw = 0.5 * w, cx -+ hw, times the image's width (height) --, then the algorithm of msda_roi.h (aligned = true: scaled by
 // spatial_scale, shifted by -0.5; a bin averages sampling_ratio^2, or ceil(roi / bins)^2, bilinear samples).  Two refusals keep a launch
-// finite whatever the box buffer holds: a live slot whose pixel box is not finite, or whose sampling grid would exceed kRoiTgtMaxGrid per
+// finite whatever the box buffer holds: a live slot whose pixel box is not finite, or whose sampling grid would exceed kRoiTgtMaxGrid (msda_roi.h) per
 // axis, is written as zeros (a normalised box inside its image never comes near either).
 //
 // Mapping: a workgroup per (slot, chunk of kRoiTgtChunk channels); thread = (bin, channel lane): consecutive threads own consecutive bins,
@@ -29,7 +29,6 @@ namespace msda {
 constexpr int kRoiTgtThreads = 256;
 constexpr int kRoiTgtChunk = 64;          // channels per workgroup
 constexpr int kRoiTgtMaxImages = 1024;    // cum is kept in LDS
-constexpr int kRoiTgtMaxGrid = 4096;      // samples per bin and axis
 
 struct RoiTgtArgs {
     const float *input;

@@ -849,7 +849,8 @@ int roi_align_impl(const char *entry, const T *input, const T *rois, int K, int 
                    int sampling_ratio, int aligned, T *output, msda_stream_t stream)
 {
     if (!input || !rois || !output) return msda::fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    if (K < 0 || N < 1 || C < 1 || H < 1 || W < 1 || PH < 1 || PW < 1 || sampling_ratio < 0 || !(spatial_scale > 0))
+    if (K < 0 || N < 1 || C < 1 || H < 1 || W < 1 || PH < 1 || PW < 1 || sampling_ratio < 0 || sampling_ratio > msda::kRoiTgtMaxGrid ||
+        !(spatial_scale > 0))
         return msda::fail(MSDA_ERR_BAD_DIMS, "bad ROIAlign dimensions");
     const int64_t n_out = (int64_t)K * C * PH * PW;
     if (n_out == 0) return MSDA_OK;
