@@ -450,6 +450,38 @@ int msda_criterion_pairs_f32(const float *logits, const float *coords, const flo
 int msda_criterion_pairs_backward_f32(const void *workspace, const int64_t *cum, const float *gscale, int nl, int N, int Q, int Qi, int C,
                                       int64_t capacity, int pad_cap, float *grad_logits, float *grad_il, float *grad_coords, float *grad_ib,
                                       msda_stream_t stream);
+/* msda_criterion_pairs_ex_f32: msda_criterion_pairs_f32 with options (that entry point is this one with flags = 0 and both row_group
+ * pointers NULL: the same launches, the same bits).
+ *   flags & 1                     enc_cls_agn (richsem.py:1249-1255): the slots of the two-stage output take label 0 instead of tgt_ids -- in the
+ *                                 positive entry's focal correction, in the record the backward scatters from and in the range check (label 0 is
+ *                                 always in range: such a slot is never left out for its label).  Other bits: MSDA_ERR_BAD_OPTION.
+ *   row_group (nl, N, pad_cap + Q) int32, row_group_int (N, Qi) int32, each or NULL: the get_loss call of every row, written by the threads
+ *                                 that write row_weight -- rows s < pad_cap of layer l: nl + l; rows s >= pad_cap: l; two-stage rows: 2 nl.  It
+ *                                 is the row_group of msda_focal_neg_{sum,grad}_masked_f32 for a class_mask of 2 nl + 1 rows.
+ * The backward is msda_criterion_pairs_backward_f32, unchanged: the record carries the class.
+ *
+ * msda_fed_class_mask_slots_f32 (csrc/msda_fed_slots.h): msda_fed_class_mask_f32 with the appeared classes of each group read from the slot
+ * space above instead of a label list of exact length.  One workgroup per get_loss call g in 0 .. 2 nl, numbered as `terms`:
+ *   g < nl            the labels tgt_ids[t] of the slots t < cum[N] with 0 <= query_of_target[g][t] < Q
+ *   nl <= g < 2 nl    nothing if dn_meta is NULL, overflow != 0, pad_size == 0 (or num_dn_group < 1, or pad_size no multiple of it); else
+ *                     tgt_ids[cum[b] + j] for every image b and j < min(T_b, pad_size / num_dn_group)
+ *   g == 2 nl         as g < nl with row nl of query_of_target and Qi queries; with flags & 1 the label of every such slot is 0
+ * Labels outside [0, C) appear nowhere; a cum that does not start at 0, decreases or exceeds capacity leaves every group empty.  So a class is
+ * appeared in group g iff msda_criterion_pairs_ex_f32 (same arguments, same flags, dn_meta from msda_dn_queries_f32 run with the pair call's
+ * pad_cap -- a layout that does not fit pad_cap has overflow set) counts a positive entry of that class in call g.
+ *   class_weight (C), uniform (2 nl + 1, C), num_sample_cats -> mask (2 nl + 1, C), n_chosen (2 nl + 1): as msda_fed_class_mask_f32, and bit for
+ *   bit what that function gives for group g's exact label list and uniform row g (same keys, same order of ties, same fewer-eligible rule).
+ * No global atomic, no workspace, no host synchronisation: capturable.  Limits: 1 <= C <= 4096, N <= 1024, nl, Q, Qi, capacity >= 1,
+ * num_sample_cats >= 0 (MSDA_ERR_BAD_DIMS); capacity < 2^24, nl < 2^20 (MSDA_ERR_TOO_LARGE); flags within bit 0 (MSDA_ERR_BAD_OPTION); int64
+ * inputs 8-byte aligned (MSDA_ERR_MISALIGNED). */
+int msda_criterion_pairs_ex_f32(const float *logits, const float *coords, const float *il, const float *ib, const int64_t *cum, const int64_t *tgt_ids,
+                                const float *tgt_boxes, const int64_t *query_of_target, const int64_t *dn_meta, const float *num_boxes, int nl, int N,
+                                int Q, int Qi, int C, int64_t capacity, int pad_cap, float alpha, float c_cls, float c_l1, float c_giou, int flags,
+                                float *row_weight, float *row_weight_int, int32_t *row_group, int32_t *row_group_int, float *terms, int32_t *status,
+                                void *workspace, msda_stream_t stream);
+int msda_fed_class_mask_slots_f32(const int64_t *cum, const int64_t *tgt_ids, const int64_t *query_of_target, const int64_t *dn_meta,
+                                  const float *class_weight, const float *uniform, int nl, int N, int Q, int Qi, int C, int64_t capacity,
+                                  int num_sample_cats, int flags, float *mask, int32_t *n_chosen, msda_stream_t stream);
 
 /* ---- the distillation term over CAPACITY buffers (csrc/msda_roi_targets.h, csrc/msda_distill_pairs.h; reference models/richsem/richsem.py:
  * 745-761 for the teacher's box targets, :967-1024 with :1158-1180 for the term): the teacher's ROI rows, the (student row, teacher row)

@@ -64,7 +64,7 @@ SYMBOLS = [
     "msda_prep_forward_f32", "msda_prep_forward_f64", "msda_prep_backward_f32", "msda_prep_backward_f64",
     "msda_prep_forward_bf16", "msda_prep_backward_bf16", "msda_forward_prep_f32", "msda_forward_prep_f64", "msda_forward_prep_bf16",
     "msda_mask_rows_f32", "msda_mask_rows_f64", "msda_mask_rows_bf16",
-    "msda_dn_indices_i64", "msda_dn_attn_mask_u8", "msda_topk_f32", "msda_sine_embed_bf16", "msda_narrow_linear_backward_bf16", "msda_box_refine_forward", "msda_box_refine_backward", "msda_box_refine_backward_ref", "msda_box_pair_loss_f32", "msda_focal_pos_sum_f32", "msda_criterion_workspace_bytes", "msda_criterion_pairs_f32", "msda_criterion_pairs_backward_f32", "msda_roi_align_targets_f32", "msda_distill_pairs", "msda_distill_scatter_f32", "msda_distill_scatter_bf16", "msda_roi_align_forward_f32", "msda_roi_align_forward_f64",
+    "msda_dn_indices_i64", "msda_dn_attn_mask_u8", "msda_topk_f32", "msda_sine_embed_bf16", "msda_narrow_linear_backward_bf16", "msda_box_refine_forward", "msda_box_refine_backward", "msda_box_refine_backward_ref", "msda_box_pair_loss_f32", "msda_focal_pos_sum_f32", "msda_criterion_workspace_bytes", "msda_criterion_pairs_f32", "msda_criterion_pairs_backward_f32", "msda_criterion_pairs_ex_f32", "msda_fed_class_mask_slots_f32", "msda_roi_align_targets_f32", "msda_distill_pairs", "msda_distill_scatter_f32", "msda_distill_scatter_bf16", "msda_roi_align_forward_f32", "msda_roi_align_forward_f64",
     "msda_ffn_pack_w2_bf16", "msda_ffn_forward_bf16", "msda_ffn_debug_stamps", "msda_ffn_forward_train_bf16", "msda_ffn_ln_backward_bf16", "msda_add_layernorm_forward_bf16", "msda_lin256_pack_bf16", "msda_lin256_forward_bf16", "msda_lin256_pack_f32", "msda_lin256_forward_f32", "msda_lin256_forward_stacked_bf16",
     "msda_attn_workspace_bytes", "msda_attn_forward_bf16", "msda_attn_backward_bf16",
     "msda_matcher_cost_f32", "msda_matcher_cost_f64", "msda_matcher_cost_tm_f32", "msda_matcher_cost_tm_f64",
@@ -148,6 +148,10 @@ def load():
     L.msda_criterion_pairs_f32.restype = ci
     L.msda_criterion_pairs_backward_f32.argtypes = [vp] * 3 + [ci] * 5 + [ctypes.c_int64, ci] + [vp] * 5
     L.msda_criterion_pairs_backward_f32.restype = ci
+    L.msda_criterion_pairs_ex_f32.argtypes = [vp] * 10 + [ci] * 5 + [ctypes.c_int64, ci] + [ctypes.c_float] * 4 + [ci] + [vp] * 8
+    L.msda_criterion_pairs_ex_f32.restype = ci
+    L.msda_fed_class_mask_slots_f32.argtypes = [vp] * 6 + [ci] * 5 + [ctypes.c_int64, ci, ci] + [vp] * 3
+    L.msda_fed_class_mask_slots_f32.restype = ci
     L.msda_roi_align_targets_f32.argtypes = [vp] * 4 + [ci] * 4 + [ctypes.c_int64, ci, ci, ctypes.c_double, ci, vp, vp, vp]
     L.msda_roi_align_targets_f32.restype = ci
     L.msda_distill_pairs.argtypes = [vp] * 4 + [ci] * 4 + [ctypes.c_int64, ctypes.c_int64, ci] + [vp] * 6

@@ -10,12 +10,18 @@ graph of cost blocks -> assignment -> criterion (+ backward) serves any batch th
 Launches: forward -- the pair kernel (slots, row weights, per-workgroup partials), its reduction, ``msda_focal_neg_sum_f32`` over the decoder
 logits and over the two-stage logits, and a few scalar torch ops that add the parts up; backward -- ``msda_focal_neg_grad_f32`` twice (the only
 dense passes over the logits) and one scatter kernel.  No gather, no index tensor, no dense zero-fill of a logit-shaped tensor.
+
+:func:`device_set_criterion` is the same criterion with the reference's two remaining switches: the federated loss (``use_fed_loss``: the
+class subset of every get_loss call is drawn on the device from the appeared classes of the batch the buffers hold,
+``msda_fed_class_mask_slots_f32``, and the all-negative term runs through the masked focal kernels with row groups the pair kernel
+writes, ``msda_criterion_pairs_ex_f32``) and ``enc_cls_agn`` (the two-stage output scored against class 0).  Two launches more.
 """
 import ctypes
 
 import torch
 
 from . import _lib
+from .fed_loss import FedClassSampler
 from .matcher import LateStatus
 
 STATUS = ("dn_overflow", "targets_without_query", "labels_out_of_range", "bad_prefix")      # the int32[4] ``status``
@@ -115,10 +121,9 @@ class DeviceCriterionFunction(torch.autograd.Function):
 def _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, fed_loss, enc_cls_agn, distill):
     """the argument checks of :func:`device_criterion`: -> the tensor arguments and ``cfg`` of :func:`criterion_forward`"""
     if fed_loss:
-        raise NotImplementedError("device_criterion: the federated loss over capacity buffers is not built (its class sampler takes a label "
-                                  "tensor of the batch's exact length)")
+        raise NotImplementedError("device_criterion: the federated loss over capacity buffers is device_set_criterion(fed=...)")
     if enc_cls_agn:
-        raise NotImplementedError("device_criterion: enc_cls_agn (class-agnostic two-stage targets) is not built")
+        raise NotImplementedError("device_criterion: class-agnostic two-stage targets are device_set_criterion(enc_cls_agn=True)")
     if distill:
         raise NotImplementedError("device_criterion: the distillation term over capacity buffers is not built (the teacher's ROI rows are one "
                                   "per target)")
@@ -183,6 +188,158 @@ def device_criterion_and_grads(logits, coords, il, ib, targets, query_of_target,
     loss, terms, status, saved = criterion_forward(*args)
     g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
     return loss, terms, status, criterion_backward(saved, g)
+
+
+# ---- the criterion with the reference's remaining switches: the federated loss (use_fed_loss) and class-agnostic two-stage targets --------
+def _neg_sum_masked(x, w, grp, mask, alpha):
+    """the one call of ``msda_focal_neg_sum_masked_f32`` here: -> the float64 partials of the all-negative focal term over each row's subset"""
+    partial = torch.empty(_NEG_PARTIALS, dtype=torch.float64, device=x.device)
+    n = ctypes.c_int(0)
+    _lib.check(_lib.load().msda_focal_neg_sum_masked_f32(x.data_ptr(), w.data_ptr(), grp.data_ptr(), mask.data_ptr(), mask.shape[0], w.numel(),
+                                                         x.shape[-1], alpha, partial.data_ptr(), _NEG_PARTIALS, ctypes.byref(n),
+                                                         _lib.raw_stream(x.device)))
+    return partial[:n.value]
+
+
+def _neg_grad_masked(x, w, grp, mask, alpha, gs):
+    gx = torch.empty_like(x)
+    _lib.check(_lib.load().msda_focal_neg_grad_masked_f32(x.data_ptr(), w.data_ptr(), grp.data_ptr(), mask.data_ptr(), mask.shape[0], w.numel(),
+                                                          x.shape[-1], alpha, gs.data_ptr(), gx.data_ptr(), _lib.raw_stream(x.device)))
+    return gx
+
+
+def set_criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg, class_mask=None, enc_cls_agn=False):
+    """:func:`criterion_forward` with the two switches: ``class_mask`` (2 nl + 1, C) float32 or None -- the class subset of each get_loss call,
+    which the all-negative term is restricted to (``msda_focal_neg_sum_masked_f32`` with the row groups the pair kernel writes) --, and
+    ``enc_cls_agn`` -- the two-stage output's positives take label 0.  Without either it IS :func:`criterion_forward`.  -> (loss, terms,
+    status, saved) for :func:`set_criterion_backward`."""
+    if class_mask is None and not enc_cls_agn:
+        return criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg)
+    pad_cap, capacity, alpha, c_cls, c_l1, c_giou = cfg
+    dev = logits.device
+    dims = _dims(logits, il, pad_cap, capacity)
+    nl, N, Q, Qi, C, cap, _ = dims
+    x, p, xi, pi = logits.contiguous(), coords.contiguous(), il.contiguous(), ib.contiguous()
+    ws = _workspace(dims, dev)
+    w_rows = torch.empty(x.shape[:3], dtype=torch.float32, device=dev)
+    w_int = torch.empty(xi.shape[:2], dtype=torch.float32, device=dev)
+    fed = class_mask is not None
+    g_rows = torch.empty(x.shape[:3], dtype=torch.int32, device=dev) if fed else None
+    g_int = torch.empty(xi.shape[:2], dtype=torch.int32, device=dev) if fed else None
+    terms = torch.empty((2 * nl + 1, 3), dtype=torch.float32, device=dev)
+    status = torch.empty(4, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib.load().msda_criterion_pairs_ex_f32(
+            x.data_ptr(), p.data_ptr(), xi.data_ptr(), pi.data_ptr(), cum.data_ptr(), tgt_ids.data_ptr(), tgt_boxes.data_ptr(), qot.data_ptr(),
+            None if dn_meta is None else dn_meta.data_ptr(), None if num_boxes is None else num_boxes.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap,
+            alpha, c_cls, c_l1, c_giou, 1 if enc_cls_agn else 0, w_rows.data_ptr(), w_int.data_ptr(), g_rows.data_ptr() if fed else None,
+            g_int.data_ptr() if fed else None, terms.data_ptr(), status.data_ptr(), ws.data_ptr(), _lib.raw_stream(dev)))
+        if fed:
+            neg = _neg_sum_masked(x, w_rows, g_rows, class_mask, alpha).sum() + _neg_sum_masked(xi, w_int, g_int, class_mask, alpha).sum()
+        else:
+            neg = _neg_sum(x, w_rows, alpha).sum() + _neg_sum(xi, w_int, alpha).sum()
+    tsum = terms.double().sum(0)
+    loss = (c_cls * (neg + tsum[0]) + c_l1 * tsum[1] + c_giou * tsum[2]).float()
+    return loss, terms, status, (x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls, g_rows, g_int, class_mask)
+
+
+def set_criterion_backward(saved, g):
+    """the backward half of :func:`set_criterion_forward`: -> (grad_logits, grad_coords, grad_il, grad_ib); the logit gradients are exactly 0
+    off each row's class subset"""
+    if len(saved) == 9 or saved[11] is None:
+        return criterion_backward(saved[:9], g)      # (enc_cls_agn alone changes the records, not the launches)
+    x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls, g_rows, g_int, mask = saved
+    nl, N, Q, Qi, C, cap, pad_cap = dims
+    dev = x.device
+    gs = g.detach().reshape(1).float().contiguous()
+    gs_cls = gs * c_cls
+    g_coords = torch.empty(x.shape[:3] + (4,), dtype=torch.float32, device=dev)
+    g_ib = torch.empty(xi.shape[:2] + (4,), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        g_logits = _neg_grad_masked(x, w_rows, g_rows, mask, alpha, gs_cls)
+        g_il = _neg_grad_masked(xi, w_int, g_int, mask, alpha, gs_cls)
+        _lib.check(_lib.load().msda_criterion_pairs_backward_f32(
+            ws.data_ptr(), cum.data_ptr(), gs.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap, g_logits.data_ptr(), g_il.data_ptr(),
+            g_coords.data_ptr(), g_ib.data_ptr(), _lib.raw_stream(dev)))
+    return g_logits, g_coords, g_il, g_ib
+
+
+class DeviceSetCriterionFunction(torch.autograd.Function):
+    """:func:`device_set_criterion` as one autograd node: gradients for logits, coords, il and ib"""
+
+    @staticmethod
+    def forward(ctx, logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg, class_mask, enc_cls_agn):
+        loss, terms, status, saved = set_criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg,
+                                                           class_mask, enc_cls_agn)
+        saved = saved + (None,) * (12 - len(saved))
+        ctx.save_for_backward(*(saved[:6] + saved[9:]))
+        ctx.rest = saved[6:9]
+        ctx.mark_non_differentiable(terms, status)
+        return loss, terms, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_terms, _g_status):
+        t = tuple(ctx.saved_tensors)
+        return set_criterion_backward(t[:6] + ctx.rest + t[6:], g) + (None,) * 9
+
+
+def _checked_set(logits, il, targets, query_of_target, dn_meta, pad_cap, fed, enc_cls_agn, generator):
+    """the checks of :func:`device_set_criterion` beyond :func:`_checked`, and the draw: -> (class_mask or None, fed_out)"""
+    if fed is None:
+        return None, None
+    nl, C = logits.shape[0], logits.shape[-1]
+    if isinstance(fed, FedClassSampler):
+        if fed.num_classes != C:
+            raise ValueError(f"device_set_criterion: the sampler draws from {fed.num_classes} classes, the logits have {C}")
+        mask, n_chosen = fed.sample_slots(targets, query_of_target, dn_meta, nl=nl, Q=logits.shape[2] - int(pad_cap), Qi=il.shape[1],
+                                          enc_cls_agn=enc_cls_agn, generator=generator)
+        return mask, (mask, n_chosen)
+    if not torch.is_tensor(fed):
+        raise TypeError("device_set_criterion: fed is a FedClassSampler, a float32 (2 nl + 1, C) tensor of class masks, or None")
+    if not fed.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    if fed.dtype != torch.float32 or tuple(fed.shape) != (2 * nl + 1, C):
+        raise ValueError(f"device_set_criterion: the class masks are a float32 ({2 * nl + 1}, {C}) tensor: one class subset per get_loss call")
+    mask = fed.detach().contiguous()
+    return mask, (mask, (mask != 0).sum(1, dtype=torch.int32))
+
+
+def device_set_criterion(logits, coords, il, ib, targets, query_of_target, dn_meta=None, *, pad_cap, fed=None, enc_cls_agn=False, generator=None,
+                         alpha=0.25, c_cls=1.0, c_l1=5.0, c_giou=2.0, num_boxes=None, late_status=None):
+    """:func:`device_criterion` with the two remaining switches of the reference's ``SetCriterion``, over the same capacity buffers.
+
+    ``fed`` -- the federated loss (``use_fed_loss``, richsem.py:938-964 with fed_loss.py:15-25): every get_loss call takes the focal loss over
+    a class subset only.  A :class:`~richsem_amd.fed_loss.FedClassSampler`: ``torch.rand((2 nl + 1, C), generator=generator)`` on the current
+    stream, then ``msda_fed_class_mask_slots_f32`` reads each call's appeared classes from the slot space -- the live pairs of THAT call in the
+    batch the buffers hold now, so a captured call draws for the batch of each replay, with fresh uniforms -- and tops them up to
+    ``num_sample_cats``.  A float32 (2 nl + 1, C) tensor: those subsets, nothing is drawn (frozen draws; the caller answers for every
+    positive class lying inside its row).  Rows are numbered as ``terms``.  ``enc_cls_agn`` -- class-agnostic two-stage targets
+    (richsem.py:1249-1255): the two-stage output's positives are class 0, in the loss and in its appeared classes; match it against
+    ``targets.class_agnostic()`` (``match_many_device(..., last_plan=...)``).
+
+    -> ``(loss, terms, status, fed_out)``: the first three as :func:`device_criterion`; ``fed_out`` = ``(class_mask (2 nl + 1, C) float32,
+    n_chosen (2 nl + 1) int32)`` or None without ``fed``.  Without either switch: the launches and bits of :func:`device_criterion`.  One
+    autograd node; the logit gradients are exactly 0 off the subsets.  Nothing waits: capturable after one eager call (which also copies the
+    sampler's weights to the device); bitwise reproducible for given uniforms.  CPU tensors raise: there is no CPU fallback."""
+    args = _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, False, False, False)
+    mask, fed_out = _checked_set(logits, il, targets, query_of_target, dn_meta, pad_cap, fed, bool(enc_cls_agn), generator)
+    loss, terms, status = DeviceSetCriterionFunction.apply(*args, mask, bool(enc_cls_agn))
+    if late_status is not None and not torch.cuda.is_current_stream_capturing():
+        late_status.push(status.view(1, 4))
+    return loss, terms, status, fed_out
+
+
+@torch.no_grad()
+def device_set_criterion_and_grads(logits, coords, il, ib, targets, query_of_target, dn_meta=None, *, pad_cap, fed=None, enc_cls_agn=False,
+                                   generator=None, alpha=0.25, c_cls=1.0, c_l1=5.0, c_giou=2.0, num_boxes=None, grad_loss=None):
+    """:func:`device_set_criterion` and its backward in one call, WITHOUT the autograd engine, as :func:`device_criterion_and_grads`:
+    -> (loss, terms, status, fed_out, (grad_logits, grad_coords, grad_il, grad_ib))"""
+    args = _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, False, False, False)
+    mask, fed_out = _checked_set(logits, il, targets, query_of_target, dn_meta, pad_cap, fed, bool(enc_cls_agn), generator)
+    loss, terms, status, saved = set_criterion_forward(*args, mask, bool(enc_cls_agn))
+    g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
+    return loss, terms, status, fed_out, set_criterion_backward(saved, g)
 
 
 class CriterionStatus(LateStatus):

@@ -16,7 +16,9 @@
 //   denoising (l, b, s), s in 0..pad_cap, from meta = (single_pad, num_dn_group, pad_size, total, overflow):
 //            stride = pad_size / num_dn_group; live iff no overflow, s < pad_size and j = s % stride < T_b; target cum[b] + j;
 //            prediction logits[l, b, s, label] / coords[l, b, s]; weight 1 / (num_boxes * num_dn_group)
-//   rows     one thread per row of logits / il writes the row weight the all-negative focal kernels take.
+//   rows     one thread per row of logits / il writes the row weight the all-negative focal kernels take -- and, where the caller asks for
+//            it, the row's get_loss call (0..nl-1 matching parts, nl..2nl-1 denoising parts, 2 nl the two-stage output): the row_group of
+//            the masked focal kernels (the federated loss, msda_fed_slots.h).
 // num_boxes = max(1, live pairs of the last decoder output), counted by every workgroup for itself (an integer: the same in each), or the
 // caller's value.  Every weight is formed in float64 and rounded to float32 once.
 //
@@ -136,6 +138,8 @@ struct CritArgs {
     int64_t cap;
     float alpha, c_cls, c_l1, c_giou;
     float *row_weight, *row_weight_int;
+    int flags;                               // bit 0: the two-stage output's slots take label 0 (enc_cls_agn, richsem.py:1249-1255)
+    int32_t *row_group, *row_group_int;      // or null: each row's get_loss call, for msda_focal_neg_*_masked_f32
     float4 *rec_gb;
     float *rec_gx;
     int32_t *rec_row, *rec_label;
@@ -231,8 +235,13 @@ __global__ __launch_bounds__(kCritThreads) void criterion_pairs_kernel(CritArgs 
         if (r < rows_dec) {
             const int s = (int)(r % QT);
             a.row_weight[r] = s >= a.pad_cap ? w_m : (!overflow && s < pad_size ? w_d : 0.f);
+            if (a.row_group) {
+                const int l = (int)(r / ((int64_t)N * QT));
+                a.row_group[r] = s >= a.pad_cap ? l : nl + l;
+            }
         } else if (r < rows_dec + (int64_t)N * a.Qi) {
             a.row_weight_int[r - rows_dec] = w_m;
+            if (a.row_group_int) a.row_group_int[r - rows_dec] = 2 * nl;
         }
         return;
     }
@@ -289,7 +298,7 @@ __global__ __launch_bounds__(kCritThreads) void criterion_pairs_kernel(CritArgs 
     float v_cls = 0.f, v_l1 = 0.f, v_giou = 0.f, gx = 0.f;
     float4 gb = make_float4(0.f, 0.f, 0.f, 0.f);
     if (row >= 0) {
-        const int64_t lab = a.tgt_ids[t];
+        const int64_t lab = two_stage && (a.flags & 1) ? 0 : a.tgt_ids[t];
         if (lab < 0 || lab >= a.C) {
             row = -1;      // skipped: nothing is read through the label
         } else {

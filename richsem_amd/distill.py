@@ -374,3 +374,25 @@ def device_distill_and_grads(pred, teacher, targets, query_of_target, dn_meta=No
                                                    None if class_mask is None else class_mask.contiguous(), bool(dynamic_weight), cfg)
     g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
     return loss[0], status, distill_capacity_backward(saved, g)
+
+
+_MASK_ROWS = {}      # (layers, nl, device) -> the static row index of distill_class_mask
+
+
+def distill_class_mask(class_mask, layers, nl):
+    """The (2 n_d, C) ``class_mask`` of :func:`device_distill` from the (2 nl + 1, C) subsets ``criterion.device_set_criterion`` returns
+    (``fed_out[0]``): the matching-part rows of the distilled ``layers``, then their denoising-part rows -- so ``use_fed_on_kd`` sees the
+    subsets ``loss_ce`` of the same get_loss call saw, as in the reference (richsem.py:959, :990-991).  One ``index_select`` with an index
+    that depends on ``layers`` and ``nl`` only: it is built on the first call for a device (a host -> device copy: outside a capture), a
+    captured call replays the select."""
+    nl = int(nl)
+    layers = tuple(sorted(set(int(l) for l in layers)))
+    if not layers or layers[0] < 0 or layers[-1] >= nl:
+        raise ValueError(f"distill_class_mask: layers names distinct decoder layers in 0..{nl - 1}")
+    if class_mask.dim() != 2 or class_mask.shape[0] != 2 * nl + 1:
+        raise ValueError(f"distill_class_mask: class_mask is ({2 * nl + 1}, C): one class subset per get_loss call")
+    key = (layers, nl, class_mask.device)
+    rows = _MASK_ROWS.get(key)
+    if rows is None:
+        rows = _MASK_ROWS[key] = torch.tensor(list(layers) + [nl + l for l in layers], dtype=torch.int64).to(class_mask.device)
+    return class_mask.index_select(0, rows)

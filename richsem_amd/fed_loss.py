@@ -88,6 +88,33 @@ class FedClassSampler:
                                                            _lib.raw_stream(dev)))
         return mask, n_chosen
 
+    def sample_slots(self, targets, query_of_target, dn_meta, *, nl, Q, Qi, enc_cls_agn=False, generator=None):
+        """:meth:`sample` for the 2 nl + 1 get_loss calls of a step over CAPACITY buffers (``msda_fed_class_mask_slots_f32``): the appeared
+        classes of each call are read on the device from ``targets`` (a ``matcher.TargetBuffers``), ``query_of_target`` (nl + 1, capacity) and
+        ``dn_meta`` (or None) -- the live pairs ``criterion.device_set_criterion`` counts in that call, of the batch the buffers hold when the
+        launch RUNS -- so a captured call serves every batch.  Rows: matching parts of layers 0..nl-1, their denoising parts, the two-stage
+        output (``enc_cls_agn``: its class is 0).  -> ``(mask (2 nl + 1, C) float32, n_chosen (2 nl + 1) int32)``."""
+        cum, ids = targets.offsets_dev, targets.tgt_ids
+        if not all(torch.is_tensor(t) and t.is_cuda for t in (cum, ids, query_of_target)) or (dn_meta is not None and not dn_meta.is_cuda):
+            raise RuntimeError("Not implemented on the CPU")
+        dev, C, nl, cap = query_of_target.device, self.num_classes, int(nl), int(targets.total)
+        if any(t.dtype != torch.int64 for t in (cum, ids, query_of_target)) or (dn_meta is not None and dn_meta.dtype != torch.int64):
+            raise TypeError("sample_slots: the target prefix, the labels, query_of_target and dn_meta are int64 tensors")
+        if tuple(query_of_target.shape) != (nl + 1, cap) or not query_of_target.is_contiguous() or tuple(ids.shape) != (cap,) or cum.numel() < 2:
+            raise ValueError(f"sample_slots: query_of_target is a contiguous ({nl + 1}, {cap}) tensor, the labels ({cap},)")
+        if dn_meta is not None and (dn_meta.numel() != 5 or not dn_meta.is_contiguous()):
+            raise ValueError("sample_slots: dn_meta is the contiguous int64[5] meta of denoising_queries")
+        groups = 2 * nl + 1
+        u = torch.rand((groups, C), device=dev, generator=generator)
+        mask = torch.empty((groups, C), dtype=torch.float32, device=dev)
+        n_chosen = torch.empty(groups, dtype=torch.int32, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(_lib.load().msda_fed_class_mask_slots_f32(
+                cum.data_ptr(), ids.contiguous().data_ptr(), query_of_target.data_ptr(), None if dn_meta is None else dn_meta.data_ptr(),
+                self.weight_on(dev).data_ptr(), u.data_ptr(), nl, cum.numel() - 1, int(Q), int(Qi), C, cap, self.num_sample_cats,
+                1 if enc_cls_agn else 0, mask.data_ptr(), n_chosen.data_ptr(), _lib.raw_stream(dev)))
+        return mask, n_chosen
+
 
 class MaskedFocalNegativeSum(torch.autograd.Function):
     """:class:`richsem_amd.matcher.FocalNegativeSum` with the classes of each row restricted to a class subset:

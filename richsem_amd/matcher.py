@@ -122,6 +122,38 @@ class TargetBuffers:
         self.tgt_boxes.copy_(boxes, non_blocking=True)
         return self
 
+    def class_agnostic(self):
+        """the reference's ``enc_targets`` (richsem.py:1249-1255: the targets with every label set to 0, which the two-stage output is matched
+        and scored against under ``enc_cls_agn``) as a plan over the SAME buffers: see :class:`ClassAgnosticTargets`"""
+        return ClassAgnosticTargets(self)
+
+
+class ClassAgnosticTargets:
+    """A :class:`TargetBuffers` seen with every label 0.  ``offsets_dev`` and ``tgt_boxes`` ARE the parent's tensors, and the size bookkeeping
+    (``sizes``, ``offsets``, ``live``, ``total``) is read from the parent, so it follows the parent's ``update_`` without a call of its own;
+    ``tgt_ids`` is a constant zero buffer of the parent's capacity.  ``cost_blocks`` and ``match_many_device(last_plan=...)`` take it."""
+
+    def __init__(self, parent):
+        self.parent = parent
+        self.num_queries = None
+        self.tgt_ids = torch.zeros(parent.capacity, dtype=torch.int64, device=parent.device)
+
+    device = property(lambda self: self.parent.device)
+    dtype = property(lambda self: self.parent.dtype)
+    capacity = property(lambda self: self.parent.capacity)
+    total = property(lambda self: self.parent.total)
+    max_per_image = property(lambda self: self.parent.max_per_image)
+    sizes = property(lambda self: self.parent.sizes)
+    offsets = property(lambda self: self.parent.offsets)
+    live = property(lambda self: self.parent.live)
+    offsets_dev = property(lambda self: self.parent.offsets_dev)
+    tgt_boxes = property(lambda self: self.parent.tgt_boxes)
+
+    def update_(self, targets):
+        """the parent's ``update_`` (the labels of ``targets`` go to the parent; here they stay 0)"""
+        self.parent.update_(targets)
+        return self
+
 
 def cost_blocks(pred_logits, pred_boxes, plan, cost_class, cost_bbox, cost_giou, focal_alpha, out=None, target_major=False):
     """Diagonal cost blocks of one decoder output on the device: a flat tensor of nq * plan.total elements, image b's (nq x T_b)
@@ -248,19 +280,24 @@ class HungarianMatcher(nn.Module):
         return self.match_many_end(self.match_many_begin(outputs_list, targets))
 
     @torch.no_grad()
-    def match_many_device(self, outputs_list, plan, target_major=True):
+    def match_many_device(self, outputs_list, plan, target_major=True, last_plan=None):
         """Match several decoder outputs against the targets of ``plan`` (a :class:`CostPlan` built BEFOREHAND: its constructor copies host
         data to the device) entirely on the device: cost kernels into one buffer, then one ``msda_lsap_*`` launch per run of outputs with
         the same query count (one launch when all have it).  -> (query_of_target (n_out, plan.total) int64: the query matched to each
         target, -1 where none; status (n_out, images) int32: 0 solved, non-zero see include/richsem_msda.h).  Nothing waits and nothing
         reaches the host: safe inside ``torch.cuda.graph`` / ``make_graphed_callables`` after one eager call; ``plan.update_`` feeds a
-        captured call its next batch."""
+        captured call its next batch.  ``last_plan``: the plan the LAST output's cost blocks are computed against -- the two-stage output
+        under ``enc_cls_agn`` against ``plan.class_agnostic()`` (richsem.py:1249-1255) --; it shares ``plan``'s offsets, so the solve launches
+        are the same."""
+        if last_plan is not None and (last_plan.total != plan.total or last_plan.offsets_dev.data_ptr() != plan.offsets_dev.data_ptr()):
+            raise ValueError("match_many_device: last_plan shares the offsets of plan (plan.class_agnostic())")
         first = outputs_list[0]["pred_logits"]
         nqs = [o["pred_logits"].shape[1] for o in outputs_list]
         dev_buf = torch.empty(sum(nq * plan.total for nq in nqs), dtype=first.dtype, device=first.device)
         at, runs = 0, []
-        for o, nq in zip(outputs_list, nqs):
-            cost_blocks(o["pred_logits"], o["pred_boxes"], plan, self.cost_class, self.cost_bbox, self.cost_giou, self.focal_alpha,
+        for i, (o, nq) in enumerate(zip(outputs_list, nqs)):
+            cost_plan = last_plan if last_plan is not None and i == len(nqs) - 1 else plan
+            cost_blocks(o["pred_logits"], o["pred_boxes"], cost_plan, self.cost_class, self.cost_bbox, self.cost_giou, self.focal_alpha,
                         out=dev_buf[at: at + nq * plan.total], target_major=target_major)
             if runs and runs[-1][1] == nq:
                 runs[-1][2] += 1
