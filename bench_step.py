@@ -588,23 +588,33 @@ CLIP_MAX_NORM = 0.1      # reference config/RichSem/baseline_4scale.py:19 (clip_
 LR = 1e-4
 
 
-def make_optimizer(params, lr=LR):
+def make_optimizer(params, lr=LR, library=False):
     """AdamW as the reference builds it (main.py:213-214; lr / weight_decay of config/RichSem/baseline_4scale.py:7,14), one fused launch per
     step (fused optimizers do not bump the parameters' version counters; richsem_amd/param_cache.py's step hook does, so the bf16 layers'
-    packed weights follow every step)"""
+    packed weights follow every step).  ``library``: richsem_amd.optim.ClipAdamW instead -- gradient clipping and AdamW in two launches of
+    the library's own (opt-in: ``--library-optimizer``)"""
+    if library:
+        from richsem_amd.optim import ClipAdamW
+        return ClipAdamW(params, lr=lr, weight_decay=1e-4, max_norm=CLIP_MAX_NORM)
     return torch.optim.AdamW(params, lr=lr, weight_decay=1e-4, fused=True)
 
 
 def optimizer_step(opt, params):
     """what follows ``losses.backward()`` in the reference's training loop (engine.py:109-113): gradient clipping to clip_max_norm, AdamW step.
-    No host synchronisation: the norm stays on the device (``error_if_nonfinite`` is off as in the reference's call)."""
+    No host synchronisation: the norm stays on the device (``error_if_nonfinite`` is off as in the reference's call).  The library's optimizer
+    clips inside its own step."""
+    from richsem_amd.optim import ClipAdamW
+    if isinstance(opt, ClipAdamW):      # make_optimizer(library=True)
+        opt.step()
+        return
     torch.nn.utils.clip_grad_norm_(params, CLIP_MAX_NORM, foreach=True)
     opt.step()
 
 
-def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, **step_kwargs):
+def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, library=False, **step_kwargs):
     """time `steps` composed steps (forward + loss + backward); returns the dict bench.py attaches as ``full_step`` (tests: ``lr``,
-    ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model" --, ``step_kwargs``: a smaller Step)"""
+    ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model" --, ``step_kwargs``: a smaller Step;
+    ``library``: make_optimizer's switch, passed on to run_graphed)"""
     model = Step(n_img=n_img, dev=dev, **step_kwargs)
     model.stop_at = stop_at      # (profiling aid: the step cut off after a section, see tools/step_sections.sh)
     images, mask, targets = model.batch()
@@ -612,7 +622,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
     if noise_seed is not None:
         model.freeze_noise(noise_seed)
     params = [p for p in model.parameters() if p.requires_grad]
-    opt = make_optimizer(params, lr)
+    opt = make_optimizer(params, lr, library)
 
     def step(indices=None, optimize=True):
         for p in params:
@@ -702,7 +712,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
         del model
         torch.cuda.empty_cache()
         fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill", "device_geometry", "device_dn")}
-        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, **fed)
+        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, library=library, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
         traceback.print_exc(file=sys.stderr)
@@ -767,9 +777,10 @@ def _time_steps(step, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3, loss
 
 
-def _graphed_result(what, n_img, ms, loss, model, params, optimizer, grads_extra=None, model_extra=None):
+def _graphed_result(what, n_img, ms, loss, model, params, optimizer, grads_extra=None, model_extra=None, library=False):
     """the dict of run_graphed / run_graphed_device; ``grads_extra`` / ``model_extra``: None, or the keys that go with "grads" / "model\""""
-    return {"what": what, "optimizer": "AdamW(fused) + clip_grad_norm_(0.1)" if optimizer else None,
+    return {"what": what, "optimizer": ("ClipAdamW(max_norm=0.1): clipping + AdamW in two library launches" if library else
+                                        "AdamW(fused) + clip_grad_norm_(0.1)") if optimizer else None,
             "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
             "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
             **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
@@ -778,7 +789,7 @@ def _graphed_result(what, n_img, ms, loss, model, params, optimizer, grads_extra
 
 
 def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, fed_seed=None,
-                device_matcher=False, **step_kwargs):
+                device_matcher=False, library=False, **step_kwargs):
     """The composed step as a trainer can run it WITHOUT freezing the matcher: the two device-only parts -- everything up to the matcher,
     and the criterion -- each captured once, forward and backward, with ``torch.cuda.make_graphed_callables`` (HIP graphs replayed by
     autograd), the Hungarian assignment between them live on the host every step.  Eagerly the step is bound by ~2900 kernel launches
@@ -786,10 +797,10 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
     ``full_step.graphed_sections`` (``step_kwargs``: a smaller Step for the tests; ``return_model``: the trained Step and the graphed model
     part under "model" / "ga", ``images`` under "images", the training step under "step"; ``fed_seed``: Step.freeze_fed).  The packed / cast forms of the parameters are built INSIDE the captured graphs
     (richsem_amd/param_cache.py): every replay re-packs from the current masters, the frozen teacher's graph included.
-    ``device_matcher``: the device-only form instead, see :func:`run_graphed_device`."""
+    ``device_matcher``: the device-only form instead, see :func:`run_graphed_device`.  ``library``: make_optimizer's switch."""
     if device_matcher:
         return run_graphed_device(n_img, dev, steps=steps, warmup=warmup, optimizer=optimizer, noise_seed=noise_seed, return_grads=return_grads, lr=lr,
-                                  return_model=return_model, fed_seed=fed_seed, **step_kwargs)
+                                  return_model=return_model, fed_seed=fed_seed, library=library, **step_kwargs)
     model, images, mask, targets = _graphed_setup(n_img, dev, noise_seed, fed_seed, **step_kwargs)
     part_a, part_b = _ModelPart(model), _LossPart(model)
     with capture_stream() as side:      # the eager warm-up, the captures and the training steps (richsem_amd/capture.py)
@@ -811,7 +822,7 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
         torch.cuda.synchronize()
         teacher_graph, t_static = capture(lambda: model.teacher_part(images), side)
         params = [p for p in model.parameters() if p.requires_grad]
-        opt = make_optimizer(params, lr) if optimizer else None
+        opt = make_optimizer(params, lr, library) if optimizer else None
         last = {}
 
         def step():
@@ -837,11 +848,11 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
         + ("; then gradient clipping (0.1) + fused AdamW step (reference engine.py:105-113): a TRAINING step, the same thing "
            "full_step_ddp measures at N > 1" if optimizer else "; no optimizer step"),
         n_img, ms, loss, model, params, optimizer, {"indices": last["assign"]} if return_grads else None,
-        {"ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else None)
+        {"ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else None, library=library)
 
 
 def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False,
-                       fed_seed=None, **step_kwargs):
+                       fed_seed=None, library=False, **step_kwargs):
     """The training step with NO host wait between its first and last kernel: model, cost blocks, the Hungarian assignment
     (``msda_lsap_*``), frozen teacher and criterion captured forward + backward as ONE ``torch.cuda.make_graphed_callables`` callable, then
     gradient clipping + fused AdamW.  The assignment is live: every replay solves it for that replay's model outputs.  The solver's status
@@ -860,7 +871,7 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
         torch.cuda.synchronize()
         model.late_status.flush()      # (the warm-up iterations ran eagerly and pushed theirs)
         params = [p for p in model.parameters() if p.requires_grad]
-        opt = make_optimizer(params, lr) if optimizer else None
+        opt = make_optimizer(params, lr, library) if optimizer else None
 
         def step(batch_images=images):
             for p in params:
@@ -881,7 +892,7 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
         + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"),
         n_img, ms, loss, model, params, optimizer, {} if return_grads else None,
         {"ga": gw, "images": images, "step": lambda *a: _on_stream(side, lambda: step(*a)),
-         "query_of_target": model.last_qot, "status": model.last_status} if return_model else None)
+         "query_of_target": model.last_qot, "status": model.last_status} if return_model else None, library=library)
 
 
 def _on_stream(stream, fn):
@@ -991,8 +1002,12 @@ if __name__ == "__main__":
     ap.add_argument("--device-matcher", action="store_true", help="time the graphed training step in both forms: the Hungarian assignment on the "
                                                                   "host between two captured parts (twice, to show its spread) and on the device "
                                                                   "inside one captured step")
+    ap.add_argument("--library-optimizer", action="store_true", help="richsem_amd.optim.ClipAdamW (gradient clipping + AdamW in two launches of the "
+                                                                      "library's own) instead of clip_grad_norm_ + torch's fused AdamW")
     a_ = ap.parse_args()
     dn_kw = {"device_dn": True} if a_.device_dn else {}
+    if a_.library_optimizer:
+        dn_kw["library"] = True
     if a_.device_matcher:
         kw = dict(**dn_kw, steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
                   **({"device_distill": True} if a_.device_distill else {}), **({"device_geometry": True} if a_.device_geometry else {}))

@@ -904,6 +904,63 @@ int msda_ffn_forward_bf16(const uint16_t *x, const uint16_t *w1, const float *b1
                           const float *ln_weight, const float *ln_bias, float eps, int tokens, int d_model, int d_ffn,
                           uint16_t *out, msda_stream_t stream);
 
+/* Gradient clipping + AdamW + EMA of the weights in two launches (csrc/msda_optim.h, csrc/optim_api.hip; reference engine.py:110-120:
+ * clip_grad_norm_(max_norm), optimizer.step(), ema_m.update(model)).  float32 parameters, gradients and state.  The kernels read
+ * everything from DEVICE-resident tables, so a captured step follows a learning-rate schedule without being captured again:
+ *
+ *   tensors   one msda_optim_tensor per tensor: device pointers (4-byte aligned, contiguous `numel` floats each), the group it belongs to
+ *             and its step counter (a float, as torch.optim keeps it);
+ *   chunks    msda_optim_chunk: chunk -> (tensor, offset, count), count <= MSDA_OPTIM_CHUNK, no chunk spans two tensors, a tensor's chunks
+ *             in order -- filled by msda_optim_plan (host only) from the list of numel: one workgroup per chunk, so every workgroup gets
+ *             a bounded, similar amount of work whatever the tensor sizes;
+ *   groups    msda_optim_group per parameter group;   settings: msda_optim_settings, call-wide.
+ *
+ * msda_optim_sumsq: partials[c] = sum of grad^2 over chunk c (fixed order, plain stores), and every listed tensor's step += 1.
+ * msda_optim_step:  every workgroup adds the partials in one fixed order; total_norm = sqrt(sum) (stored by workgroup 0),
+ *                   coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 as torch.nn.utils.clip_grad_norm_ (max_norm <= 0: coef = 1, the
+ *                   reference's `if max_norm > 0`), then torch's AdamW per element with g' = coef * g:
+ *                   p *= 1 - lr wd;  m = b1 m + (1 - b1) g';  v = b2 v + (1 - b2) g'^2;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),
+ *                   bc = 1 - beta^step from the tensor's own counter (double, once per workgroup); where settings.ema_on and the tensor
+ *                   has an `ema` pointer also ema = decay ema + (1 - decay) p_new (reference util/utils.py:396-397).
+ *                   The gradient is READ, never written (clip_grad_norm_ scales p.grad in place; here coef * g exists only in registers).
+ *                   Non-finite gradients behave as the torch sequence: an inf gives coef = 0 (NaN at that element, a zero-gradient update
+ *                   elsewhere), a NaN gives NaN everywhere.
+ * msda_optim_ema:   ema = decay ema + (1 - decay) param over a table whose tensors carry `ema` and `param` only.
+ * Host checks (before any launch): null tables, n_chunks / n_tensors < 1, tables not aligned to 8 bytes (total_norm: 4). */
+#define MSDA_OPTIM_CHUNK 16384
+typedef struct msda_optim_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *ema;          /* NULL: no shadow */
+    float *step;         /* one float on the device */
+    int64_t numel;
+    int32_t group;
+    int32_t reserved;
+} msda_optim_tensor;
+typedef struct msda_optim_chunk {
+    int64_t offset;      /* first element, a multiple of MSDA_OPTIM_CHUNK */
+    int32_t tensor;
+    int32_t count;
+} msda_optim_chunk;
+typedef struct msda_optim_group {
+    double lr, beta1, beta2, eps, weight_decay;
+} msda_optim_group;
+typedef struct msda_optim_settings {
+    double max_norm;     /* <= 0: no clipping */
+    double ema_decay;
+    int32_t ema_on;
+    int32_t reserved;
+} msda_optim_settings;
+/* chunks may be NULL (count only); otherwise at most `capacity` entries are written and a larger need is MSDA_ERR_BAD_DIMS */
+int msda_optim_plan(const int64_t *numel, int n_tensors, msda_optim_chunk *chunks, int64_t capacity, int64_t *n_chunks);
+int msda_optim_sumsq(const msda_optim_tensor *tensors, const msda_optim_chunk *chunks, int n_chunks, double *partials, msda_stream_t stream);
+int msda_optim_step(const msda_optim_tensor *tensors, const msda_optim_chunk *chunks, int n_chunks, const double *partials,
+                    const msda_optim_group *groups, const msda_optim_settings *settings, float *total_norm, msda_stream_t stream);
+int msda_optim_ema(const msda_optim_tensor *tensors, const msda_optim_chunk *chunks, int n_chunks, const msda_optim_settings *settings,
+                   msda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ ERR_NAMES = {
 
 ABI_VERSION = 13
 DISTILL_WORKSPACE_BYTES = 16384      # MSDA_DISTILL_WORKSPACE_BYTES
+OPTIM_CHUNK = 16384                  # MSDA_OPTIM_CHUNK
 
 
 def raw_stream(dev=None):
@@ -74,6 +75,7 @@ SYMBOLS = [
     "msda_postprocess_workspace_bytes", "msda_postprocess_select", "msda_nms_f32",
     "msda_cls_packed_elems", "msda_cls_pack", "msda_cls_max_scores",
     "msda_conv_set_tiling", "msda_conv_set_ring", "msda_conv_dgrad_fused_bf16", "msda_conv_packed_elems", "msda_conv_pack_weight", "msda_conv_forward_bf16", "msda_conv_dgrad_bf16", "msda_conv_forward_workspace_bytes", "msda_conv_forward_ws_bf16", "msda_conv_dgrad_workspace_bytes", "msda_conv_dgrad_ws_bf16", "msda_pool_nhwc_bf16", "msda_groupnorm8_nhwc_bf16", "msda_groupnorm8_backward_nhwc_bf16", "msda_conv_wgrad_workspace_bytes", "msda_conv_wgrad_bf16", "msda_conv_set_wgrad_ring", "msda_conv_wgrad_group_workspace_bytes", "msda_conv_wgrad_group_bf16",
+    "msda_optim_plan", "msda_optim_sumsq", "msda_optim_step", "msda_optim_ema",
 ]
 
 
@@ -301,6 +303,14 @@ def load():
         f = getattr(L, "msda_mask_rows_" + sfx)
         f.argtypes = [vp, vp, i64, ci, vp]
         f.restype = ci
+    L.msda_optim_plan.argtypes = [vp, ci, vp, i64, ctypes.POINTER(i64)]
+    L.msda_optim_plan.restype = ci
+    L.msda_optim_sumsq.argtypes = [vp, vp, ci, vp, vp]
+    L.msda_optim_sumsq.restype = ci
+    L.msda_optim_step.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
+    L.msda_optim_step.restype = ci
+    L.msda_optim_ema.argtypes = [vp, vp, ci, vp, vp]
+    L.msda_optim_ema.restype = ci
     if L.msda_abi_version() != ABI_VERSION:
         raise ImportError(f"{path}: ABI version {L.msda_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L
