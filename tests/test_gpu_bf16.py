@@ -6,7 +6,10 @@ oracle run (in float32) on the SAME bf16-rounded inputs:
     significant bits) plus the fp32 accumulation error (~1e-6) -> tolerance 4e-3 of the tensor's largest magnitude,
     AND -- the stronger statement -- the result must equal the correctly rounded oracle value up to ONE bf16 ulp
     almost everywhere (sums are formed in fp32, never in bf16; a bf16 running sum would be off by many ulps);
-  * grad_sampling_loc / grad_attn_weight are float32 outputs of exact (bf16-valued) inputs: the fp32 tolerance 2e-4."""
+  * grad_sampling_loc / grad_attn_weight are float32 outputs of exact (bf16-valued) inputs: the fp32 tolerance 2e-4.
+The element-wise statement -- every stored element between the bf16 roundings of the float64 reference -+ the fp32 sum's bound (a bf16
+store is off by up to 2^-8 of the number, 8 significant bits), no share of elements exempt, none skipped for being small -- lives in
+tests/test_gpu_msda_bounds.py (comparator: tests/msda_ref.py)."""
 import glob
 import os
 

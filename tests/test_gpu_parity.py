@@ -5,7 +5,9 @@
   (3) size-independent properties at BASELINE.json's full sizes.
 Tolerances: fp64 1e-10 relative to the tensor's max (summation order differs, float atomics in backward);
 fp32 2e-5 for forward and 2e-4 for gradients (sums of up to Lq*16 atomically-added terms) -- far inside
-north_star's 1e-3 and the reference's own rtol 1e-2 / atol 1e-3 (ops/test.py:56)."""
+north_star's 1e-3 and the reference's own rtol 1e-2 / atol 1e-3 (ops/test.py:56).
+These are whole-tensor criteria (rel_err below: max|a-b| / max|b|); the ELEMENT-WISE statement -- a derived bound per element of every
+output, exact probes at the borders -- lives in tests/test_gpu_msda_bounds.py (comparator: tests/msda_ref.py)."""
 import glob
 import os
 
