@@ -611,10 +611,41 @@ def optimizer_step(opt, params):
     opt.step()
 
 
-def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, library=False, **step_kwargs):
+class GroupedRepack:
+    """``--grouped-repack``: a richsem_amd.repack.RepackPlan recorded around the first eager forward + backward (``recording()``), then
+    attached to the library's optimizer (``attach``: its step ends with the one refresh launch) or refreshed after any other optimizer's
+    step (``after_step``).  The captured forms of the step then hold no pack launch; ``plan`` is None when the switch is off."""
+
+    def __init__(self, on):
+        self.plan = None
+        if on:
+            from richsem_amd.repack import RepackPlan
+            self.plan = RepackPlan()
+        self._recorded = self._attached = False
+
+    def recording(self):
+        import contextlib
+        if self.plan is None or self._recorded:
+            return contextlib.nullcontext()
+        self._recorded = True
+        return self.plan.record()
+
+    def attach(self, opt):
+        from richsem_amd.optim import ClipAdamW
+        if self.plan is not None and isinstance(opt, ClipAdamW):
+            opt.attach_repack(self.plan)
+            self._attached = True
+
+    def after_step(self):
+        if self.plan is not None and not self._attached:
+            self.plan.refresh()
+
+
+def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, library=False,
+        grouped_repack=False, **step_kwargs):
     """time `steps` composed steps (forward + loss + backward); returns the dict bench.py attaches as ``full_step`` (tests: ``lr``,
-    ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model" --, ``step_kwargs``: a smaller Step;
-    ``library``: make_optimizer's switch, passed on to run_graphed)"""
+    ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model", its plan under "repack" --, ``step_kwargs``: a
+    smaller Step; ``library``: make_optimizer's switch, ``grouped_repack``: :class:`GroupedRepack`'s, both passed on to run_graphed)"""
     model = Step(n_img=n_img, dev=dev, **step_kwargs)
     model.stop_at = stop_at      # (profiling aid: the step cut off after a section, see tools/step_sections.sh)
     images, mask, targets = model.batch()
@@ -623,18 +654,22 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
         model.freeze_noise(noise_seed)
     params = [p for p in model.parameters() if p.requires_grad]
     opt = make_optimizer(params, lr, library)
+    repack = GroupedRepack(grouped_repack)
+    repack.attach(opt)
 
     def step(indices=None, optimize=True):
         for p in params:
             p.grad = None
-        loss = model(images, mask, targets, indices)
-        fwd = None
-        if model.timing:
-            fwd = torch.cuda.Event(enable_timing=True)
-            fwd.record()
-        loss.backward()
+        with repack.recording():      # (the first step only, and only with grouped_repack)
+            loss = model(images, mask, targets, indices)
+            fwd = None
+            if model.timing:
+                fwd = torch.cuda.Event(enable_timing=True)
+                fwd.record()
+            loss.backward()
         if optimize:
             optimizer_step(opt, params)
+            repack.after_step()
         return loss, fwd
 
     rows, totals, bwds = {}, [], []
@@ -664,6 +699,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
            "backward_ms": round(sum(bwds) / len(bwds), 2)}
     if return_model:
         out["model"] = model
+        out["repack"] = repack.plan
     if not graph:
         return out
     # the device part as a captured graph: the assignment of the last eager step held fixed (the matcher's host round trip cannot be captured)
@@ -712,7 +748,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
         del model
         torch.cuda.empty_cache()
         fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill", "device_geometry", "device_dn")}
-        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, library=library, **fed)
+        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, library=library, grouped_repack=grouped_repack, **fed)
     except Exception as e:      # noqa: BLE001
         import traceback
         traceback.print_exc(file=sys.stderr)
@@ -789,7 +825,7 @@ def _graphed_result(what, n_img, ms, loss, model, params, optimizer, grads_extra
 
 
 def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, fed_seed=None,
-                device_matcher=False, library=False, **step_kwargs):
+                device_matcher=False, library=False, grouped_repack=False, **step_kwargs):
     """The composed step as a trainer can run it WITHOUT freezing the matcher: the two device-only parts -- everything up to the matcher,
     and the criterion -- each captured once, forward and backward, with ``torch.cuda.make_graphed_callables`` (HIP graphs replayed by
     autograd), the Hungarian assignment between them live on the host every step.  Eagerly the step is bound by ~2900 kernel launches
@@ -797,18 +833,22 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
     ``full_step.graphed_sections`` (``step_kwargs``: a smaller Step for the tests; ``return_model``: the trained Step and the graphed model
     part under "model" / "ga", ``images`` under "images", the training step under "step"; ``fed_seed``: Step.freeze_fed).  The packed / cast forms of the parameters are built INSIDE the captured graphs
     (richsem_amd/param_cache.py): every replay re-packs from the current masters, the frozen teacher's graph included.
-    ``device_matcher``: the device-only form instead, see :func:`run_graphed_device`.  ``library``: make_optimizer's switch."""
+    ``device_matcher``: the device-only form instead, see :func:`run_graphed_device`.  ``library``: make_optimizer's switch.
+    ``grouped_repack``: :class:`GroupedRepack` -- the plan is recorded in the eager warm-up step, the graphs then hold no pack launch and the
+    one refresh follows the optimizer step (``return_model``: the plan under "repack")."""
     if device_matcher:
         return run_graphed_device(n_img, dev, steps=steps, warmup=warmup, optimizer=optimizer, noise_seed=noise_seed, return_grads=return_grads, lr=lr,
-                                  return_model=return_model, fed_seed=fed_seed, library=library, **step_kwargs)
+                                  return_model=return_model, fed_seed=fed_seed, library=library, grouped_repack=grouped_repack, **step_kwargs)
     model, images, mask, targets = _graphed_setup(n_img, dev, noise_seed, fed_seed, **step_kwargs)
     part_a, part_b = _ModelPart(model), _LossPart(model)
+    repack = GroupedRepack(grouped_repack)
     with capture_stream() as side:      # the eager warm-up, the captures and the training steps (richsem_amd/capture.py)
         pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (before anything touches a parameter; alive to the end)
         with torch.no_grad():
             outs = model.model_part(images, mask)
         idx = model.pack_indices(model.match(*outs[:4], targets), targets)
-        model.loss_part(*model.model_part(images, mask), *idx).backward()      # (eager once: workspaces of this stream, caches)
+        with repack.recording():
+            model.loss_part(*model.model_part(images, mask), *idx).backward()      # (eager once: workspaces of this stream, caches)
         for p in model.parameters():
             p.grad = None
         sample_b = tuple(o.detach().clone().requires_grad_(i < 5) for i, o in enumerate(outs)) + tuple(idx)
@@ -823,6 +863,7 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
         teacher_graph, t_static = capture(lambda: model.teacher_part(images), side)
         params = [p for p in model.parameters() if p.requires_grad]
         opt = make_optimizer(params, lr, library) if optimizer else None
+        repack.attach(opt)
         last = {}
 
         def step():
@@ -838,6 +879,7 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
             loss.backward()
             if opt is not None:
                 optimizer_step(opt, params)
+                repack.after_step()
             return loss
 
         ms, loss = _time_steps(step, steps, warmup)
@@ -848,11 +890,11 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
         + ("; then gradient clipping (0.1) + fused AdamW step (reference engine.py:105-113): a TRAINING step, the same thing "
            "full_step_ddp measures at N > 1" if optimizer else "; no optimizer step"),
         n_img, ms, loss, model, params, optimizer, {"indices": last["assign"]} if return_grads else None,
-        {"ga": ga, "images": images, "step": lambda: _on_stream(side, step)} if return_model else None, library=library)
+        {"ga": ga, "images": images, "step": lambda: _on_stream(side, step), "repack": repack.plan} if return_model else None, library=library)
 
 
 def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False,
-                       fed_seed=None, library=False, **step_kwargs):
+                       fed_seed=None, library=False, grouped_repack=False, **step_kwargs):
     """The training step with NO host wait between its first and last kernel: model, cost blocks, the Hungarian assignment
     (``msda_lsap_*``), frozen teacher and criterion captured forward + backward as ONE ``torch.cuda.make_graphed_callables`` callable, then
     gradient clipping + fused AdamW.  The assignment is live: every replay solves it for that replay's model outputs.  The solver's status
@@ -860,9 +902,11 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
     :func:`run_graphed` returns; with ``return_model`` also "query_of_target" / "status": the static tensors every replay rewrites."""
     model, images, _, _ = _graphed_setup(n_img, dev, noise_seed, fed_seed, device_matcher=True, **step_kwargs)
     whole = _WholeStep(model)
+    repack = GroupedRepack(grouped_repack)
     with capture_stream() as side:
         pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (alive to the end)
-        whole(images).backward()      # (eager once: workspaces of this stream, caches, the solver's LDS attribute)
+        with repack.recording():
+            whole(images).backward()      # (eager once: workspaces of this stream, caches, the solver's LDS attribute)
         for p in model.parameters():
             p.grad = None
         torch.cuda.synchronize()
@@ -872,6 +916,7 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
         model.late_status.flush()      # (the warm-up iterations ran eagerly and pushed theirs)
         params = [p for p in model.parameters() if p.requires_grad]
         opt = make_optimizer(params, lr, library) if optimizer else None
+        repack.attach(opt)
 
         def step(batch_images=images):
             for p in params:
@@ -881,6 +926,7 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
             model.late_status.push(model.last_status)      # (raises for the PREVIOUS step's status)
             if opt is not None:
                 optimizer_step(opt, params)
+                repack.after_step()
             return loss
 
         ms, loss = _time_steps(step, steps, warmup)
@@ -892,7 +938,7 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
         + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"),
         n_img, ms, loss, model, params, optimizer, {} if return_grads else None,
         {"ga": gw, "images": images, "step": lambda *a: _on_stream(side, lambda: step(*a)),
-         "query_of_target": model.last_qot, "status": model.last_status} if return_model else None, library=library)
+         "query_of_target": model.last_qot, "status": model.last_status, "repack": repack.plan} if return_model else None, library=library)
 
 
 def _on_stream(stream, fn):
@@ -1004,10 +1050,15 @@ if __name__ == "__main__":
                                                                   "inside one captured step")
     ap.add_argument("--library-optimizer", action="store_true", help="richsem_amd.optim.ClipAdamW (gradient clipping + AdamW in two launches of the "
                                                                       "library's own) instead of clip_grad_norm_ + torch's fused AdamW")
+    ap.add_argument("--grouped-repack", action="store_true", help="every derived form of the parameters (bf16 casts, packed weights) refreshed from "
+                                                                   "the masters in ONE launch after the optimizer step (richsem_amd/repack.py) "
+                                                                   "instead of rebuilt by every cache inside the captured graphs")
     a_ = ap.parse_args()
     dn_kw = {"device_dn": True} if a_.device_dn else {}
     if a_.library_optimizer:
         dn_kw["library"] = True
+    if a_.grouped_repack:
+        dn_kw["grouped_repack"] = True
     if a_.device_matcher:
         kw = dict(**dn_kw, steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
                   **({"device_distill": True} if a_.device_distill else {}), **({"device_geometry": True} if a_.device_geometry else {}))

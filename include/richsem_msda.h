@@ -961,6 +961,66 @@ int msda_optim_step(const msda_optim_tensor *tensors, const msda_optim_chunk *ch
 int msda_optim_ema(const msda_optim_tensor *tensors, const msda_optim_chunk *chunks, int n_chunks, const msda_optim_settings *settings,
                    msda_stream_t stream);
 
+/* Grouped re-pack: every derived form of the trained parameters (bf16 casts, lin256's fragment order, the feed-forward kernel's W2 order,
+ * the convolutions' forward and input-gradient packs) rebuilt from the fp32 masters in ONE launch over a device-resident job table
+ * (csrc/msda_repack.h, csrc/repack_api.hip).  Every form is a destination-indexed gather: an output element is one source element, at
+ * most multiplied by one fp32 scale, rounded to bf16 (nearest even) -- bit-equal to what the single-form entry points
+ * (msda_lin256_pack_bf16, msda_ffn_pack_w2_bf16, msda_conv_pack_weight) write from the same masters.
+ *
+ *   jobs      one msda_repack_job per destination tensor.  The source is the concatenation of `n_segs` fp32 segments (4-byte aligned,
+ *             contiguous; a segment may be a row slice of a larger parameter); seg_end[s] is the cumulative end of segment s, counted in
+ *             rows for the lin256 kinds and in elements for the flat kinds; the convolution kinds read src[0] only.
+ *   chunks    msda_repack_chunk: chunk -> (job, offset, count) in destination elements, count <= MSDA_REPACK_CHUNK, no chunk spans two
+ *             jobs -- filled by msda_repack_plan: one workgroup per chunk, 16 bytes of destination per thread and store.
+ *
+ * kinds (n_dst = destination elements; dims as listed, the rest 0):
+ *   MSDA_REPACK_CAST      bf16 of the flat concatenation, zero from its end up to n_dst
+ *   MSDA_REPACK_COPY      fp32 copy of the flat concatenation, zero from its end up to n_dst
+ *   MSDA_REPACK_LIN256    dims[0] = N (a multiple of 64, n_dst = 256 N): msda_lin256_pack_bf16 of the (N x 256) row concatenation, rows
+ *                         from its end up to N zero
+ *   MSDA_REPACK_LIN256_T  dims[0] = N: msda_lin256_pack_bf16 of the transpose of the (256 x N) row concatenation
+ *   MSDA_REPACK_FFN_W2    dims[0] = d_model, dims[1] = d_ffn (a multiple of 32, n_dst = d_model d_ffn): msda_ffn_pack_w2_bf16
+ *   MSDA_REPACK_CONV      dims = Cout, Cin, KH, KW, Kpad (KH KW Cin rounded up to 32; n_dst = Cout Kpad): msda_conv_pack_weight
+ *   MSDA_REPACK_CONV_T    dims = Cout, Cin, KH, KW of the SOURCE, Kpad (KH KW Cout rounded up to 32; n_dst = Cin Kpad): msda_conv_pack_weight
+ *                         of w_t[ci][co][kh][kw] = w[co][ci][KH-1-kh][KW-1-kw] * scale[co], the product taken in fp32 (`scale`: Cout floats)
+ *
+ * msda_repack_plan (host only) checks the HOST copy of the job table -- null dst / src / scale (MSDA_ERR_NULL_POINTER), a dst not aligned
+ * to 16 bytes or a src / scale not aligned to 4 (MSDA_ERR_MISALIGNED), an unknown kind, n_segs outside 1..MSDA_REPACK_MAX_SEGS, segment
+ * ends that do not grow, dims and n_dst that do not fit the kind (MSDA_ERR_BAD_DIMS), n_dst or the chunk count >= 2^31
+ * (MSDA_ERR_TOO_LARGE) -- and writes the chunk table; chunks may be NULL (count only), a need above `capacity` is MSDA_ERR_BAD_DIMS.  A
+ * job with n_dst = 0 has no chunks, and only its kind and n_segs are checked.
+ * msda_repack: one launch of n_chunks workgroups over DEVICE copies of both tables (8-byte aligned); n_chunks = 0 launches nothing,
+ * n_chunks < 0 is MSDA_ERR_BAD_DIMS.  No host synchronisation; capturable. */
+#define MSDA_REPACK_CHUNK 8192
+#define MSDA_REPACK_MAX_SEGS 8
+enum msda_repack_kind {
+    MSDA_REPACK_CAST = 0,
+    MSDA_REPACK_COPY = 1,
+    MSDA_REPACK_LIN256 = 2,
+    MSDA_REPACK_LIN256_T = 3,
+    MSDA_REPACK_FFN_W2 = 4,
+    MSDA_REPACK_CONV = 5,
+    MSDA_REPACK_CONV_T = 6
+};
+typedef struct msda_repack_job {
+    void *dst;                                 /* 16-byte aligned */
+    const float *scale;                        /* MSDA_REPACK_CONV_T only, else NULL */
+    const float *src[MSDA_REPACK_MAX_SEGS];
+    int32_t seg_end[MSDA_REPACK_MAX_SEGS];     /* cumulative: rows (lin256 kinds) or elements (flat kinds) */
+    int64_t n_dst;                             /* destination elements */
+    int32_t kind;
+    int32_t n_segs;
+    int32_t dims[6];
+    int32_t reserved[2];
+} msda_repack_job;
+typedef struct msda_repack_chunk {
+    int64_t offset;      /* first destination element, a multiple of MSDA_REPACK_CHUNK */
+    int32_t job;
+    int32_t count;
+} msda_repack_chunk;
+int msda_repack_plan(const msda_repack_job *jobs, int n_jobs, msda_repack_chunk *chunks, int64_t capacity, int64_t *n_chunks);
+int msda_repack(const msda_repack_job *jobs, const msda_repack_chunk *chunks, int n_chunks, msda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,18 @@ ERR_NAMES = {
 ABI_VERSION = 13
 DISTILL_WORKSPACE_BYTES = 16384      # MSDA_DISTILL_WORKSPACE_BYTES
 OPTIM_CHUNK = 16384                  # MSDA_OPTIM_CHUNK
+REPACK_CHUNK = 8192                  # MSDA_REPACK_CHUNK
+REPACK_MAX_SEGS = 8                  # MSDA_REPACK_MAX_SEGS
+
+
+def repack_dtypes():
+    """numpy dtypes of ``msda_repack_job`` / ``msda_repack_chunk`` (include/richsem_msda.h) -> (job, chunk)"""
+    import numpy as np
+    job = np.dtype([("dst", "<u8"), ("scale", "<u8"), ("src", "<u8", (REPACK_MAX_SEGS,)), ("seg_end", "<i4", (REPACK_MAX_SEGS,)), ("n_dst", "<i8"),
+                    ("kind", "<i4"), ("n_segs", "<i4"), ("dims", "<i4", (6,)), ("reserved", "<i4", (2,))])
+    chunk = np.dtype([("offset", "<i8"), ("job", "<i4"), ("count", "<i4")])
+    assert (job.itemsize, chunk.itemsize) == (160, 16)
+    return job, chunk
 
 
 def raw_stream(dev=None):
@@ -76,6 +88,7 @@ SYMBOLS = [
     "msda_cls_packed_elems", "msda_cls_pack", "msda_cls_max_scores",
     "msda_conv_set_tiling", "msda_conv_set_ring", "msda_conv_dgrad_fused_bf16", "msda_conv_packed_elems", "msda_conv_pack_weight", "msda_conv_forward_bf16", "msda_conv_dgrad_bf16", "msda_conv_forward_workspace_bytes", "msda_conv_forward_ws_bf16", "msda_conv_dgrad_workspace_bytes", "msda_conv_dgrad_ws_bf16", "msda_pool_nhwc_bf16", "msda_groupnorm8_nhwc_bf16", "msda_groupnorm8_backward_nhwc_bf16", "msda_conv_wgrad_workspace_bytes", "msda_conv_wgrad_bf16", "msda_conv_set_wgrad_ring", "msda_conv_wgrad_group_workspace_bytes", "msda_conv_wgrad_group_bf16",
     "msda_optim_plan", "msda_optim_sumsq", "msda_optim_step", "msda_optim_ema",
+    "msda_repack_plan", "msda_repack",
 ]
 
 
@@ -311,6 +324,10 @@ def load():
     L.msda_optim_step.restype = ci
     L.msda_optim_ema.argtypes = [vp, vp, ci, vp, vp]
     L.msda_optim_ema.restype = ci
+    L.msda_repack_plan.argtypes = [vp, ci, vp, i64, ctypes.POINTER(i64)]
+    L.msda_repack_plan.restype = ci
+    L.msda_repack.argtypes = [vp, vp, ci, vp]
+    L.msda_repack.restype = ci
     if L.msda_abi_version() != ABI_VERSION:
         raise ImportError(f"{path}: ABI version {L.msda_abi_version()} != expected {ABI_VERSION}; rebuild")
     _lib = L

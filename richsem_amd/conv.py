@@ -5,11 +5,12 @@ it in the backbones (frozen / eval-mode BatchNorm folded into scale and shift --
 clip/model.py:16-27), an optional residual and an optional ReLU, all applied in the kernel's epilogue.  ``ConvAffine`` is the inference form;
 ``ConvAffineFunction`` / ``ConvBNAct`` add the input and weight gradients.
 """
+import copy
 import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, param_cache
 from .param_cache import VersionCache, capturing
 
 
@@ -261,15 +262,52 @@ class PackCache:
     gradient, refreshed when the parameter (or the scale) has been modified in place -- i.e. after any optimizer step (fused ones
     included: richsem_amd/param_cache.py bumps the version counters of what an optimizer step updates), a ``load_state_dict`` or any
     other in-place op that autograd's version counter sees.  Writes through ``param.data`` bypass that counter: call :meth:`clear`
-    after them.  During a graph capture :meth:`get` packs on every call and keeps nothing (param_cache.py, rule 2)."""
+    after them.  During a graph capture :meth:`get` packs on every call and keeps nothing (param_cache.py, rule 2).
+
+    A slot bound to a RepackPlan (repack.py) hands out the plan's buffer: a version mismatch refreshes the whole plan in one launch, a
+    capture launches nothing.  A ``copy.deepcopy`` of a cache with a bound slot is unbound (and empty)."""
+
+    _bound = None      # transposed -> repack.Binding, once a plan has bound a slot
 
     def __init__(self):
         self._slots = {}
 
     def clear(self):
         self._slots.clear()
+        for b in (self._bound or {}).values():
+            b.ver = None
+
+    def __deepcopy__(self, memo):
+        if self._bound:
+            return type(self)()
+        new = type(self).__new__(type(self))
+        memo[id(self)] = new
+        new.__dict__.update(copy.deepcopy(self.__dict__, memo))
+        return new
+
+    def _unbind_slot(self, b):
+        if self._bound and self._bound.get(b.slot) is b:
+            del self._bound[b.slot]
+            self._slots.pop(b.slot, None)
 
     def get(self, weight, scale, transposed):
+        b = self._bound.get(transposed) if self._bound else None
+        if b is not None:
+            val = b.get((weight, scale) if transposed else (weight,))
+            if val is not param_cache.UNBOUND:
+                return val
+            self._unbind_slot(b)
+        elif param_cache._RECORDING is not None and not capturing(weight) and not param_cache._RECORDING.declined(self, transposed):
+            packed, b = param_cache._RECORDING._record(self, transposed, (weight, scale) if transposed else (weight,),
+                                                       lambda: _pack_form(weight, scale, transposed))
+            if b is not None:
+                if self._bound is None:
+                    self._bound = {}
+                self._bound[transposed] = b
+            else:
+                self._slots[transposed] = ((weight.data_ptr(), weight._version, scale.data_ptr() if transposed else 0,
+                                            scale._version if transposed else 0, tuple(weight.shape)), packed)
+            return packed
         if capturing(weight):
             return _pack_form(weight, scale, transposed)
         ver = (weight.data_ptr(), weight._version, scale.data_ptr() if transposed else 0, scale._version if transposed else 0,
@@ -286,7 +324,10 @@ def _pack_form(weight, scale, transposed):
     w = weight.detach().float()
     if transposed:
         w = (w * scale.view(-1, 1, 1, 1)).flip(2, 3).permute(1, 0, 2, 3)          # (Cin, Cout, KH, KW)
-    return _pack(w.contiguous())
+    packed = _pack(w.contiguous())
+    if param_cache._RECORDING is not None:      # (a recording RepackPlan: the same form, from the master, as one job of its launch)
+        param_cache.note("conv_t" if transposed else "conv", packed, [weight], scale if transposed else None)
+    return packed
 
 
 def _packed_for(weight, scale, transposed, cache=None):

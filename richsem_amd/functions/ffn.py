@@ -11,7 +11,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from .. import _lib
+from .. import _lib, param_cache
 from .linear import WgradGroup, deferrable, lin256, lin256_pack, linear_wgrad, linear_wgrad_bf16
 
 
@@ -111,8 +111,15 @@ def pack_ffn(linear1_weight, linear1_bias, linear2_weight):
     linear2.weight in the fused kernel's hidden-column order and its transpose in lin256's order, linear1.bias as float32."""
     w1_16 = linear1_weight.detach().to(torch.bfloat16).contiguous()
     w2_16 = linear2_weight.detach().to(torch.bfloat16).contiguous()
-    return {"w1_16": w1_16, "w1_packed": lin256_pack(w1_16), "w2_ffn": pack_w2_bf16(w2_16), "w2t_packed": lin256_pack(w2_16.t().contiguous()),
-            "b1_32": linear1_bias.detach().float().contiguous()}
+    pk = {"w1_16": w1_16, "w1_packed": lin256_pack(w1_16), "w2_ffn": pack_w2_bf16(w2_16), "w2t_packed": lin256_pack(w2_16.t().contiguous()),
+          "b1_32": linear1_bias.detach().float().contiguous()}
+    if param_cache.recording() is not None:      # (a recording RepackPlan, richsem_amd/repack.py: the same forms as jobs over the masters)
+        param_cache.note("cast", w1_16, [linear1_weight])
+        param_cache.note("lin256", pk["w1_packed"], [linear1_weight])
+        param_cache.note("ffn_w2", pk["w2_ffn"], [linear2_weight])
+        param_cache.note("lin256_t", pk["w2t_packed"], [linear2_weight])
+        param_cache.note("copy", pk["b1_32"], [linear1_bias])
+    return pk
 
 
 class FusedFFNCachedFunction(Function):

@@ -5,7 +5,7 @@ transposed.  Used by the bf16 module path for the four projections of MSDeformAt
 feed-forward block's backward."""
 import torch
 
-from .. import _lib
+from .. import _lib, param_cache
 from ..conv import wgrad_group_launch, wgrad_launch
 from ..param_cache import VersionCache  # noqa: F401  (the caches' home: richsem_amd/param_cache.py)
 from .fused import mask_rows_
@@ -193,6 +193,12 @@ def pack_linear256(weights, biases):
     """The forms :class:`Lin256Function` runs a (stack of) ``nn.Linear(256, n_i)`` from: the weights concatenated along the output
     dimension as bf16 (``w16``, for the input gradient), in lin256's fragment order (``packed``), the transposed weight packed the
     same way when the stack is 256 wide (``packed_t``: the input gradient is then a K = 256 product too), and the float32 bias."""
+    pk = _linear256_forms(weights, biases)
+    _note_linear256(pk, weights, biases)
+    return pk
+
+
+def _linear256_forms(weights, biases):
     w = torch.cat([t.detach() for t in weights], 0) if len(weights) > 1 else weights[0].detach()
     b = torch.cat([t.detach() for t in biases], 0) if len(biases) > 1 else biases[0].detach()
     w16 = w.to(torch.bfloat16).contiguous()
@@ -202,6 +208,25 @@ def pack_linear256(weights, biases):
             "b32": b.float().contiguous(), "rows": [int(t.shape[0]) for t in weights]}
 
 
+def _note_linear256(pk, weights, biases):
+    """(a recording RepackPlan, richsem_amd/repack.py) the forms of ``pk`` as jobs over the fp32 masters; rows the masters do not have
+    are the zero padding"""
+    if param_cache.recording() is None:
+        return
+    param_cache.note("cast", pk["w16"], weights)
+    param_cache.note("lin256", pk["packed"], weights)
+    if pk["packed_t"] is not None:
+        param_cache.note("lin256_t", pk["packed_t"], weights)
+    param_cache.note("copy", pk["b32"], biases)
+
+
+def lin256_pack_transposed(weight):
+    """:func:`lin256_pack` of the transpose of a (256, n) fp32 weight (a feed-forward block's ``linear2.weight``), n % 64 == 0"""
+    packed = lin256_pack(weight.detach().to(torch.bfloat16).t().contiguous())
+    param_cache.note("lin256_t", packed, [weight])
+    return packed
+
+
 def pack_linear256_padded(weight, bias):
     """:func:`pack_linear256` for a layer with fewer than 64 outputs (the box heads' 256 -> 4): the weight padded with zero rows to 64;
     the caller takes the first ``out_features`` columns of the result"""
@@ -209,8 +234,9 @@ def pack_linear256_padded(weight, bias):
     w = torch.zeros((64, 256), dtype=weight.dtype, device=weight.device)
     b = torch.zeros(64, dtype=bias.dtype, device=bias.device)
     w[:n], b[:n] = weight.detach(), bias.detach()
-    pk = pack_linear256([w], [b])
+    pk = _linear256_forms([w], [b])
     pk["rows"] = [n]
+    _note_linear256(pk, [weight], [bias])
     return pk
 
 

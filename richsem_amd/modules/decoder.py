@@ -25,6 +25,7 @@ from torch import nn
 
 from ..functions.linear import (wgrad_boundary, WgradGroup, Lin256Function, Lin256NarrowFunction, LinearBf16CachedFunction, StackedValueProjFunction, VersionCache, pack_linear256,
                                 pack_linear256_padded)
+from ..param_cache import cast_bf16
 
 
 def inverse_sigmoid(x, eps=1e-3):
@@ -64,7 +65,7 @@ class MLP(nn.Module):
                 elif w.shape[1] == 256 and w.shape[0] < 64:
                     forms.append(("lin256pad", pack_linear256_padded(w, b)))
                 else:
-                    forms.append(("gemm", (w.detach().to(torch.bfloat16).contiguous(), b.detach().to(torch.bfloat16).contiguous())))
+                    forms.append(("gemm", (cast_bf16(w), cast_bf16(b))))
             return forms
         forms = self._packs.get(ps, build)
         # the 256-wide layers' weight gradients in one launch (functions/linear.py: WgradGroup) unless a caller's group is active

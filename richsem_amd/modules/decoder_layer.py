@@ -26,7 +26,8 @@ from torch import nn
 
 from ..functions.attention import masked_self_attention
 from ..functions.ffn import AddLayerNormFunction, FFNSmallFunction
-from ..functions.linear import Lin256Function, VersionCache, wgrad_boundary, WgradGroup, lin256_pack, pack_linear256
+from ..functions.linear import Lin256Function, VersionCache, wgrad_boundary, WgradGroup, lin256_pack_transposed, pack_linear256
+from ..param_cache import cast_bf16
 from .ms_deform_attn import MSDeformAttn
 
 
@@ -75,8 +76,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
             return {"qk": pack_linear256([w[:512]], [b[:512]]), "v": pack_linear256([w[512:]], [b[512:]]),
                     "o": pack_linear256([a.out_proj.weight], [a.out_proj.bias]),
                     "w1": pack_linear256([self.linear1.weight], [self.linear1.bias]),
-                    "w2_16": self.linear2.weight.detach().to(torch.bfloat16).contiguous(),
-                    "w2t": lin256_pack(self.linear2.weight.detach().to(torch.bfloat16).t().contiguous())}
+                    "w2_16": cast_bf16(self.linear2.weight), "w2t": lin256_pack_transposed(self.linear2.weight)}
         return self._packs.get(ps, build)
 
     def forward_batch_first(self, x, query_pos, reference_points, value, lsi, shapes, attn_mask):

@@ -20,6 +20,7 @@ from torch import nn
 
 from ..functions import MaskRows, MSDeformAttnFunction, MSDeformAttnFusedFunction
 from ..functions.linear import wgrad_boundary, WgradGroup, Lin256Function, LinearBf16CachedFunction, VersionCache, pack_linear256
+from ..param_cache import cast_bf16
 
 
 def _is_power_of_2(n):
@@ -86,9 +87,9 @@ class MSDeformAttn(nn.Module):
         them has been modified in place (optimizer step, load_state_dict; see :meth:`invalidate_bf16_cache` for ``.data`` writes)"""
         ps = (self.value_proj.weight, self.value_proj.bias, self.sampling_offsets.weight, self.sampling_offsets.bias,
               self.attention_weights.weight, self.attention_weights.bias, self.output_proj.weight, self.output_proj.bias)
-        b16 = lambda t: t.detach().to(torch.bfloat16).contiguous()
-        return self._bf16.get(ps, lambda: {"wv": b16(ps[0]), "bv": b16(ps[1]), "wq": b16(torch.cat((ps[2], ps[4]), 0)),
-                                           "bq": b16(torch.cat((ps[3], ps[5]), 0)), "wo": b16(ps[6]), "bo": b16(ps[7])})
+        b16 = cast_bf16
+        return self._bf16.get(ps, lambda: {"wv": b16(ps[0]), "bv": b16(ps[1]), "wq": b16(ps[2], ps[4]),
+                                           "bq": b16(ps[3], ps[5]), "wo": b16(ps[6]), "bo": b16(ps[7])})
 
     def _lin256_packs(self):
         ps = (self.value_proj.weight, self.value_proj.bias, self.sampling_offsets.weight, self.sampling_offsets.bias,

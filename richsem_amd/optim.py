@@ -99,6 +99,7 @@ class ClipAdamW(torch.optim.Optimizer):
         self.max_norm = float(max_norm)
         self.ema_on = False
         self._ema = None
+        self._repack = None
         self._table = self._table_sig = None
         self._captured = []          # tables built during a capture: alive (and unchanged) as long as the optimizer
         self._spare = []
@@ -169,6 +170,11 @@ class ClipAdamW(torch.optim.Optimizer):
         ema._opt = self
         self._epoch += 1
         self._hyper_key = None
+
+    def attach_repack(self, plan):
+        """end every ``step()`` -- eager or captured -- with ``plan.refresh()`` (richsem_amd/repack.py): the derived forms of the
+        parameters follow the masters in one more launch on the same stream; ``None`` detaches"""
+        self._repack = plan
 
     def folded(self):
         """ids of the parameters whose shadows the last ``step()`` updated"""
@@ -291,6 +297,9 @@ class ClipAdamW(torch.optim.Optimizer):
             _lib.check(L.msda_optim_sumsq(table.tensors_ptr, table.chunks_ptr, table.n_chunks, table.partials.data_ptr(), stream))
             _lib.check(L.msda_optim_step(table.tensors_ptr, table.chunks_ptr, table.n_chunks, table.partials.data_ptr(), hyper + _GROUPS_AT,
                                          hyper, self.total_norm.data_ptr(), stream))
+        if self._repack is not None:      # (the step hook records what the forms were refreshed from, once it has bumped the versions)
+            self._repack.refresh(_snapshot=False)
+            self._repack._stepped = True
         return loss
 
 
