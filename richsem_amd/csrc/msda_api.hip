@@ -17,6 +17,7 @@
 #include "msda_host.h"
 #include "msda_direct.h"
 #include "msda_levelsum.h"
+#include "msda_roles.h"
 #include "msda_prep.h"
 #include "msda_band.h"
 #include "msda_rps.h"
@@ -90,7 +91,7 @@ struct Problem {
     std::vector<int64_t> shapes, lsi;  // host mirrors
 };
 
-std::atomic<int> g_fwd_variant{0}, g_bwd_variant{0}, g_bwd_cpl{0}, g_levelsum{1}, g_fwd_prep_fused{1}, g_bwd_split{1};
+std::atomic<int> g_fwd_variant{0}, g_bwd_variant{0}, g_bwd_cpl{0}, g_levelsum{1}, g_fwd_prep_fused{1}, g_bwd_split{1}, g_bwd_dd_roles{1}, g_bwd_dd_roles_calls{0};
 thread_local int g_tl_fwd_variant = -1;      // >= 0: the forward variant of THIS call (set by a caller inside the library that has already chosen)
 
 // ---- launch profiler: pre-created event pairs, one per logged call -----------------------------
@@ -639,6 +640,29 @@ hipError_t launch_bwd_split(const Problem &pb, const TV *value, const int64_t *s
     return hipGetLastError();
 }
 
+// ---- level-sum and split workgroups in one launch (msda_roles.h): decoder-shaped calls, fp32 storage, P = 4 ----------------------------
+// returns hipErrorNotSupported when windows of this launch's size cannot take every level (the call then takes two launches).
+hipError_t launch_bwd_dd_roles(const Problem &pb, const float *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
+                               const float *aw, const float *grad_out, float *grad_value, float *grad_loc, float *grad_aw,
+                               const msda::DirectGeom &g, hipStream_t stream)
+{
+    msda::LevelSumGeom lg;
+    size_t window = 0;
+    if (msda::plan_levelsum(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data(), lg, window, msda::kDdRolesLdsKb) !=
+        all_levels_mask(pb.L))
+        return hipErrorNotSupported;
+    const msda::DdRoles r = msda::plan_dd_roles<msda::kDdRolesThreads>((int64_t)pb.N * pb.Lq * pb.M);
+    const uint64_t grid = (uint64_t)r.sp_first + (uint64_t)msda::levelsum_grid(lg);
+    if (grid > 0x7fffffffu) return hipErrorNotSupported;
+    const size_t lds = msda::dd_roles_lds_bytes(pb.L, window);
+    auto kern = &msda::bwd_dd_roles_kernel<float, msda::kDdRolesThreads>;
+    hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(msda::kDdRolesThreads), lds, stream, value, shapes, lsi, loc, aw, grad_out, grad_value,
+                       grad_loc, grad_aw, lg, g, r);
+    return hipGetLastError();
+}
+
 // ---- bf16 storage (value / out / grad_out / grad_value), fp32 compute: the fp32 scratch image of grad_value and its one rounding -------
 bool bf16_scratch(hipStream_t stream, size_t n_floats, float **out)
 {
@@ -690,6 +714,7 @@ __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restr
 //   ... a launch error there          the profile record is given back              the profile record stays
 //   level-sum backward                f32: any subset of levels, the rest by        only when it takes ALL levels; else fp32 scratch + zero-fill +
 //                                     atomics after a zero-fill of grad_value;      direct kernel + one rounding pass
+//   level-sum + split in one launch   yes (bwd_dd_roles; P = 4, loc / aw 16-B aligned)  no: two launches (not measured there)
 //   bwd_direct_cpl option             honoured                                      ignored
 //   direct backward adds grad_value   into grad_value                               into the fp32 scratch (null when level-sum took everything)
 //   no scratch during stream capture  n/a                                           MSDA_ERR_BAD_DIMS
@@ -859,7 +884,21 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
     ProfileScope prof(1, 1, (int)sizeof(TV), pb, stream);
     if constexpr (std::is_same<T, float>::value) {
         // (forking the level-sum kernel onto a second stream beside the direct kernel was tried: the cross-stream fork / join costs
-        // more than the overlap gains on a 90 us call -- 113 vs 96 us)
+        // more than the overlap gains on a 90 us call -- 113 vs 96 us; what runs the two jobs in one pass is the role kernel right below)
+        // decoder-shaped calls (every level summed in LDS, the split kernel for the other two gradients): both jobs in ONE launch whose
+        // workgroups are of two kinds (msda_roles.h: 65.9-66.7 against 70.0-70.2 us on call Dd); bwd_dd_roles = 0 keeps the two launches
+        // below.  bf16 storage keeps them too: the one-launch form has not been measured there.
+        if constexpr (!kBf16) {
+            if (g_bwd_dd_roles.load() && ls_levels == all_levels && g_bwd_split.load() && split_fits(pb, C) && split_small(pb) && P == 4 &&
+                aligned(16, {loc, aw})) {
+                e = launch_bwd_dd_roles(pb, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, g, stream);
+                if (e == hipSuccess) {
+                    ++g_bwd_dd_roles_calls;
+                    return MSDA_OK;
+                }
+                if (e != hipErrorNotSupported) return hip_fail(e, "launch of the level-sum / split role kernel");
+            }
+        }
         if (ls_levels) {
             // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
             // for element alignment only)
@@ -1054,6 +1093,8 @@ const Option *find_option(const char *key)
         {"tile_persist", &msda::tiled_options().persist, 0, 65536, 0},
         {"bwd_levelsum", &g_levelsum, 0, 1, 0},
         {"bwd_split", &g_bwd_split, 0, 1, 0},
+        {"bwd_dd_roles", &g_bwd_dd_roles, 0, 1, 0},
+        {"bwd_dd_roles_calls", &g_bwd_dd_roles_calls, 0, -1, 0},   // read-only: calls that took the one-launch path
         {"profile_filter", &g_prof_filter, 0, 47, 0},
         {"levelsum_lds_kb", &msda::levelsum_lds_kb(), 8, 150, 0},
         {"tile_grow", &msda::tiled_options().grow, 0, 1, 0},

@@ -359,19 +359,17 @@ __global__ __launch_bounds__(kDirectThreads, OCC) void fwd_direct_prep_kernel(
 // other -- gathers, then three shuffle reductions, per point: sixteen rounds of memory latency per wave, 33 us at 1092 queries.  Here a
 // lane has its L*P/4 points' sixteen corner gathers in flight at once and the three sums of a point meet over the item's 8 channel lanes
 // in three DPP steps (group8_sum).
-template <typename TV, int PPG>
-__global__ __launch_bounds__(kDirectThreads, 4) void bwd_split_kernel(
-    const TV *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
-    const float *__restrict__ loc, const float *__restrict__ aw, const TV *__restrict__ grad_out,
-    float *__restrict__ grad_loc, float *__restrict__ grad_aw, const DirectGeom g)
+// The body of workgroup `bid` of THREADS threads (THREADS / 32 items), the level table `lv` already in LDS: a function of its own so
+// that a launch whose workgroups do different jobs (msda_roles.h) can hand some of them this one.
+template <typename TV, int PPG, int THREADS>
+__device__ __forceinline__ void bwd_split_body(unsigned bid, const LevelGeom *lv, const TV *__restrict__ value,
+                                               const float *__restrict__ loc, const float *__restrict__ aw, const TV *__restrict__ grad_out,
+                                               float *__restrict__ grad_loc, float *__restrict__ grad_aw, const DirectGeom &g)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    LevelGeom *lv = reinterpret_cast<LevelGeom *>(smem);
-    load_levels(lv, shapes, lsi, g.L);
     const int lane = threadIdx.x & (kWave - 1);
     const int j = lane & 7, pg = (lane >> 3) & (kSplitGroups - 1);
     const long long n_items = (long long)g.N * g.Lq * g.M;
-    const long long item_raw = ((long long)blockIdx.x * kDirectThreads + threadIdx.x) >> 5;
+    const long long item_raw = ((long long)bid * THREADS + threadIdx.x) >> 5;
     const bool live = item_raw < n_items;
     const long long item = live ? item_raw : n_items - 1;      // (a valid item whatever the lane: the reductions need every lane)
     const int m = (int)(item % g.M);
@@ -434,6 +432,18 @@ __global__ __launch_bounds__(kDirectThreads, 4) void bwd_split_kernel(
             *reinterpret_cast<Pack<float, 2> *>(grad_loc + (item * LP + gp) * 2) = gl;
         }
     }
+}
+
+template <typename TV, int PPG>
+__global__ __launch_bounds__(kDirectThreads, 4) void bwd_split_kernel(
+    const TV *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
+    const float *__restrict__ loc, const float *__restrict__ aw, const TV *__restrict__ grad_out,
+    float *__restrict__ grad_loc, float *__restrict__ grad_aw, const DirectGeom g)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    LevelGeom *lv = reinterpret_cast<LevelGeom *>(smem);
+    load_levels(lv, shapes, lsi, g.L);
+    bwd_split_body<TV, PPG, kDirectThreads>(blockIdx.x, lv, value, loc, aw, grad_out, grad_loc, grad_aw, g);
 }
 
 // TV = storage type of value / grad_out.  grad_value is accumulated with atomics in the compute type T (in bf16 mode it

@@ -42,13 +42,14 @@ struct LevelSumGeom {
 // (MI355X, call E: 2248 -> 1142 us on uniform-random locations).
 // Otherwise: only the levels that fit LDS whole and receive at least two sampling points per pixel (there is something
 // to merge); the rest stays with the direct kernel's row atomics.
+// budget_kb: the window size to plan for; 0 = the levelsum_lds_kb option.
 inline unsigned plan_levelsum(int N, int S, int M, int D, int L, int Lq, int P, const int64_t *shapes,
-                              const int64_t *lsi, LevelSumGeom &g, size_t &lds_bytes)
+                              const int64_t *lsi, LevelSumGeom &g, size_t &lds_bytes, int budget_kb = 0)
 {
     lds_bytes = 0;
     if (L > 32 || D > 128 || (int64_t)Lq * P > 1048576) { g = LevelSumGeom{}; return 0; }
     const size_t px_bytes = (size_t)kLsChan * sizeof(double);
-    const size_t budget = std::min<size_t>(kLsLdsBudget, (size_t)std::max(8, levelsum_lds_kb().load()) * 1024);
+    const size_t budget = std::min<size_t>(kLsLdsBudget, (size_t)std::max(8, budget_kb ? budget_kb : levelsum_lds_kb().load()) * 1024);
     for (int all = 1; all >= 0; --all) {
         g = LevelSumGeom{};
         g.N = N; g.S = S; g.M = M; g.D = D; g.L = L; g.Lq = Lq; g.P = P;
@@ -90,17 +91,15 @@ inline int levelsum_grid(const LevelSumGeom &g)
 
 // P4: exactly four points per level (RichSem) -- their locations / weights are loaded as whole vectors.
 // TV: storage type of grad_out / grad_value (float, or bf16_t: the f64 window is rounded to bf16 once, at the store).
-template <bool P4, typename TV = float>
-__global__ __launch_bounds__(kLsThreads) void bwd_levelsum_kernel(const float *__restrict__ loc,
-                                                                  const float *__restrict__ aw,
-                                                                  const TV *__restrict__ grad_out,
-                                                                  TV *__restrict__ grad_value, const LevelSumGeom g)
+// The body of one workgroup: entry `bid` of the levelsum_grid() order, THREADS threads, `win` = its window in LDS.  A function of its
+// own so that a launch whose workgroups do different jobs (msda_roles.h) can hand some of them this one.  (g by value: by reference
+// bwd_levelsum_kernel comes out with other registers, 27 VGPRs / 54 SGPRs for 29 / 48.)
+template <bool P4, typename TV, int THREADS>
+__device__ __forceinline__ void levelsum_body(int bid, double *win, const float *loc, const float *aw, const TV *grad_out,
+                                              TV *grad_value, const LevelSumGeom g)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *win = reinterpret_cast<double *>(smem);
-
     int pair, t;
-    if (!decode_block(blockIdx.x, g.N * g.M, g.nlev * g.nslices, pair, t)) return;
+    if (!decode_block(bid, g.N * g.M, g.nlev * g.nslices, pair, t)) return;
     // the slices of one level are neighbours in the XCD-local order: they read the same loc / attn lines
     // (entries are taken LAST FIRST -- round 5: the coarse levels, whose single window takes every point of the call, are the long workgroups;
     // launched behind the 512 short row-band workgroups of level 0 they ran as a half-empty last round)
@@ -110,11 +109,11 @@ __global__ __launch_bounds__(kLsThreads) void bwd_levelsum_kernel(const float *_
     const int npx = nr * W;   // the window: rows [r0, r0 + nr) of the level
     const int tid = threadIdx.x;
     const int j = tid & (kLsChan - 1), grp = tid / kLsChan;
-    constexpr int kGroups = kLsThreads / kLsChan;
+    constexpr int kGroups = THREADS / kLsChan;
     const int ch = slice * kLsChan + j;
     const bool has_ch = ch < g.D;
 
-    for (int e = tid; e < npx * kLsChan; e += kLsThreads) win[e] = 0.0;
+    for (int e = tid; e < npx * kLsChan; e += THREADS) win[e] = 0.0;
     __syncthreads();
 
     const int LP = g.L * g.P;
@@ -204,6 +203,16 @@ __global__ __launch_bounds__(kLsThreads) void bwd_levelsum_kernel(const float *_
     TV *dst = grad_value + ((int64_t)(b * g.S + g.start[li] + r0 * W) * g.M + m) * g.D + ch;
     if (has_ch)
         for (int px = grp; px < npx; px += kGroups) dst[(int64_t)px * g.M * g.D] = to_storage<TV, float>((float)win[px * kLsChan + j]);
+}
+
+template <bool P4, typename TV = float>
+__global__ __launch_bounds__(kLsThreads) void bwd_levelsum_kernel(const float *__restrict__ loc,
+                                                                  const float *__restrict__ aw,
+                                                                  const TV *__restrict__ grad_out,
+                                                                  TV *__restrict__ grad_value, const LevelSumGeom g)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    levelsum_body<P4, TV, kLsThreads>(blockIdx.x, reinterpret_cast<double *>(smem), loc, aw, grad_out, grad_value, g);
 }
 
 }  // namespace msda
