@@ -565,36 +565,41 @@ __global__ __launch_bounds__(256) void pool_nhwc_kernel(const uint16_t *__restri
 }
 
 // GroupNorm over NHWC bf16 with 8 channels per group (nn.GroupNorm(32, 256) of the input projections, richsem.py:301, :307): a pixel's
-// group is one 16-byte vector.  Pass 1: sums of x and x^2 per (image, group) -- per-thread fp32 partials over a strip of pixels, folded
-// per workgroup and added as doubles; pass 2: (x - mean) * rstd * gamma + beta to fp32 and / or bf16.
+// group is one 16-byte vector.  Pass 1: sums of x and x^2 per (image, group), accumulated in fp64 from the first addition on -- a bf16
+// value and the product of two are exact in fp32, so the sums are exact to n 2^-53 and the variance E[x^2] - mean^2 that pass 2 forms in
+// fp64 keeps its digits whatever mean^2 / var is (fp32 partials lost it: 1.3 bounds at mean 48, std 1, profiles/r26_row_bounds.md);
+// pass 2: (x - mean) * rstd * gamma + beta to fp32 and / or bf16.
 __global__ __launch_bounds__(256) void gn8_stats_kernel(const uint16_t *__restrict__ x, double *__restrict__ stats, int HW, int C)
 {
-    __shared__ float red[2][256];
+    __shared__ double red[2][4];
     const int groups = C / 8;
     const int g = blockIdx.y, n = blockIdx.z;
-    float s1 = 0.f, s2 = 0.f;
+    double s1 = 0.0, s2 = 0.0;
     for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += gridDim.x * 256) {
         const u32x4 v = *reinterpret_cast<const u32x4 *>(x + ((long long)n * HW + p) * C + 8 * g);
+        double t1[4], t2[4];      // the vector's eight values as a tree: one addition per trip on each accumulator's chain
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float a = bf16_lo(v[e]), b = bf16_hi(v[e]);
-            s1 += a + b;
-            s2 += a * a + b * b;
+            t1[e] = (double)a + (double)b;
+            t2[e] = (double)(a * a) + (double)(b * b);
         }
+        s1 += (t1[0] + t1[1]) + (t1[2] + t1[3]);
+        s2 += (t2[0] + t2[1]) + (t2[2] + t2[3]);
     }
-    red[0][threadIdx.x] = s1;
-    red[1][threadIdx.x] = s2;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {      // the wave's sums by shuffles, the workgroup's four waves through LDS: one barrier
+        s1 += __shfl_xor(s1, o, 64);
+        s2 += __shfl_xor(s2, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = s1;
+        red[1][threadIdx.x >> 6] = s2;
+    }
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + o];
-            red[1][threadIdx.x] += red[1][threadIdx.x + o];
-        }
-        __syncthreads();
-    }
     if (threadIdx.x == 0) {
-        atomicAdd(stats + ((long long)n * groups + g) * 2, (double)red[0][0]);
-        atomicAdd(stats + ((long long)n * groups + g) * 2 + 1, (double)red[1][0]);
+        atomicAdd(stats + ((long long)n * groups + g) * 2, (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
+        atomicAdd(stats + ((long long)n * groups + g) * 2 + 1, (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
     }
 }
 
