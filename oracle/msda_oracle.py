@@ -16,10 +16,11 @@ _lib = None
 
 
 def build(force=False):
-    """Compile the oracle with gcc (a few seconds).  Idempotent."""
+    """Compile the oracle with gcc (a few seconds).  Idempotent, and safe when several processes do it at once:
+    the recipe renames the finished library into place and nothing removes the one that is there."""
     src = os.path.join(_HERE, "msda_oracle.c")
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-s", "-C", _HERE, "clean", "all"])
+        subprocess.check_call(["make", "-s", "-B", "-C", _HERE, "all"])
     return _SO
 
 

@@ -1,4 +1,4 @@
-"""The criterion's classification and box terms over CAPACITY buffers (``msda_criterion_pairs_f32``, csrc/msda_criterion.h).
+"""The criterion's classification and box terms over CAPACITY buffers (``msda_criterion_pairs_ex_f32``, csrc/msda_criterion.h).
 
 ``SetCriterion.forward`` of the reference (models/richsem/richsem.py:1124-1298) decides on the host which (prediction, target) pairs carry a
 loss: the matcher's index lists, ``num_boxes`` (:1143-1147), the denoising positive indices from ``pad_size`` and the group count
@@ -7,25 +7,32 @@ batch's exact size.  :func:`device_criterion` reads all of it on the device inst
 :class:`~richsem_amd.matcher.TargetBuffers`, the solver's ``query_of_target``, the ``meta`` of ``denoising_queries`` -- so that ONE captured
 graph of cost blocks -> assignment -> criterion (+ backward) serves any batch that fits the capacities.
 
-Launches: forward -- the pair kernel (slots, row weights, per-workgroup partials), its reduction, ``msda_focal_neg_sum_f32`` over the decoder
-logits and over the two-stage logits, and a few scalar torch ops that add the parts up; backward -- ``msda_focal_neg_grad_f32`` twice (the only
-dense passes over the logits) and one scatter kernel.  No gather, no index tensor, no dense zero-fill of a logit-shaped tensor.
+Launches: forward -- the pair kernel (slots, row weights, per-workgroup partials), its reduction, ``focal.neg_sum`` over the decoder logits
+and over the two-stage logits, and a few scalar torch ops that add the parts up; backward -- ``focal.neg_grad`` twice (the only dense passes
+over the logits) and one scatter kernel.  No gather, no index tensor, no dense zero-fill of a logit-shaped tensor.
 
 :func:`device_set_criterion` is the same criterion with the reference's two remaining switches: the federated loss (``use_fed_loss``: the
 class subset of every get_loss call is drawn on the device from the appeared classes of the batch the buffers hold,
 ``msda_fed_class_mask_slots_f32``, and the all-negative term runs through the masked focal kernels with row groups the pair kernel
-writes, ``msda_criterion_pairs_ex_f32``) and ``enc_cls_agn`` (the two-stage output scored against class 0).  Two launches more.
+writes) and ``enc_cls_agn`` (the two-stage output scored against class 0).  Two launches more.  Both functions are front ends of ONE path
+-- :func:`set_criterion_forward`, :func:`set_criterion_backward`, :class:`DeviceCriterionFunction` --, whose switches are optional arguments.
 """
+import collections
 import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, focal
 from .fed_loss import FedClassSampler
 from .matcher import LateStatus
 
 STATUS = ("dn_overflow", "targets_without_query", "labels_out_of_range", "bad_prefix")      # the int32[4] ``status``
-_NEG_PARTIALS = 4096
+
+# what the forward half keeps for the backward half; ``g_rows``, ``g_int`` and ``class_mask`` are None where no class mask was given.  An
+# autograd node keeps the host values in ctx and hands the rest, the tensors, to save_for_backward.
+Saved = collections.namedtuple("Saved", ("x", "xi", "w_rows", "w_int", "ws", "cum", "dims", "alpha", "c_cls", "g_rows", "g_int", "class_mask"))
+_SAVED_VALUES = ("dims", "alpha", "c_cls")
+_SAVED_TENSORS = tuple(k for k in Saved._fields if k not in _SAVED_VALUES)
 
 
 def _dims(logits, il, pad_cap, capacity):
@@ -40,26 +47,14 @@ def _workspace(dims, device):
     return torch.empty(n.value, dtype=torch.uint8, device=device)
 
 
-def _neg_sum(x, w, alpha):
-    """the one call of ``msda_focal_neg_sum_f32`` here: -> the float64 partials of the all-negative focal term"""
-    partial = torch.empty(_NEG_PARTIALS, dtype=torch.float64, device=x.device)
-    n = ctypes.c_int(0)
-    _lib.check(_lib.load().msda_focal_neg_sum_f32(x.data_ptr(), w.data_ptr(), w.numel(), x.shape[-1], alpha, partial.data_ptr(), _NEG_PARTIALS,
-                                                  ctypes.byref(n), _lib.raw_stream(x.device)))
-    return partial[:n.value]
-
-
-def _neg_grad(x, w, alpha, gs):
-    gx = torch.empty_like(x)
-    _lib.check(_lib.load().msda_focal_neg_grad_f32(x.data_ptr(), w.data_ptr(), w.numel(), x.shape[-1], alpha, gs.data_ptr(), gx.data_ptr(),
-                                                   _lib.raw_stream(x.device)))
-    return gx
-
-
-def criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg):
-    """the forward half on checked, contiguous tensors: -> (loss, terms, status, saved); ``saved`` is what :func:`criterion_backward` takes.
-    ``cfg`` = (pad_cap, capacity, alpha, c_cls, c_l1, c_giou).  :class:`DeviceCriterionFunction` is these two halves as an autograd node; a
-    caller that schedules the backward itself (a whole step captured without the autograd engine) calls them directly."""
+def set_criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg, class_mask=None, enc_cls_agn=False):
+    """the forward half on checked, contiguous tensors: -> (loss, terms, status, saved); ``saved`` (a :class:`Saved`) is what
+    :func:`set_criterion_backward` takes.  ``cfg`` = (pad_cap, capacity, alpha, c_cls, c_l1, c_giou).  The two switches: ``class_mask``
+    (2 nl + 1, C) float32 or None -- the class subset of each get_loss call, which the all-negative term is restricted to (the masked focal
+    kernels with the row groups the pair kernel writes) --, and ``enc_cls_agn`` -- the two-stage output's positives take label 0.  Without
+    either, ``msda_criterion_pairs_ex_f32`` gets flags = 0 and no row groups: the launches of ``msda_criterion_pairs_f32``
+    (csrc/criterion_api.hip).  :class:`DeviceCriterionFunction` is the two halves as an autograd node; a caller that schedules the backward
+    itself (a whole step captured without the autograd engine) calls them directly."""
     pad_cap, capacity, alpha, c_cls, c_l1, c_giou = cfg
     dev = logits.device
     dims = _dims(logits, il, pad_cap, capacity)
@@ -68,58 +63,67 @@ def criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_m
     ws = _workspace(dims, dev)
     w_rows = torch.empty(x.shape[:3], dtype=torch.float32, device=dev)
     w_int = torch.empty(xi.shape[:2], dtype=torch.float32, device=dev)
+    fed = class_mask is not None
+    g_rows = torch.empty(x.shape[:3], dtype=torch.int32, device=dev) if fed else None
+    g_int = torch.empty(xi.shape[:2], dtype=torch.int32, device=dev) if fed else None
     terms = torch.empty((2 * nl + 1, 3), dtype=torch.float32, device=dev)
     status = torch.empty(4, dtype=torch.int32, device=dev)
     with _lib.on_device(dev):
-        _lib.check(_lib.load().msda_criterion_pairs_f32(
+        _lib.check(_lib.load().msda_criterion_pairs_ex_f32(
             x.data_ptr(), p.data_ptr(), xi.data_ptr(), pi.data_ptr(), cum.data_ptr(), tgt_ids.data_ptr(), tgt_boxes.data_ptr(), qot.data_ptr(),
             None if dn_meta is None else dn_meta.data_ptr(), None if num_boxes is None else num_boxes.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap,
-            alpha, c_cls, c_l1, c_giou, w_rows.data_ptr(), w_int.data_ptr(), terms.data_ptr(), status.data_ptr(), ws.data_ptr(),
-            _lib.raw_stream(dev)))
-        neg = _neg_sum(x, w_rows, alpha).sum() + _neg_sum(xi, w_int, alpha).sum()
+            alpha, c_cls, c_l1, c_giou, 1 if enc_cls_agn else 0, w_rows.data_ptr(), w_int.data_ptr(), g_rows.data_ptr() if fed else None,
+            g_int.data_ptr() if fed else None, terms.data_ptr(), status.data_ptr(), ws.data_ptr(), _lib.raw_stream(dev)))
+        neg = focal.neg_sum(x, w_rows, alpha, g_rows, class_mask).sum() + focal.neg_sum(xi, w_int, alpha, g_int, class_mask).sum()
     tsum = terms.double().sum(0)      # (float64 scalars from here on; the coefficients are host numbers: nothing is copied)
     loss = (c_cls * (neg + tsum[0]) + c_l1 * tsum[1] + c_giou * tsum[2]).float()
-    return loss, terms, status, (x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls)
+    return loss, terms, status, Saved(x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls, g_rows, g_int, class_mask)
 
 
-def criterion_backward(saved, g):
-    """the backward half: ``g`` = d / d loss (0-dim or (1,) float32 on the device) -> (grad_logits, grad_coords, grad_il, grad_ib)"""
-    x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls = saved
-    nl, N, Q, Qi, C, cap, pad_cap = dims
+def set_criterion_backward(saved, g):
+    """the backward half: ``g`` = d / d loss (0-dim or (1,) float32 on the device) -> (grad_logits, grad_coords, grad_il, grad_ib); with a
+    class mask the logit gradients are exactly 0 off each row's class subset (``enc_cls_agn`` alone changes the records, not the launches)"""
+    nl, N, Q, Qi, C, cap, pad_cap = saved.dims
+    x, xi = saved.x, saved.xi
     dev = x.device
     gs = g.detach().reshape(1).float().contiguous()
-    gs_cls = gs * c_cls
+    gs_cls = gs * saved.c_cls
     g_coords = torch.empty(x.shape[:3] + (4,), dtype=torch.float32, device=dev)
     g_ib = torch.empty(xi.shape[:2] + (4,), dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
-        g_logits = _neg_grad(x, w_rows, alpha, gs_cls)      # (the dense passes: every element written)
-        g_il = _neg_grad(xi, w_int, alpha, gs_cls)
+        g_logits = focal.neg_grad(x, saved.w_rows, saved.alpha, gs_cls, saved.g_rows, saved.class_mask)      # (the dense passes: every element written)
+        g_il = focal.neg_grad(xi, saved.w_int, saved.alpha, gs_cls, saved.g_int, saved.class_mask)
         _lib.check(_lib.load().msda_criterion_pairs_backward_f32(
-            ws.data_ptr(), cum.data_ptr(), gs.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap, g_logits.data_ptr(), g_il.data_ptr(),
+            saved.ws.data_ptr(), saved.cum.data_ptr(), gs.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap, g_logits.data_ptr(), g_il.data_ptr(),
             g_coords.data_ptr(), g_ib.data_ptr(), _lib.raw_stream(dev)))
     return g_logits, g_coords, g_il, g_ib
 
 
+criterion_forward, criterion_backward = set_criterion_forward, set_criterion_backward      # (the names from before the switches)
+
+
 class DeviceCriterionFunction(torch.autograd.Function):
-    """:func:`device_criterion` as one autograd node: gradients for logits, coords, il and ib.  ``cfg`` = (pad_cap, capacity, alpha, c_cls,
-    c_l1, c_giou)."""
+    """:func:`device_criterion` / :func:`device_set_criterion` as one autograd node: gradients for logits, coords, il and ib.  ``cfg`` =
+    (pad_cap, capacity, alpha, c_cls, c_l1, c_giou)."""
 
     @staticmethod
-    def forward(ctx, logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg):
-        loss, terms, status, saved = criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg)
-        ctx.save_for_backward(*saved[:6])
-        ctx.rest = saved[6:]
+    def forward(ctx, logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg, class_mask, enc_cls_agn):
+        loss, terms, status, saved = set_criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg,
+                                                           class_mask, enc_cls_agn)
+        ctx.save_for_backward(*(getattr(saved, k) for k in _SAVED_TENSORS))
+        ctx.values = {k: getattr(saved, k) for k in _SAVED_VALUES}
         ctx.mark_non_differentiable(terms, status)
         return loss, terms, status
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g, _g_terms, _g_status):
-        return criterion_backward(tuple(ctx.saved_tensors) + ctx.rest, g) + (None,) * 7
+        saved = Saved(**dict(zip(_SAVED_TENSORS, ctx.saved_tensors)), **ctx.values)
+        return set_criterion_backward(saved, g) + (None,) * 9
 
 
 def _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, fed_loss, enc_cls_agn, distill):
-    """the argument checks of :func:`device_criterion`: -> the tensor arguments and ``cfg`` of :func:`criterion_forward`"""
+    """the argument checks of :func:`device_criterion`: -> the tensor arguments and ``cfg`` of :func:`set_criterion_forward`"""
     if fed_loss:
         raise NotImplementedError("device_criterion: the federated loss over capacity buffers is device_set_criterion(fed=...)")
     if enc_cls_agn:
@@ -153,6 +157,21 @@ def _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap,
             num_boxes, cfg)
 
 
+def _apply(args, class_mask, enc_cls_agn, late_status):
+    """the autograd form of the four front ends: -> (loss, terms, status); outside a capture the status goes to ``late_status``"""
+    loss, terms, status = DeviceCriterionFunction.apply(*args, class_mask, enc_cls_agn)
+    if late_status is not None and not torch.cuda.is_current_stream_capturing():
+        late_status.push(status.view(1, 4))
+    return loss, terms, status
+
+
+def _forward_and_backward(args, class_mask, enc_cls_agn, grad_loss):
+    """the form WITHOUT the autograd engine: -> (loss, terms, status, (grad_logits, grad_coords, grad_il, grad_ib))"""
+    loss, terms, status, saved = set_criterion_forward(*args, class_mask, enc_cls_agn)
+    g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
+    return loss, terms, status, set_criterion_backward(saved, g)
+
+
 def device_criterion(logits, coords, il, ib, targets, query_of_target, dn_meta=None, *, pad_cap, alpha=0.25, c_cls=1.0, c_l1=5.0, c_giou=2.0,
                      num_boxes=None, fed_loss=False, enc_cls_agn=False, distill=False, late_status=None):
     """The classification (sigmoid focal) and box (L1, GIoU) terms of the criterion over all outputs of a step, pairs found on the device.
@@ -172,10 +191,7 @@ def device_criterion(logits, coords, il, ib, targets, query_of_target, dn_meta=N
     after one eager call.  Bitwise reproducible.  CPU tensors raise: there is no CPU fallback."""
     args = _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, fed_loss,
                     enc_cls_agn, distill)
-    loss, terms, status = DeviceCriterionFunction.apply(*args)
-    if late_status is not None and not torch.cuda.is_current_stream_capturing():
-        late_status.push(status.view(1, 4))
-    return loss, terms, status
+    return _apply(args, None, False, late_status)
 
 
 @torch.no_grad()
@@ -185,105 +201,10 @@ def device_criterion_and_grads(logits, coords, il, ib, targets, query_of_target,
     grad_il, grad_ib)) for d / d loss = ``grad_loss`` (a device scalar; default 1).  For a caller that schedules the backward itself -- a
     whole step captured into one graph on the capturing thread.  Same arguments, checks and launches as :func:`device_criterion`."""
     args = _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, False, False, False)
-    loss, terms, status, saved = criterion_forward(*args)
-    g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
-    return loss, terms, status, criterion_backward(saved, g)
+    return _forward_and_backward(args, None, False, grad_loss)
 
 
-# ---- the criterion with the reference's remaining switches: the federated loss (use_fed_loss) and class-agnostic two-stage targets --------
-def _neg_sum_masked(x, w, grp, mask, alpha):
-    """the one call of ``msda_focal_neg_sum_masked_f32`` here: -> the float64 partials of the all-negative focal term over each row's subset"""
-    partial = torch.empty(_NEG_PARTIALS, dtype=torch.float64, device=x.device)
-    n = ctypes.c_int(0)
-    _lib.check(_lib.load().msda_focal_neg_sum_masked_f32(x.data_ptr(), w.data_ptr(), grp.data_ptr(), mask.data_ptr(), mask.shape[0], w.numel(),
-                                                         x.shape[-1], alpha, partial.data_ptr(), _NEG_PARTIALS, ctypes.byref(n),
-                                                         _lib.raw_stream(x.device)))
-    return partial[:n.value]
-
-
-def _neg_grad_masked(x, w, grp, mask, alpha, gs):
-    gx = torch.empty_like(x)
-    _lib.check(_lib.load().msda_focal_neg_grad_masked_f32(x.data_ptr(), w.data_ptr(), grp.data_ptr(), mask.data_ptr(), mask.shape[0], w.numel(),
-                                                          x.shape[-1], alpha, gs.data_ptr(), gx.data_ptr(), _lib.raw_stream(x.device)))
-    return gx
-
-
-def set_criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg, class_mask=None, enc_cls_agn=False):
-    """:func:`criterion_forward` with the two switches: ``class_mask`` (2 nl + 1, C) float32 or None -- the class subset of each get_loss call,
-    which the all-negative term is restricted to (``msda_focal_neg_sum_masked_f32`` with the row groups the pair kernel writes) --, and
-    ``enc_cls_agn`` -- the two-stage output's positives take label 0.  Without either it IS :func:`criterion_forward`.  -> (loss, terms,
-    status, saved) for :func:`set_criterion_backward`."""
-    if class_mask is None and not enc_cls_agn:
-        return criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg)
-    pad_cap, capacity, alpha, c_cls, c_l1, c_giou = cfg
-    dev = logits.device
-    dims = _dims(logits, il, pad_cap, capacity)
-    nl, N, Q, Qi, C, cap, _ = dims
-    x, p, xi, pi = logits.contiguous(), coords.contiguous(), il.contiguous(), ib.contiguous()
-    ws = _workspace(dims, dev)
-    w_rows = torch.empty(x.shape[:3], dtype=torch.float32, device=dev)
-    w_int = torch.empty(xi.shape[:2], dtype=torch.float32, device=dev)
-    fed = class_mask is not None
-    g_rows = torch.empty(x.shape[:3], dtype=torch.int32, device=dev) if fed else None
-    g_int = torch.empty(xi.shape[:2], dtype=torch.int32, device=dev) if fed else None
-    terms = torch.empty((2 * nl + 1, 3), dtype=torch.float32, device=dev)
-    status = torch.empty(4, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(_lib.load().msda_criterion_pairs_ex_f32(
-            x.data_ptr(), p.data_ptr(), xi.data_ptr(), pi.data_ptr(), cum.data_ptr(), tgt_ids.data_ptr(), tgt_boxes.data_ptr(), qot.data_ptr(),
-            None if dn_meta is None else dn_meta.data_ptr(), None if num_boxes is None else num_boxes.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap,
-            alpha, c_cls, c_l1, c_giou, 1 if enc_cls_agn else 0, w_rows.data_ptr(), w_int.data_ptr(), g_rows.data_ptr() if fed else None,
-            g_int.data_ptr() if fed else None, terms.data_ptr(), status.data_ptr(), ws.data_ptr(), _lib.raw_stream(dev)))
-        if fed:
-            neg = _neg_sum_masked(x, w_rows, g_rows, class_mask, alpha).sum() + _neg_sum_masked(xi, w_int, g_int, class_mask, alpha).sum()
-        else:
-            neg = _neg_sum(x, w_rows, alpha).sum() + _neg_sum(xi, w_int, alpha).sum()
-    tsum = terms.double().sum(0)
-    loss = (c_cls * (neg + tsum[0]) + c_l1 * tsum[1] + c_giou * tsum[2]).float()
-    return loss, terms, status, (x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls, g_rows, g_int, class_mask)
-
-
-def set_criterion_backward(saved, g):
-    """the backward half of :func:`set_criterion_forward`: -> (grad_logits, grad_coords, grad_il, grad_ib); the logit gradients are exactly 0
-    off each row's class subset"""
-    if len(saved) == 9 or saved[11] is None:
-        return criterion_backward(saved[:9], g)      # (enc_cls_agn alone changes the records, not the launches)
-    x, xi, w_rows, w_int, ws, cum, dims, alpha, c_cls, g_rows, g_int, mask = saved
-    nl, N, Q, Qi, C, cap, pad_cap = dims
-    dev = x.device
-    gs = g.detach().reshape(1).float().contiguous()
-    gs_cls = gs * c_cls
-    g_coords = torch.empty(x.shape[:3] + (4,), dtype=torch.float32, device=dev)
-    g_ib = torch.empty(xi.shape[:2] + (4,), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        g_logits = _neg_grad_masked(x, w_rows, g_rows, mask, alpha, gs_cls)
-        g_il = _neg_grad_masked(xi, w_int, g_int, mask, alpha, gs_cls)
-        _lib.check(_lib.load().msda_criterion_pairs_backward_f32(
-            ws.data_ptr(), cum.data_ptr(), gs.data_ptr(), nl, N, Q, Qi, C, cap, pad_cap, g_logits.data_ptr(), g_il.data_ptr(),
-            g_coords.data_ptr(), g_ib.data_ptr(), _lib.raw_stream(dev)))
-    return g_logits, g_coords, g_il, g_ib
-
-
-class DeviceSetCriterionFunction(torch.autograd.Function):
-    """:func:`device_set_criterion` as one autograd node: gradients for logits, coords, il and ib"""
-
-    @staticmethod
-    def forward(ctx, logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg, class_mask, enc_cls_agn):
-        loss, terms, status, saved = set_criterion_forward(logits, coords, il, ib, cum, tgt_ids, tgt_boxes, qot, dn_meta, num_boxes, cfg,
-                                                           class_mask, enc_cls_agn)
-        saved = saved + (None,) * (12 - len(saved))
-        ctx.save_for_backward(*(saved[:6] + saved[9:]))
-        ctx.rest = saved[6:9]
-        ctx.mark_non_differentiable(terms, status)
-        return loss, terms, status
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g, _g_terms, _g_status):
-        t = tuple(ctx.saved_tensors)
-        return set_criterion_backward(t[:6] + ctx.rest + t[6:], g) + (None,) * 9
-
-
+# ---- the reference's remaining switches: the federated loss (use_fed_loss) and class-agnostic two-stage targets ------------------------
 def _checked_set(logits, il, targets, query_of_target, dn_meta, pad_cap, fed, enc_cls_agn, generator):
     """the checks of :func:`device_set_criterion` beyond :func:`_checked`, and the draw: -> (class_mask or None, fed_out)"""
     if fed is None:
@@ -324,10 +245,7 @@ def device_set_criterion(logits, coords, il, ib, targets, query_of_target, dn_me
     sampler's weights to the device); bitwise reproducible for given uniforms.  CPU tensors raise: there is no CPU fallback."""
     args = _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, False, False, False)
     mask, fed_out = _checked_set(logits, il, targets, query_of_target, dn_meta, pad_cap, fed, bool(enc_cls_agn), generator)
-    loss, terms, status = DeviceSetCriterionFunction.apply(*args, mask, bool(enc_cls_agn))
-    if late_status is not None and not torch.cuda.is_current_stream_capturing():
-        late_status.push(status.view(1, 4))
-    return loss, terms, status, fed_out
+    return _apply(args, mask, bool(enc_cls_agn), late_status) + (fed_out,)
 
 
 @torch.no_grad()
@@ -337,21 +255,14 @@ def device_set_criterion_and_grads(logits, coords, il, ib, targets, query_of_tar
     -> (loss, terms, status, fed_out, (grad_logits, grad_coords, grad_il, grad_ib))"""
     args = _checked(logits, coords, il, ib, targets, query_of_target, dn_meta, pad_cap, alpha, c_cls, c_l1, c_giou, num_boxes, False, False, False)
     mask, fed_out = _checked_set(logits, il, targets, query_of_target, dn_meta, pad_cap, fed, bool(enc_cls_agn), generator)
-    loss, terms, status, saved = set_criterion_forward(*args, mask, bool(enc_cls_agn))
-    g = torch.ones(1, dtype=torch.float32, device=loss.device) if grad_loss is None else grad_loss
-    return loss, terms, status, fed_out, set_criterion_backward(saved, g)
+    loss, terms, status, grads = _forward_and_backward(args, mask, bool(enc_cls_agn), grad_loss)
+    return loss, terms, status, fed_out, grads
 
 
 class CriterionStatus(LateStatus):
     """``matcher.LateStatus`` for the status of :func:`device_criterion`: the error text names the entry of ``STATUS`` that was set"""
 
-    def _finish(self):
-        if self._pending is None:
-            return
-        host, event = self._pending
-        self._pending = None
-        if event is not None:
-            event.synchronize()
-        if bool((host != 0).any()):
-            what = ", ".join(f"{name} = {int(v)}" for name, v in zip(STATUS, host.reshape(-1).tolist()) if v)
-            raise ValueError(f"device_criterion (the previous step): {what}")
+    @staticmethod
+    def _message(host):
+        what = ", ".join(f"{name} = {int(v)}" for name, v in zip(STATUS, host.reshape(-1).tolist()) if v)
+        return f"device_criterion (the previous step): {what}"

@@ -83,8 +83,10 @@ __global__ __launch_bounds__(kFedThreads) void fed_class_mask_kernel(const int64
 }
 
 // the all-negative focal term of msda_focal_neg_sum_f32 / _grad_f32 (rows_api.hip) with a class selector per row: row r counts class c only
-// where class_mask[row_group[r]][c] != 0 (a row whose group lies outside [0, groups) counts nothing).  The loops and the reduction are those of
-// the unmasked kernels, so an all-ones mask gives the same bits.
+// where class_mask[row_group[r]][c] != 0 (a row whose group lies outside [0, groups) counts nothing).  The loops and the reduction are hand copies
+// of the unmasked kernels', so that an all-ones mask gives the same bits: a change to either pair goes into both
+// (tests/test_gpu_fed_loss.py compares them bit for bit at the grid caps and the column loop's edges).  One templated body for both was
+// tried and left out: inlined into these shells it did not compile to the same instructions (profiles/r27_loss_host_layer.md).
 __global__ __launch_bounds__(256) void focal_neg_sum_masked_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                                    const int32_t *__restrict__ row_group, const float *__restrict__ class_mask,
                                                                    int groups, long long rows, int C, float one_m_alpha,

@@ -414,6 +414,47 @@ __global__ __launch_bounds__(1024) void focal_pos_sum_kernel(const float *__rest
     if (threadIdx.x == 0) loss[0] = s;
 }
 
+namespace {
+
+// the checks, the grid rule and the launch of msda_focal_neg_sum_f32 (masked = false: no row groups, no class masks) and of its masked form
+int focal_neg_sum_launch(const char *entry, bool masked, const float *logits, const float *row_weight, const int32_t *row_group,
+                         const float *class_mask, int groups, int64_t rows, int C, float alpha, double *partial, int max_partial, int *n_partial,
+                         msda_stream_t stream)
+{
+    if (!logits || !row_weight || !partial || !n_partial || (masked && (!row_group || !class_mask)))
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, entry);
+    if (rows < 1 || C < 1 || max_partial < 1 || (masked && groups < 1)) return msda::arg_fail(MSDA_ERR_BAD_DIMS, entry);
+    const int grid = (int)std::min<int64_t>(std::min<int64_t>(rows, 4096), max_partial);
+    *n_partial = grid;
+    if (masked)
+        hipLaunchKernelGGL(msda::focal_neg_sum_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight,
+                           row_group, class_mask, groups, (long long)rows, C, 1.f - alpha, partial);
+    else
+        hipLaunchKernelGGL(focal_neg_sum_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
+                           1.f - alpha, partial);
+    return msda::launched(entry);
+}
+
+// the same for msda_focal_neg_grad_f32 and its masked form
+int focal_neg_grad_launch(const char *entry, bool masked, const float *logits, const float *row_weight, const int32_t *row_group,
+                          const float *class_mask, int groups, int64_t rows, int C, float alpha, const float *gscale, float *grad_logits,
+                          msda_stream_t stream)
+{
+    if (!logits || !row_weight || !gscale || !grad_logits || (masked && (!row_group || !class_mask)))
+        return msda::arg_fail(MSDA_ERR_NULL_POINTER, entry);
+    if (rows < 1 || C < 1 || (masked && groups < 1)) return msda::arg_fail(MSDA_ERR_BAD_DIMS, entry);
+    const int grid = (int)std::min<int64_t>(rows, 8192);
+    if (masked)
+        hipLaunchKernelGGL(msda::focal_neg_grad_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight,
+                           row_group, class_mask, groups, (long long)rows, C, 1.f - alpha, gscale, grad_logits);
+    else
+        hipLaunchKernelGGL(focal_neg_grad_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
+                           1.f - alpha, gscale, grad_logits);
+    return msda::launched(entry);
+}
+
+}  // namespace
+
 extern "C" {
 
 /* msda_focal_neg_sum_f32: partial (grid doubles, grid = the value returned through n_partial) <- weighted all-negative focal sums; the caller adds
@@ -421,23 +462,12 @@ extern "C" {
 int msda_focal_neg_sum_f32(const float *logits, const float *row_weight, int64_t rows, int C, float alpha, double *partial, int max_partial,
                            int *n_partial, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !partial || !n_partial) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1 || max_partial < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
-    const int grid = (int)std::min<int64_t>(std::min<int64_t>(rows, 4096), max_partial);
-    *n_partial = grid;
-    hipLaunchKernelGGL(focal_neg_sum_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
-                       1.f - alpha, partial);
-    return msda::launched(__func__);
+    return focal_neg_sum_launch(__func__, false, logits, row_weight, nullptr, nullptr, 0, rows, C, alpha, partial, max_partial, n_partial, stream);
 }
 int msda_focal_neg_grad_f32(const float *logits, const float *row_weight, int64_t rows, int C, float alpha, const float *gscale,
                             float *grad_logits, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !gscale || !grad_logits) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
-    const int grid = (int)std::min<int64_t>(rows, 8192);
-    hipLaunchKernelGGL(focal_neg_grad_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, (long long)rows, C,
-                       1.f - alpha, gscale, grad_logits);
-    return msda::launched(__func__);
+    return focal_neg_grad_launch(__func__, false, logits, row_weight, nullptr, nullptr, 0, rows, C, alpha, gscale, grad_logits, stream);
 }
 
 /* msda_fed_class_mask_f32: per group g, mask[g][c] = 1 for the classes among labels and for m = max(num_sample_cats - appeared, 0) more
@@ -459,23 +489,13 @@ int msda_fed_class_mask_f32(const int64_t *labels, int64_t n_labels, const float
 int msda_focal_neg_sum_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
                                   int64_t rows, int C, float alpha, double *partial, int max_partial, int *n_partial, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !row_group || !class_mask || !partial || !n_partial) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1 || groups < 1 || max_partial < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
-    const int grid = (int)std::min<int64_t>(std::min<int64_t>(rows, 4096), max_partial);
-    *n_partial = grid;
-    hipLaunchKernelGGL(msda::focal_neg_sum_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
-                       class_mask, groups, (long long)rows, C, 1.f - alpha, partial);
-    return msda::launched(__func__);
+    return focal_neg_sum_launch(__func__, true, logits, row_weight, row_group, class_mask, groups, rows, C, alpha, partial, max_partial, n_partial,
+                                stream);
 }
 int msda_focal_neg_grad_masked_f32(const float *logits, const float *row_weight, const int32_t *row_group, const float *class_mask, int groups,
                                    int64_t rows, int C, float alpha, const float *gscale, float *grad_logits, msda_stream_t stream)
 {
-    if (!logits || !row_weight || !row_group || !class_mask || !gscale || !grad_logits) return msda::arg_fail(MSDA_ERR_NULL_POINTER, __func__);
-    if (rows < 1 || C < 1 || groups < 1) return msda::arg_fail(MSDA_ERR_BAD_DIMS, __func__);
-    const int grid = (int)std::min<int64_t>(rows, 8192);
-    hipLaunchKernelGGL(msda::focal_neg_grad_masked_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), logits, row_weight, row_group,
-                       class_mask, groups, (long long)rows, C, 1.f - alpha, gscale, grad_logits);
-    return msda::launched(__func__);
+    return focal_neg_grad_launch(__func__, true, logits, row_weight, row_group, class_mask, groups, rows, C, alpha, gscale, grad_logits, stream);
 }
 
 /* The distillation term over K gathered rows (msda_distill.h; semantics in include/richsem_msda.h): loss[0] <- the sum of the row losses,

@@ -13,11 +13,9 @@ is an appeared class and so always in the mask (matcher.FocalPositiveSum).
 One difference: where fewer classes are eligible (weight > 0, not appeared) than are to be drawn, ``torch.multinomial`` raises; a graph
 cannot, so every eligible class is taken, and ``n_chosen`` tells.
 """
-import ctypes
-
 import torch
 
-from . import _lib
+from . import _lib, focal
 
 MAX_CLASSES = 4096      # msda::kFedMaxClasses: one group's keys sort in LDS
 
@@ -132,27 +130,17 @@ class MaskedFocalNegativeSum(torch.autograd.Function):
         assert row_group.dtype == torch.int32 and row_group.numel() == row_weight.numel()
         assert class_mask.dtype == torch.float32 and class_mask.dim() == 2 and class_mask.shape[1] == logits.shape[-1]
         x, w, grp, m = logits.contiguous(), row_weight.contiguous(), row_group.contiguous(), class_mask.detach().contiguous()
-        rows, C = w.numel(), x.shape[-1]
-        partial = torch.empty(4096, dtype=torch.float64, device=x.device)
-        n = ctypes.c_int(0)
-        with _lib.on_device(x.device):
-            _lib.check(_lib.load().msda_focal_neg_sum_masked_f32(x.data_ptr(), w.data_ptr(), grp.data_ptr(), m.data_ptr(), m.shape[0], rows, C,
-                                                                 float(alpha), partial.data_ptr(), 4096, ctypes.byref(n),
-                                                                 _lib.raw_stream(x.device)))
         ctx.save_for_backward(x, w, grp, m)
         ctx.alpha = float(alpha)
-        return partial[:n.value].sum().float()
+        with _lib.on_device(x.device):
+            return focal.neg_sum(x, w, ctx.alpha, grp, m).sum().float()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         x, w, grp, m = ctx.saved_tensors
-        gx = torch.empty_like(x)
-        gs = g.reshape(1).float().contiguous()
         with _lib.on_device(x.device):
-            _lib.check(_lib.load().msda_focal_neg_grad_masked_f32(x.data_ptr(), w.data_ptr(), grp.data_ptr(), m.data_ptr(), m.shape[0], w.numel(),
-                                                                  x.shape[-1], ctx.alpha, gs.data_ptr(), gx.data_ptr(), _lib.raw_stream(x.device)))
-        return gx, None, None, None, None
+            return focal.neg_grad(x, w, ctx.alpha, g.reshape(1).float().contiguous(), grp, m), None, None, None, None
 
 
 def fed_ids(mask_row):

@@ -24,11 +24,30 @@ import torch
 from scipy.optimize import linear_sum_assignment
 from torch import nn
 
-from . import _lib
+from . import _lib, focal
 
 
 def _stream(dev):
     return _lib.raw_stream(dev)
+
+
+def _sizes_and_offsets(targets):
+    """the per-image target counts of a batch and their prefix [0, T_0, T_0 + T_1, ...]"""
+    sizes = [int(v["boxes"].shape[0]) for v in targets]
+    offsets = [0]
+    for n in sizes:
+        offsets.append(offsets[-1] + n)
+    return sizes, offsets
+
+
+def _read_late(t):
+    """start reading the device tensor ``t`` on the host without a wait: -> (its copy in pinned memory, an event recorded behind the copy on
+    the current stream); the copy is valid once the event has completed -- one step later, for the classes below"""
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    event = torch.cuda.Event()
+    event.record(torch.cuda.current_stream(t.device))
+    return host, event
 
 
 class CostPlan:
@@ -38,10 +57,7 @@ class CostPlan:
     def __init__(self, targets, device, dtype):
         self.device, self.dtype = torch.device(device), dtype
         self.num_queries = None      # (set by match_many_device: the query count the last solve ran with)
-        self.sizes = [int(v["boxes"].shape[0]) for v in targets]
-        self.offsets = [0]
-        for s in self.sizes:
-            self.offsets.append(self.offsets[-1] + s)
+        self.sizes, self.offsets = _sizes_and_offsets(targets)
         self.total = self.offsets[-1]
         self.offsets_dev = torch.tensor(self.offsets, dtype=torch.int64).to(device, non_blocking=True)
         if self.total:
@@ -56,14 +72,11 @@ class CostPlan:
         """write another batch's labels, boxes and offsets into the device buffers this plan already has -- the same number of images and
         the same TOTAL number of targets (the per-image counts may change), anything else raises -- so that a graph captured with this plan
         solves the next batch on its next replay.  Host -> device copies on the current stream: call it between replays, not in a capture."""
-        sizes = [int(v["boxes"].shape[0]) for v in targets]
+        sizes, offsets = _sizes_and_offsets(targets)
         if len(sizes) != len(self.sizes):
             raise ValueError(f"CostPlan.update_: {len(sizes)} images, the plan was built for {len(self.sizes)}")
         if sum(sizes) != self.total:
             raise ValueError(f"CostPlan.update_: {sum(sizes)} targets in all, the plan was built for {self.total}")
-        offsets = [0]
-        for n in sizes:
-            offsets.append(offsets[-1] + n)
         self.sizes, self.offsets = sizes, offsets
         self.offsets_dev.copy_(torch.tensor(offsets, dtype=torch.int64), non_blocking=True)
         if self.total:
@@ -100,16 +113,13 @@ class TargetBuffers:
         """write a batch -- a list over the images of dicts with "labels" (T_b) and "boxes" (T_b, 4) -- into the buffers: host -> device
         copies on the current stream, between replays and not in a capture, as :meth:`CostPlan.update_`.  Another image count, more
         targets than ``capacity``, or an image with more than ``max_per_image`` of them raise ValueError and leave the buffers alone."""
-        sizes = [int(v["boxes"].shape[0]) for v in targets]
+        sizes, offsets = _sizes_and_offsets(targets)
         if len(sizes) != len(self.sizes):
             raise ValueError(f"TargetBuffers.update_: {len(sizes)} images, the buffers were built for {len(self.sizes)}")
         if sum(sizes) > self.capacity:
             raise ValueError(f"TargetBuffers.update_: {sum(sizes)} targets in all, the capacity is {self.capacity}")
         if self.max_per_image is not None and max(sizes) > self.max_per_image:
             raise ValueError(f"TargetBuffers.update_: an image with {max(sizes)} targets, at most {self.max_per_image} are allowed")
-        offsets = [0]
-        for n in sizes:
-            offsets.append(offsets[-1] + n)
         live = offsets[-1]
         ids = torch.zeros(self.capacity, dtype=torch.int64)
         boxes = torch.tensor([0.5, 0.5, 1.0, 1.0], dtype=self.dtype).repeat(self.capacity, 1)
@@ -406,14 +416,7 @@ class AsyncLossLog:
             dist.all_reduce(values, group=self.group, async_op=True).wait()
             if self.average:
                 values = values / self.world_size
-        if values.is_cuda:
-            host = torch.empty(values.shape, dtype=values.dtype, pin_memory=True)
-            host.copy_(values, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(values.device))
-        else:
-            host, event = values, None
-        self._pending = (names, host, event)
+        self._pending = (names,) + (_read_late(values) if values.is_cuda else (values, None))
         return prev
 
     def flush(self):
@@ -436,21 +439,18 @@ class LateStatus:
         if event is not None:
             event.synchronize()
         if bool((host != 0).any()):
-            o, b = (host != 0).nonzero()[0].tolist()
-            raise ValueError(f"matrix contains invalid numeric entries (the previous step's assignment: output {o}, image {b}, solver status "
-                             f"{int(host[o, b])})")
+            raise ValueError(self._message(host))
+
+    @staticmethod
+    def _message(host):
+        """the error text for a status with a non-zero entry (subclasses: what their status means)"""
+        o, b = (host != 0).nonzero()[0].tolist()
+        return f"matrix contains invalid numeric entries (the previous step's assignment: output {o}, image {b}, solver status {int(host[o, b])})"
 
     @torch.no_grad()
     def push(self, status):
         self._finish()
-        if status.is_cuda:
-            host = torch.empty(status.shape, dtype=status.dtype, pin_memory=True)
-            host.copy_(status, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record(torch.cuda.current_stream(status.device))
-        else:
-            host, event = status.clone(), None
-        self._pending = (host, event)
+        self._pending = _read_late(status) if status.is_cuda else (status.clone(), None)
 
     def flush(self):
         self._finish()
@@ -469,26 +469,17 @@ class FocalNegativeSum(torch.autograd.Function):
             raise RuntimeError("Not implemented on the CPU")
         assert logits.dtype == torch.float32 and row_weight.dtype == torch.float32 and row_weight.numel() * logits.shape[-1] == logits.numel()
         x, w = logits.contiguous(), row_weight.contiguous()
-        rows, C = w.numel(), x.shape[-1]
-        partial = torch.empty(4096, dtype=torch.float64, device=x.device)
-        n = ctypes.c_int(0)
-        with _lib.on_device(x.device):
-            _lib.check(_lib.load().msda_focal_neg_sum_f32(x.data_ptr(), w.data_ptr(), rows, C, float(alpha), partial.data_ptr(), 4096,
-                                                          ctypes.byref(n), _lib.raw_stream(x.device)))
         ctx.save_for_backward(x, w)
         ctx.alpha = float(alpha)
-        return partial[:n.value].sum().float()
+        with _lib.on_device(x.device):
+            return focal.neg_sum(x, w, ctx.alpha).sum().float()
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         x, w = ctx.saved_tensors
-        gx = torch.empty_like(x)
-        gs = g.reshape(1).float().contiguous()
         with _lib.on_device(x.device):
-            _lib.check(_lib.load().msda_focal_neg_grad_f32(x.data_ptr(), w.data_ptr(), w.numel(), x.shape[-1], ctx.alpha, gs.data_ptr(),
-                                                           gx.data_ptr(), _lib.raw_stream(x.device)))
-        return gx, None, None
+            return focal.neg_grad(x, w, ctx.alpha, g.reshape(1).float().contiguous()), None, None
 
 
 class _PairSum(torch.autograd.Function):

@@ -234,6 +234,47 @@ def test_all_ones_mask_gives_focal_negative_sum_bit_for_bit():
     assert bool((xc.grad[md == 0] == 0).all())
 
 
+@pytest.mark.parametrize("C", [1, 255, 256, 257])
+@pytest.mark.parametrize("rows", [1, 4097, 8193])
+def test_all_ones_mask_bit_for_bit_where_a_workgroup_takes_a_second_row(rows, C):
+    """The masked and the unmasked kernels at the shapes where their loops can drift apart: 4097 and 8193 rows are one past the grid caps of
+    the sum kernel (4096) and of the gradient kernel (8192), so workgroup 0 takes a second row; C around 256 is the edge of the 256-thread
+    column loop.  Rows 4096 and 8192 (the second rows) are live; every fifth row has weight 0."""
+    g = torch.Generator(device=DEV).manual_seed(1000 * rows + C)
+    G = 3
+    x = torch.randn(rows, C, device=DEV, generator=g) * 6
+    w = torch.rand(rows, device=DEV, generator=g) + 0.5
+    w[3::5] = 0.0
+    grp = torch.randint(0, G, (rows,), device=DEV, generator=g, dtype=torch.int32)
+    xa, xb = x.clone().requires_grad_(True), x.clone().requires_grad_(True)
+    la = FocalNegativeSum.apply(xa, w, 0.25)
+    lb = MaskedFocalNegativeSum.apply(xb, w, grp, torch.ones(G, C, device=DEV), 0.25)
+    (la * 1.3).backward()
+    (lb * 1.3).backward()
+    assert torch.equal(la, lb), (float(la), float(lb))
+    assert torch.equal(xa.grad, xb.grad)
+    assert bool((xb.grad[w == 0] == 0).all()) and bool((xb.grad[w != 0] != 0).any())
+    # a 0 / 1 mask, and rows whose group is outside [0, groups): exact zeros in the gradient there, something elsewhere
+    m = (torch.rand(G, C, device=DEV, generator=g) < 0.5).float()
+    m[0, 0] = 1.0
+    grp2 = grp.clone()
+    grp2[1::7] = G
+    grp2[2::7] = -1
+    grp2[rows - 1] = 0      # (the second row of workgroup 0 -- or the only row -- stays live)
+    xc = x.clone().requires_grad_(True)
+    (MaskedFocalNegativeSum.apply(xc, w, grp2, m, 0.25) * 1.3).backward()
+    live = (grp2 >= 0) & (grp2 < G)
+    md = m[grp2.clamp(0, G - 1).long()] * live[:, None]
+    assert bool((xc.grad[md == 0] == 0).all())
+    assert bool(xc.grad[rows - 1, 0] != 0) and bool(live.all()) == (rows == 1)
+    # every row out of range: nothing is counted at all
+    for dead in (G, -1):
+        xd = x.clone().requires_grad_(True)
+        ld = MaskedFocalNegativeSum.apply(xd, w, torch.full((rows,), dead, device=DEV, dtype=torch.int32), m, 0.25)
+        ld.backward()
+        assert float(ld) == 0.0 and bool((xd.grad == 0).all())
+
+
 def _small_fed_step(seed=0):
     import bench_step
     model = bench_step.Step(n_img=2, height=H, width=W_IMG, boxes_per_image=BOXES, seed=seed, dev=torch.device(DEV, 0), fed_loss=True)
