@@ -92,7 +92,13 @@ struct Problem {
 };
 
 std::atomic<int> g_fwd_variant{0}, g_bwd_variant{0}, g_bwd_cpl{0}, g_levelsum{1}, g_fwd_prep_fused{1}, g_bwd_split{1}, g_bwd_dd_roles{1}, g_bwd_dd_roles_calls{0};
-thread_local int g_tl_fwd_variant = -1;      // >= 0: the forward variant of THIS call (set by a caller inside the library that has already chosen)
+
+// The options a call's path depends on, read ONCE -- `Options{}` at the start of the exported call -- and passed down: a msda_set_option
+// from another thread in the middle of a call cannot give a call that follows neither the old value nor the new.
+struct Options {
+    int fwd_variant = g_fwd_variant.load(), fwd_prep_fused = g_fwd_prep_fused.load(), bwd_variant = g_bwd_variant.load(), bwd_cpl = g_bwd_cpl.load(),
+        levelsum = g_levelsum.load(), bwd_split = g_bwd_split.load(), bwd_dd_roles = g_bwd_dd_roles.load();
+};
 
 // ---- launch profiler: pre-created event pairs, one per logged call -----------------------------
 struct ProfileSlot {
@@ -136,6 +142,26 @@ struct ProfileScope {
         if (slot) (void)hipEventRecord(slot->stop, stream);
     }
 };
+
+// ---- one path of a call: bracket it for the profiler, launch, map the error ------------------------------------------------------------
+// launch() returns the hipError_t of its launches and hip_fail's words about it.  An ATTEMPT may answer hipErrorNotSupported -- its plan does
+// not apply, or no workspace can be had right now --: the profile record is given back and the call goes on to the next path (kNextPath).
+struct Launched {
+    hipError_t e;
+    const char *what = "", *tag = "";
+};
+constexpr int kNextPath = 1 << 30;
+enum class Attempt { kNo, kRecordStaysOnError, kRecordBackOnError };
+template <typename Launch>
+int run_path(int kind, int prof_variant, int dtype_bytes, Attempt attempt, const Problem &pb, hipStream_t stream, Launch launch)
+{
+    ProfileScope prof(kind, prof_variant, dtype_bytes, pb, stream);
+    const Launched l = launch();
+    const bool refused = attempt != Attempt::kNo && l.e == hipErrorNotSupported;
+    if (refused || (attempt == Attempt::kRecordBackOnError && l.e != hipSuccess)) prof.cancel();
+    if (l.e == hipSuccess) return MSDA_OK;
+    return refused ? kNextPath : hip_fail(l.e, l.what, l.tag);
+}
 
 
 // ---- locality monitor -----------------------------------------------------------------------------------
@@ -212,6 +238,13 @@ Monitor *monitor_for_current_device()
     return &g_monitors[dev];
 }
 
+bool capturing(hipStream_t stream)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(stream, &cap);
+    return cap != hipStreamCaptureStatusNone;
+}
+
 // Forward, automatic mode, window kernels applicable.  Returns the variant to run (1 direct, 2 window) and, through
 // *probe, the device counter the window kernel should add its general points to (or null).  With *probe set the caller
 // MUST call monitor_finish_probe after its launch.  The monitor's mutex is held from here to monitor_finish_probe.
@@ -219,11 +252,9 @@ int monitor_choose_fwd(Monitor *mo, uint64_t key, hipStream_t stream, unsigned *
 {
     *probe = nullptr;
     if (!mo || !g_monitor_on.load()) return 2;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const bool in_capture = capturing(stream);
     mo->mu.lock();
-    if (!capturing) monitor_poll(*mo);   // (querying an event is not allowed while a capture is under way)
+    if (!in_capture) monitor_poll(*mo);   // (querying an event is not allowed while a capture is under way)
     if (mo->table.size() > kMonitorMaxEntries) mo->table.clear();
     MonitorEntry &en = mo->table[key];
     const unsigned call = en.calls++;
@@ -233,7 +264,7 @@ int monitor_choose_fwd(Monitor *mo, uint64_t key, hipStream_t stream, unsigned *
         if (!mo->slot[i].pending && free_slot < 0) free_slot = i;
         mine_in_flight = mine_in_flight || (mo->slot[i].pending && mo->slot[i].key == key);
     }
-    bool want = free_slot >= 0 && !mine_in_flight && !capturing && call >= en.next_probe;
+    bool want = free_slot >= 0 && !mine_in_flight && !in_capture && call >= en.next_probe;
     if (want && !mo->dev) {   // first probe on this device
         bool ok = hipMalloc(reinterpret_cast<void **>(&mo->dev), kProbeSlots * sizeof(unsigned)) == hipSuccess &&
                   hipHostMalloc(reinterpret_cast<void **>(&mo->host), kProbeSlots * sizeof(unsigned), hipHostMallocDefault) == hipSuccess;
@@ -288,22 +319,6 @@ FwdChoice choose_window_fwd(int asked, const Problem &pb, const void *loc, hipSt
     return ch;
 }
 
-// One launch of a window forward kernel (profile variant 2; 6 with the location / softmax arithmetic fused in): bracket it, launch,
-// hand the probe back to the monitor, map the error.  launch(probe) returns the hipError_t of the launch.
-template <typename Launch>
-int run_window_fwd(const FwdChoice &ch, int prof_variant, int dtype_bytes, const Problem &pb, hipStream_t stream, const char *what,
-                   const char *tag, Launch launch)
-{
-    hipError_t e;
-    {
-        ProfileScope prof(0, prof_variant, dtype_bytes, pb, stream);
-        e = launch(ch.probe);
-    }
-    if (ch.probe) monitor_finish_probe(ch.mo, 2.0 * pb.N * pb.Lq * pb.M * pb.L * pb.P, stream, e == hipSuccess);
-    if (e != hipSuccess) return hip_fail(e, what, tag);
-    return MSDA_OK;
-}
-
 // Argument checks shared by forward and backward.  Mirrors the reference's preconditions
 // (ms_deform_attn_cuda.cu:28-52) and adds the bounds the kernels rely on.
 int check_problem(Problem &pb, const int64_t *shapes_dev, const int64_t *lsi_dev, const int64_t *shapes_host,
@@ -349,6 +364,19 @@ int check_problem(Problem &pb, const int64_t *shapes_dev, const int64_t *lsi_dev
     if (total != pb.S)
         return fail(MSDA_ERR_BAD_DIMS, "sum of H*W over levels (%lld) != S (%d)", (long long)total, pb.S);
     return MSDA_OK;
+}
+
+// The checked problem of ONE exported call: msda_forward_*, msda_backward_* and msda_forward_prep_* each run this exactly once per call; nothing
+// else calls check_problem.  Error text reset, null pointers (`non_null`), check_problem, alignment (`ptrs_aligned`; `misaligned`: its refusal).
+struct LevelTables { const int64_t *shapes, *lsi, *shapes_host, *lsi_host; };
+int misaligned_fail(const char *which) { return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (%s)", which); }
+int checked_problem(Problem &pb, bool non_null, const LevelTables &lt, int im2col_step, hipStream_t stream, bool ptrs_aligned,
+                    const char *misaligned)
+{
+    g_err[0] = 0;
+    if (!non_null) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (int rc = check_problem(pb, lt.shapes, lt.lsi, lt.shapes_host, lt.lsi_host, im2col_step, stream)) return rc;
+    return ptrs_aligned ? MSDA_OK : misaligned_fail(misaligned);
 }
 
 int floor_log2(int x)
@@ -438,8 +466,7 @@ struct Workspace {
     float *gv32 = nullptr;   // bf16 backward: fp32 accumulation buffer for grad_value (rounded to bf16 once)
     size_t gv32_cap = 0;
     unsigned *rps_bins = nullptr;            // routed backward: queue heads (32 words), then one 64-bit (records | runs) counter per
-    size_t rps_bins_cap = 0;                 // bin on a 128-byte line of its own
-    size_t rps_bins_n = 0;                   // capacity in bins
+    size_t rps_bins_n = 0;                   // bin on a 128-byte line of its own (rps_bins_words); capacity in bins
     uint2 *rps_runs = nullptr;               // [cap] the bins' run tables (nbins x max_runs)
     size_t rps_runs_cap = 0;
     msda::RpsRec *rps_entries = nullptr;     // [cap] routed records
@@ -453,6 +480,24 @@ struct Workspace {
 };
 std::mutex g_ws_mu;
 std::map<std::pair<int, hipStream_t>, Workspace> g_ws;
+
+// Under g_ws_mu, the one place a workspace is allocated: make `ptr` a buffer of `need` elements of `elem_bytes` (+ `extra_bytes` behind them)
+// at least.  Nothing while the stream is being captured, the old buffer retired, the new one half as large again as needed (+ `pad`
+// elements).  false, with the runtime's error cleared, when there is no buffer to be had: the caller falls back or refuses.
+template <typename E>
+bool grow_buffer(Workspace &ws, hipStream_t stream, E *&ptr, size_t &cap, size_t need, size_t pad, size_t elem_bytes, size_t extra_bytes = 0)
+{
+    if (cap >= need) return true;
+    if (capturing(stream)) return false;
+    ws.retire(ptr);
+    ptr = nullptr;
+    cap = 0;
+    const size_t want = need + need / 2 + pad;
+    if (hipMalloc(reinterpret_cast<void **>(&ptr), want * elem_bytes + extra_bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+    cap = want;
+    return true;
+}
+
 int g_cu_count[kMaxDevices] = {0};
 
 int cu_count()
@@ -470,49 +515,29 @@ int cu_count()
 // ---- routed pixel-stationary backward (msda_rps.h) ---------------------------------------------------------------------------
 // The bin counters are zero between calls (the tile kernel zeroes a bin's counter when it has consumed the bin), so that no call has to clear
 // them first: they are cleared when allocated and after a launch error.
-bool rps_workspace(hipStream_t stream, size_t n_bins, size_t n_runs, size_t n_entries, Workspace &out)
+struct RpsBuffers { unsigned *bins; uint2 *runs; msda::RpsRec *entries; size_t entries_cap; };
+constexpr size_t rps_bins_words(size_t n_bins) { return 32 + (size_t)msda::kRpsPad * n_bins + 8; }
+
+bool rps_workspace(hipStream_t stream, size_t n_bins, size_t n_runs, size_t n_entries, RpsBuffers &out)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return false;
     std::lock_guard<std::mutex> lock(g_ws_mu);
     Workspace &ws = g_ws[std::make_pair(dev, stream)];
-    if (ws.rps_bins_n < n_bins || ws.rps_runs_cap < n_runs || ws.rps_entries_cap < n_entries || ws.rps_dirty) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(stream, &cap);
-        if (cap != hipStreamCaptureStatusNone) return false;   // no allocation while the stream is being captured
-        if (ws.rps_bins_n < n_bins) {
-            const size_t cap_n = n_bins + n_bins / 2 + 64;
-            const size_t want_bins = 32 + (size_t)msda::kRpsPad * cap_n + 8;
-            ws.retire(ws.rps_bins);
-            ws.rps_bins = nullptr;
-            ws.rps_bins_cap = ws.rps_bins_n = 0;
-            if (hipMalloc(reinterpret_cast<void **>(&ws.rps_bins), want_bins * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return false; }
-            ws.rps_bins_cap = want_bins;
-            ws.rps_bins_n = cap_n;
-            ws.rps_dirty = true;
-        }
-        if (ws.rps_dirty) {
-            if (hipMemsetAsync(ws.rps_bins, 0, ws.rps_bins_cap * sizeof(unsigned), stream) != hipSuccess) { (void)hipGetLastError(); return false; }
-            ws.rps_dirty = false;
-        }
-        if (ws.rps_runs_cap < n_runs) {
-            ws.retire(ws.rps_runs);
-            ws.rps_runs = nullptr;
-            ws.rps_runs_cap = 0;
-            const size_t want = n_runs + n_runs / 2 + 1024;
-            if (hipMalloc(reinterpret_cast<void **>(&ws.rps_runs), want * sizeof(uint2)) != hipSuccess) { (void)hipGetLastError(); return false; }
-            ws.rps_runs_cap = want;
-        }
-        if (ws.rps_entries_cap < n_entries) {   // (+ the tile kernel's scratch lines behind the records)
-            ws.retire(ws.rps_entries);
-            ws.rps_entries = nullptr;
-            ws.rps_entries_cap = 0;
-            const size_t want = n_entries + n_entries / 2;
-            if (hipMalloc(reinterpret_cast<void **>(&ws.rps_entries), want * sizeof(msda::RpsRec) + msda::kRpsDummyBytes) != hipSuccess) { (void)hipGetLastError(); return false; }
-            ws.rps_entries_cap = want;
-        }
+    // in this order: allocate -> mark dirty -> clear
+    if (ws.rps_bins_n < n_bins) {
+        if (!grow_buffer(ws, stream, ws.rps_bins, ws.rps_bins_n, n_bins, 64, msda::kRpsPad * sizeof(unsigned), rps_bins_words(0) * sizeof(unsigned)))
+            return false;
+        ws.rps_dirty = true;
     }
-    out = ws;
+    if (ws.rps_dirty) {
+        if (capturing(stream)) return false;      // (a call being captured neither allocates nor clears)
+        if (hipMemsetAsync(ws.rps_bins, 0, rps_bins_words(ws.rps_bins_n) * sizeof(unsigned), stream) != hipSuccess) { (void)hipGetLastError(); return false; }
+        ws.rps_dirty = false;
+    }
+    if (!grow_buffer(ws, stream, ws.rps_runs, ws.rps_runs_cap, n_runs, 1024, sizeof(uint2))) return false;
+    if (!grow_buffer(ws, stream, ws.rps_entries, ws.rps_entries_cap, n_entries, 0, sizeof(msda::RpsRec), msda::kRpsDummyBytes)) return false;      // (+ the tile kernel's scratch lines)
+    out = RpsBuffers{ws.rps_bins, ws.rps_runs, ws.rps_entries, ws.rps_entries_cap};
     return true;
 }
 
@@ -535,16 +560,16 @@ hipError_t launch_bwd_rps(const Problem &pb, const TV *value, const float *loc, 
     // rows: 16 B (fp32) / 8 B (bf16) per lane access
     if (!aligned(sizeof(TV) * 4, {value, grad_out, grad_value}) || !aligned(16, {grad_acc}) || !aligned(8, {grad_loc, loc})) return hipErrorNotSupported;
     if ((int64_t)pb.N * pb.Lq * pb.M * msda::kRpsD * (int64_t)sizeof(TV) > (int64_t)0xFFFFFFFF) return hipErrorNotSupported;      // (the tile kernel addresses grad_out rows by 32-bit byte offsets)
-    Workspace ws;
+    RpsBuffers ws;
     const size_t n_runs = (size_t)pl.g.nbins * (size_t)pl.g.max_runs;
     if (n_runs * sizeof(uint2) > ((size_t)256 << 20)) return hipErrorNotSupported;      // (run tables of a quarter GB: not a shape this path is for)
     if (!rps_workspace(stream, (size_t)pl.g.nbins, n_runs, pl.max_entries, ws)) return hipErrorNotSupported;
-    pl.g.ctr = ws.rps_bins;
-    pl.g.bin_state = reinterpret_cast<unsigned long long *>(ws.rps_bins + 32);   // (line-aligned; one per 128-B line)
-    pl.g.runs = ws.rps_runs;
-    pl.g.entries_cap = (unsigned)std::min<size_t>(ws.rps_entries_cap, 0xFFFFFFFFu);
-    pl.g.entries = ws.rps_entries;
-    pl.g.dummy = reinterpret_cast<float *>(ws.rps_entries + ws.rps_entries_cap);
+    pl.g.ctr = ws.bins;
+    pl.g.bin_state = reinterpret_cast<unsigned long long *>(ws.bins + 32);   // (line-aligned; one per 128-B line)
+    pl.g.runs = ws.runs;
+    pl.g.entries_cap = (unsigned)std::min<size_t>(ws.entries_cap, 0xFFFFFFFFu);
+    pl.g.entries = ws.entries;
+    pl.g.dummy = reinterpret_cast<float *>(ws.entries + ws.entries_cap);
     pl.g.stamps = msda::tiled_options().stamps;
     auto kern = pl.g.stamps ? (pb.P == 4 ? &msda::rps_tile_kernel<true, TV, true> : &msda::rps_tile_kernel<false, TV, true>)
                             : (pb.P == 4 ? &msda::rps_tile_kernel<true, TV> : &msda::rps_tile_kernel<false, TV>);
@@ -619,10 +644,8 @@ hipError_t launch_fwd_split(const Problem &pb, const TV *value, const int64_t *s
                             TV *out, const msda::DirectGeom &g, hipStream_t stream)
 {
     const size_t lds = sizeof(msda::LevelGeom) * pb.L;
-    if (pb.L * pb.P == 16)
-        hipLaunchKernelGGL((msda::fwd_split_kernel<TV, 4>), split_grid(pb), dim3(msda::kDirectThreads), lds, stream, value, shapes, lsi, loc, aw, out, g);
-    else
-        hipLaunchKernelGGL((msda::fwd_split_kernel<TV, 0>), split_grid(pb), dim3(msda::kDirectThreads), lds, stream, value, shapes, lsi, loc, aw, out, g);
+    auto kern = pb.L * pb.P == 16 ? &msda::fwd_split_kernel<TV, 4> : &msda::fwd_split_kernel<TV, 0>;
+    hipLaunchKernelGGL(kern, split_grid(pb), dim3(msda::kDirectThreads), lds, stream, value, shapes, lsi, loc, aw, out, g);
     return hipGetLastError();
 }
 
@@ -631,12 +654,8 @@ hipError_t launch_bwd_split(const Problem &pb, const TV *value, const int64_t *s
                             const TV *grad_out, float *grad_loc, float *grad_aw, const msda::DirectGeom &g, hipStream_t stream)
 {
     const size_t lds = sizeof(msda::LevelGeom) * pb.L;
-    if (pb.L * pb.P == 16)
-        hipLaunchKernelGGL((msda::bwd_split_kernel<TV, 4>), split_grid(pb), dim3(msda::kDirectThreads), lds, stream, value, shapes, lsi, loc, aw,
-                           grad_out, grad_loc, grad_aw, g);
-    else
-        hipLaunchKernelGGL((msda::bwd_split_kernel<TV, 0>), split_grid(pb), dim3(msda::kDirectThreads), lds, stream, value, shapes, lsi, loc, aw,
-                           grad_out, grad_loc, grad_aw, g);
+    auto kern = pb.L * pb.P == 16 ? &msda::bwd_split_kernel<TV, 4> : &msda::bwd_split_kernel<TV, 0>;
+    hipLaunchKernelGGL(kern, split_grid(pb), dim3(msda::kDirectThreads), lds, stream, value, shapes, lsi, loc, aw, grad_out, grad_loc, grad_aw, g);
     return hipGetLastError();
 }
 
@@ -663,6 +682,23 @@ hipError_t launch_bwd_dd_roles(const Problem &pb, const float *value, const int6
     return hipGetLastError();
 }
 
+// ---- level-sum backward (msda_levelsum.h): grad_value of the levels of `lg`, summed in LDS windows -----------------------------------------
+// *at_lds_limit: the error returned is the refusal of the kernel's LDS size, not of its launch
+template <typename TV>
+hipError_t launch_bwd_levelsum(const Problem &pb, const float *loc, const float *aw, const TV *grad_out, TV *grad_value,
+                               const msda::LevelSumGeom &lg, size_t lds, hipStream_t stream, bool *at_lds_limit)
+{
+    // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
+    // for element alignment only)
+    const bool vec = pb.P == 4 && aligned(16, {loc, aw});
+    auto kern = vec ? &msda::bwd_levelsum_kernel<true, TV> : &msda::bwd_levelsum_kernel<false, TV>;
+    const hipError_t e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), lds);
+    *at_lds_limit = e != hipSuccess;
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(msda::levelsum_grid(lg)), dim3(msda::kLsThreads), lds, stream, loc, aw, grad_out, grad_value, lg);
+    return hipGetLastError();
+}
+
 // ---- bf16 storage (value / out / grad_out / grad_value), fp32 compute: the fp32 scratch image of grad_value and its one rounding -------
 bool bf16_scratch(hipStream_t stream, size_t n_floats, float **out)
 {
@@ -670,20 +706,20 @@ bool bf16_scratch(hipStream_t stream, size_t n_floats, float **out)
     if (hipGetDevice(&dev) != hipSuccess) return false;
     std::lock_guard<std::mutex> lock(g_ws_mu);
     Workspace &ws = g_ws[std::make_pair(dev, stream)];
-    if (ws.gv32_cap < n_floats) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(stream, &cap);
-        if (cap != hipStreamCaptureStatusNone) return false;
-        ws.retire(ws.gv32);      // (not freed: an earlier capture on this stream may hold the address)
-        ws.gv32 = nullptr;
-        ws.gv32_cap = 0;
-        const size_t want = n_floats + n_floats / 2;
-        if (hipMalloc(reinterpret_cast<void **>(&ws.gv32), want * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return false; }
-        ws.gv32_cap = want;
-    }
+    if (!grow_buffer(ws, stream, ws.gv32, ws.gv32_cap, n_floats, 0, sizeof(float))) return false;
     *out = ws.gv32;
     return true;
 }
+
+// What atomics add grad_value into: grad_value itself, or for bf16 storage the library's fp32 scratch -- null until a path asks (have()).
+template <typename T, typename TV>
+struct GradAcc {
+    T *ptr = nullptr;
+    size_t n_value;
+    hipStream_t stream;
+    GradAcc(TV *grad_value, size_t n, hipStream_t st) : n_value(n), stream(st) { if constexpr (std::is_same<T, TV>::value) ptr = grad_value; }
+    bool have() { if constexpr (std::is_same<T, TV>::value) return true; else return bf16_scratch(stream, n_value, &ptr); }
+};
 
 // n4 vectors of four elements (dst 8-byte aligned), then the n - 4*n4 elements of the tail one by one
 __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restrict__ src, msda::bf16_t *__restrict__ dst, size_t n4,
@@ -720,96 +756,195 @@ __global__ __launch_bounds__(256) void round_to_bf16_kernel(const float *__restr
 //   no scratch during stream capture  n/a                                           MSDA_ERR_BAD_DIMS
 //   error texts                       as written                                    the runtime's (HIP) errors + " (bf16)", "LDS limit"; "... needs 8
 //                                                                                   bytes"; the refusals ("too many levels", no scratch) untagged
+//
+// msda_forward_prep_* (locations computed from the projection: PrepLoc below) against msda_forward_* (locations given: GivenLoc), all types:
+//   one launch, decoder-shaped        the call's own alignment set (+ ref, offsets, logits); its misalignment text says "2*sizeof(T)" and its
+//   (fwd_prep_fused >= 1)             launch error carries no " (bf16)" for bf16 too; no split forward; profile variant 5
+//   window kernel, encoder-shaped     fp32 compute, P = 4, fwd_variant != 1: the problem is checked BEFORE the location / softmax kernel's
+//   (fwd_prep_fused = 2)              own checks (otherwise after them, and after its launch); the fused window kernel (profile variant 6)
+//                                     asks for its rows (value / out rows of four, offsets in pairs, ref / loc 8 B) and the plan only: the
+//                                     alignment set of msda_forward_* (the level tables' 8 B too) comes after it and the location / softmax launch
+//   ... the monitor chose direct      location / softmax kernel, then the 8-lane direct kernel (variant 1) with the choice held; a forced
+//       or fwd_variant = 3            fwd_variant 3 ends there too where the window kernel applies: it is not the split kernel on this path
 int too_many_levels(int L) { return fail(MSDA_ERR_BAD_DIMS, "too many levels (L=%d) for the level table in LDS", L); }
 
-template <typename T, typename TV = T>
-int forward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, const T *loc, const T *aw, int N, int S,
-                 int M, int D, int L, int Lq, int P, int im2col_step, TV *out, const int64_t *shapes_host,
-                 const int64_t *lsi_host, msda_stream_t stream_)
+// Where a forward call's sampling locations and attention weights come from, and with that all that differs between msda_forward_* and the
+// one-launch forms of msda_forward_prep_*: kernel templates, profile variants, alignment sets, error texts.  GivenLoc: the caller's tensors.
+template <typename T, typename TV>
+struct GivenLoc {
+    static constexpr bool kBf16 = std::is_same<TV, msda::bf16_t>::value, kSplit = true;      // (the split forward is tried on this path only)
+    static constexpr int kDirectVariant = 1, kWindowVariant = 2;
+    static constexpr const char *kDirectWhat = "launch of the direct forward kernel", *kWindowWhat = "launch of the tiled forward kernel";
+    static constexpr const char *kTag = kBf16 ? " (bf16)" : "", *kMisaligned = kBf16 ? "sampling_loc needs 8 bytes" : "sampling_loc needs 2*sizeof(T)";
+    const T *loc, *aw;
+    bool call_aligned(const TV *value, const TV *out, const LevelTables &lt) const
+    {
+        return aligned(sizeof(TV), {value, out}) && aligned(sizeof(T), {aw}) && aligned(2 * sizeof(T), {loc}) && aligned(8, {lt.shapes, lt.lsi});
+    }
+    bool window_rows(const TV *value, const TV *out) const { return aligned(4 * sizeof(TV), {value, out}); }
+    hipError_t launch_window(const Problem &pb, const TV *value, TV *out, unsigned *probe, hipStream_t stream) const
+    {
+        return msda::launch_fwd_tiled_tv<TV>(value, loc, aw, out, pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data(), probe, stream);
+    }
+    template <int CC, int WAVES>
+    void launch_direct(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const TV *value, const LevelTables &lt, TV *out, const msda::DirectGeom &g) const
+    {
+        hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, WAVES, TV>), grid, block, lds, stream, value, lt.shapes, lt.lsi, loc, aw, out, g);
+    }
+};
+
+// PrepLoc: computed by the kernel itself from the raw projection (offsets, logits) and the reference points; loc / aw are by-products.
+template <typename T, typename TV, typename TP>
+struct PrepLoc {
+    static constexpr bool kSplit = false;
+    static constexpr int kDirectVariant = 5, kWindowVariant = 6;
+    static constexpr const char *kDirectWhat = "launch of the fused location / softmax / gather kernel";
+    static constexpr const char *kWindowWhat = "launch of the fused location / softmax / window-gather kernel";
+    static constexpr const char *kTag = "", *kMisaligned = "sampling_loc needs 2*sizeof(T)";
+    const TP *offsets, *logits;
+    int64_t off_stride, log_stride;
+    const T *ref;
+    int ref_dim;
+    T *loc, *aw;
+    bool call_aligned(const TV *value, const TV *out, const LevelTables &lt) const
+    {
+        return aligned(sizeof(TV), {value, out}) && aligned(sizeof(T), {aw, ref}) && aligned(2 * sizeof(T), {loc}) &&
+               aligned(sizeof(TP), {offsets, logits}) && aligned(8, {lt.shapes, lt.lsi});
+    }
+    bool window_rows(const TV *value, const TV *out) const
+    {
+        return aligned(4 * sizeof(TV), {value, out}) && aligned(2 * sizeof(TP), {offsets}) && off_stride % 2 == 0 && aligned(sizeof(TP), {logits}) &&
+               aligned(8, {ref, loc}) && aligned(4, {aw});
+    }
+    hipError_t launch_window(const Problem &pb, const TV *value, TV *out, unsigned *probe, hipStream_t stream) const
+    {
+        const msda::TiledPrepSrc src{offsets, logits, (long long)off_stride, (long long)log_stride, ref, ref_dim, loc, aw};
+        return msda::launch_fwd_tiled_prep<TV, TP>(value, src, out, pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data(), probe, stream);
+    }
+    template <int CC, int WAVES>
+    void launch_direct(dim3 grid, dim3 block, size_t lds, hipStream_t stream, const TV *value, const LevelTables &lt, TV *out, const msda::DirectGeom &g) const
+    {
+        const msda::PrepSrc<TP> src{offsets, logits, off_stride, log_stride, ref_dim};
+        hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, WAVES, TV, TP>), grid, block, lds, stream, value, lt.shapes, lt.lsi, src, ref, loc, aw, out, g);
+    }
+};
+
+// The window-kernel attempt (msda_tiled.h: fp32 compute, rows read four channels at a time).  `variant`: what was asked for; where a window
+// kernel applies (*applies), what the call runs -- in automatic mode the locality monitor's choice.  kNextPath unless that is 2.
+template <typename TV, typename Src>
+int window_fwd(int &variant, bool *applies, const Problem &pb, const TV *value, TV *out, const Src &src, hipStream_t stream)
+{
+    *applies = variant != 1 && src.window_rows(value, out) &&
+               msda::plan_gather(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data()).ok;
+    if (!*applies) return kNextPath;
+    const FwdChoice ch = choose_window_fwd(variant, pb, src.loc, stream);
+    variant = ch.variant;
+    if (variant != 2) return kNextPath;
+    const int rc = run_path(0, Src::kWindowVariant, (int)sizeof(TV), Attempt::kNo, pb, stream, [&]() {
+        return Launched{src.launch_window(pb, value, out, ch.probe, stream), Src::kWindowWhat, Src::kTag};
+    });
+    if (ch.probe) monitor_finish_probe(ch.mo, 2.0 * pb.N * pb.Lq * pb.M * pb.L * pb.P, stream, rc == MSDA_OK);
+    return rc;
+}
+
+// The direct kernels (msda_direct.h); for given locations the split kernel first -- small calls at D = 32 (decoder-shaped): 32 lanes per item,
+// all of a lane's gathers in flight at once (fwd_split_kernel); fwd_variant 3 forces it wherever it applies, 1 keeps the 8-lane kernel.
+template <typename T, typename TV, typename Src>
+int direct_fwd(int variant, const Problem &pb, const TV *value, const LevelTables &lt, TV *out, const Src &src, hipStream_t stream)
 {
     constexpr bool kBf16 = std::is_same<TV, msda::bf16_t>::value;
-    constexpr const char *kTag = kBf16 ? " (bf16)" : "";
-    g_err[0] = 0;
-    if (!value || !shapes || !lsi || !loc || !aw || !out) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    Problem pb{N, S, M, D, L, Lq, P, {}, {}};
-    if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!aligned(sizeof(TV), {value, out}) || !aligned(sizeof(T), {aw}) || !aligned(2 * sizeof(T), {loc}) || !aligned(8, {shapes, lsi}))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs %s)", kBf16 ? "8 bytes" : "2*sizeof(T)");
-
-    int variant = g_tl_fwd_variant >= 0 ? g_tl_fwd_variant : g_fwd_variant.load();
-    if constexpr (std::is_same<T, float>::value) {      // the LDS-window kernel (msda_tiled.h): fp32 compute, rows read four channels at a time
-        if (variant != 1 && aligned(4 * sizeof(TV), {value, out}) &&
-            msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
-            const FwdChoice ch = choose_window_fwd(variant, pb, loc, stream);      // automatic: follow the locality monitor
-            variant = ch.variant;
-            if (variant == 2)
-                return run_window_fwd(ch, 2, (int)sizeof(TV), pb, stream, "launch of the tiled forward kernel", kTag, [&](unsigned *probe) {
-                    return msda::launch_fwd_tiled_tv<TV>(value, loc, aw, out, N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), probe, stream);
-                });
-        }
-    }
-
-    const int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, out});
+    const int C = pick_channels<TV>(pb.D, kMaxChannels<TV>, {value, out});
     msda::DirectGeom g = direct_geom(pb, C);
     const size_t lds = msda::direct_lds_bytes<T>(g);
-    if (kBf16 && lds > 64 * 1024) return too_many_levels(L);
-    // small calls at D = 32 (decoder-shaped): 32 lanes per item, all of a lane's gathers in flight at once (fwd_split_kernel);
-    // fwd_variant 3 forces it wherever it applies, 1 keeps the 8-lane kernel
-    if constexpr (std::is_same<T, float>::value) {
-        if (split_fits(pb, C) && (variant == 3 || (variant != 1 && split_small(pb)))) {
-            ProfileScope prof(0, 3, (int)sizeof(TV), pb, stream);
-            const hipError_t e = launch_fwd_split<TV>(pb, value, shapes, lsi, loc, aw, out, g, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch of the split forward kernel", kTag);
-            return MSDA_OK;
-        }
+    if (kBf16 && lds > 64 * 1024) return too_many_levels(pb.L);
+    if constexpr (Src::kSplit && std::is_same<T, float>::value) {
+        if (split_fits(pb, C) && (variant == 3 || (variant != 1 && split_small(pb))))
+            return run_path(0, 3, (int)sizeof(TV), Attempt::kNo, pb, stream, [&]() {
+                return Launched{launch_fwd_split<TV>(pb, value, lt.shapes, lt.lsi, src.loc, src.aw, out, g, stream), "launch of the split forward kernel",
+                                Src::kTag};
+            });
     }
-    if (lds > 64 * 1024) return too_many_levels(L);
-    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
-    ProfileScope prof(0, 1, (int)sizeof(TV), pb, stream);
-    with_channels<T>(C, [&](auto cc) {
-        constexpr int CC = decltype(cc)::value;
-        if (many_items(pb)) hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 6, TV>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g);
-        else hipLaunchKernelGGL((msda::fwd_direct_kernel<T, CC, 4, TV>), grid, block, lds, stream, value, shapes, lsi, loc, aw, out, g);
+    if (lds > 64 * 1024) return too_many_levels(pb.L);
+    return run_path(0, Src::kDirectVariant, (int)sizeof(TV), Attempt::kNo, pb, stream, [&]() {
+        const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
+        with_channels<T>(C, [&](auto cc) {
+            constexpr int CC = decltype(cc)::value;
+            if (many_items(pb)) src.template launch_direct<CC, 6>(grid, block, lds, stream, value, lt, out, g);
+            else src.template launch_direct<CC, 4>(grid, block, lds, stream, value, lt, out, g);
+        });
+        return Launched{hipGetLastError(), Src::kDirectWhat, Src::kTag};
     });
-    return launched("launch of the direct forward kernel", kTag);
 }
 
-// One attempt at a backward kernel that may answer hipErrorNotSupported -- its plan does not apply, or no workspace can be had right
-// now --, upon which the call goes on to the next path: returns kNextPath then, else the call's return code.
-constexpr int kNextPath = 1 << 30;
-template <typename Launch>
-int try_bwd(int prof_variant, int dtype_bytes, bool cancel_on_error, const Problem &pb, hipStream_t stream, const char *what,
-            const char *tag, Launch launch)
+// The forward of a checked problem with given locations, for the variant the caller (msda_forward_* or _forward_prep_*) decided on.
+template <typename T, typename TV>
+int forward_body(int variant, const Problem &pb, const TV *value, const LevelTables &lt, const GivenLoc<T, TV> &src, TV *out, hipStream_t stream)
 {
-    hipError_t e;
-    {
-        ProfileScope prof(1, prof_variant, dtype_bytes, pb, stream);
-        e = launch();
-        if (e == hipErrorNotSupported || (cancel_on_error && e != hipSuccess)) prof.cancel();
+    if constexpr (std::is_same<T, float>::value) {
+        bool applies;
+        const int rc = window_fwd(variant, &applies, pb, value, out, src, stream);
+        if (rc != kNextPath) return rc;
     }
-    if (e == hipSuccess) return MSDA_OK;
-    return e == hipErrorNotSupported ? kNextPath : hip_fail(e, what, tag);
+    return direct_fwd<T, TV>(variant, pb, value, lt, out, src, stream);
 }
 
 template <typename T, typename TV = T>
-int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, const T *loc, const T *aw,
-                  const TV *grad_out, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step, TV *grad_value,
-                  T *grad_loc, T *grad_aw, const int64_t *shapes_host, const int64_t *lsi_host, msda_stream_t stream_)
+int forward_impl(const Options &opt, const TV *value, const LevelTables &lt, const T *loc, const T *aw, int N, int S, int M, int D, int L, int Lq,
+                 int P, int im2col_step, TV *out, msda_stream_t stream_)
+{
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const GivenLoc<T, TV> src{loc, aw};
+    Problem pb{N, S, M, D, L, Lq, P, {}, {}};
+    if (int rc = checked_problem(pb, value && lt.shapes && lt.lsi && loc && aw && out, lt, im2col_step, stream, src.call_aligned(value, out, lt),
+                                 src.kMisaligned))
+        return rc;
+    return forward_body<T, TV>(opt.fwd_variant, pb, value, lt, src, out, stream);
+}
+
+// One attempt of an fp32-compute backward call at the routed pixel-stationary kernels (msda_rps.h; variant 4) or the row-band kernel
+// (msda_band.h; variant 5): kNextPath when the kernel does not apply.  Both take grad_value twice: the tensor, and an fp32 image for the
+// levels several workgroups add to -- grad_value itself, or for bf16 the library's scratch (zeroed by the kernels, rounded once at the end);
+// plain bf16 stores serve the levels a workgroup owns alone.
+template <typename TV>
+int bwd_routed_or_band(int variant, const Problem &pb, const TV *value, const float *loc, const float *aw, const TV *grad_out, TV *grad_value,
+                       float *grad_loc, float *grad_aw, hipStream_t stream)
 {
     constexpr bool kBf16 = std::is_same<TV, msda::bf16_t>::value;
     constexpr const char *kTag = kBf16 ? " (bf16)" : "";
-    g_err[0] = 0;
-    if (!value || !shapes || !lsi || !loc || !aw || !grad_out || !grad_value || !grad_loc || !grad_aw)
-        return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    constexpr Attempt kAttempt = kBf16 ? Attempt::kRecordStaysOnError : Attempt::kRecordBackOnError;      // (the table's "... a launch error there")
+    if (kBf16 && !aligned(8, {value, grad_out, grad_value})) return kNextPath;
+    GradAcc<float, TV> acc(grad_value, (size_t)pb.N * pb.S * pb.M * pb.D, stream);
+    bool go = false;
+    if (variant == 4) go = (!kBf16 || pb.D == msda::kRpsD) && acc.have();
+    else if (variant == 5 && (!kBf16 || pb.D == msda::kBandD)) {
+        go = true;
+        if constexpr (kBf16) {      // (a scratch only if the plan has levels that several workgroups add to)
+            const msda::BandPlan bp = msda::plan_band(pb.N, pb.S, pb.M, pb.D, pb.L, pb.Lq, pb.P, pb.shapes.data(), pb.lsi.data());
+            go = bp.ok && (!bp.atomic_levels || acc.have());
+        }
+    }
+    if (!go) return kNextPath;
+    return run_path(1, variant, (int)sizeof(TV), kAttempt, pb, stream, [&]() {
+        if (variant == 4)
+            return Launched{launch_bwd_rps<TV>(pb, value, loc, aw, grad_out, grad_value, acc.ptr, grad_loc, grad_aw, stream), "launch of the routed backward kernels", kTag};
+        return Launched{launch_bwd_band<TV>(pb, value, loc, aw, grad_out, grad_value, acc.ptr, grad_loc, grad_aw, stream), "launch of the row-band backward kernel", kTag};
+    });
+}
+
+template <typename T, typename TV = T>
+int backward_impl(const Options &opt, const TV *value, const LevelTables &lt, const T *loc, const T *aw, const TV *grad_out, int N, int S, int M,
+                  int D, int L, int Lq, int P, int im2col_step, TV *grad_value, T *grad_loc, T *grad_aw, msda_stream_t stream_)
+{
+    constexpr bool kBf16 = std::is_same<TV, msda::bf16_t>::value;
+    constexpr const char *kTag = kBf16 ? " (bf16)" : "";
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     Problem pb{N, S, M, D, L, Lq, P, {}, {}};
-    if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!aligned(sizeof(TV), {value, grad_out, grad_value}) || !aligned(sizeof(T), {aw, grad_aw}) || !aligned(2 * sizeof(T), {loc, grad_loc}) ||
-        !aligned(8, {shapes, lsi}))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc / grad_sampling_loc need %s)", kBf16 ? "8 bytes" : "2*sizeof(T)");
+    if (int rc = checked_problem(pb, value && lt.shapes && lt.lsi && loc && aw && grad_out && grad_value && grad_loc && grad_aw, lt, im2col_step, stream,
+                                 aligned(sizeof(TV), {value, grad_out, grad_value}) && aligned(sizeof(T), {aw, grad_aw}) &&
+                                     aligned(2 * sizeof(T), {loc, grad_loc}) && aligned(8, {lt.shapes, lt.lsi}),
+                                 kBf16 ? "sampling_loc / grad_sampling_loc need 8 bytes" : "sampling_loc / grad_sampling_loc need 2*sizeof(T)"))
+        return rc;
     const size_t n_value = (size_t)N * S * M * D;
-    hipError_t e = hipSuccess;
 
     // Kernel choice: the routed pixel-stationary kernels (msda_rps.h: no float atomics, no zero-fill, cost independent of where
     // the points fall) for encoder-shaped fp32-compute calls at D = 32 (bwd_variant 4 forces them for any Lq, 1 forces the direct
@@ -817,119 +952,84 @@ int backward_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, co
     // bwd_variant 5: the row-band kernel (msda_band.h) -- grad_value, grad_sampling_loc and grad_attn_weight in ONE launch, no zero-fill of
     // grad_value.  A measured option, not the automatic choice: 101-123 us on the decoder call Dd against 88 us for the level-sum + direct
     // kernels below (profiles/r05_dd_backward.md).
-    // Both take grad_value twice: the tensor, and an fp32 image for the levels several workgroups add to -- grad_value itself, or for bf16
-    // the library's scratch (zeroed by the kernels, rounded once at the end); plain bf16 stores serve the levels a workgroup owns alone.
     if constexpr (std::is_same<T, float>::value) {
-        int variant = g_bwd_variant.load();
-        if (variant == 0) variant = Lq == S ? 4 : 1;
-        const bool rows = !kBf16 || aligned(8, {value, grad_out, grad_value});
-        float *acc = nullptr;
-        if constexpr (!kBf16) acc = grad_value;
-        if (variant == 4 && rows && (!kBf16 || (D == msda::kRpsD && bf16_scratch(stream, n_value, &acc)))) {
-            const int rc = try_bwd(4, (int)sizeof(TV), !kBf16, pb, stream, "launch of the routed backward kernels", kTag, [&]() {
-                return launch_bwd_rps<TV>(pb, value, loc, aw, grad_out, grad_value, acc, grad_loc, grad_aw, stream);
-            });
-            if (rc != kNextPath) return rc;
-        }
-        if (variant == 5 && rows && (!kBf16 || D == msda::kBandD)) {
-            bool go = true;
-            if constexpr (kBf16) {
-                const msda::BandPlan bp = msda::plan_band(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data());
-                go = bp.ok && (!bp.atomic_levels || bf16_scratch(stream, n_value, &acc));
-            }
-            if (go) {
-                const int rc = try_bwd(5, (int)sizeof(TV), !kBf16, pb, stream, "launch of the row-band backward kernel", kTag, [&]() {
-                    return launch_bwd_band<TV>(pb, value, loc, aw, grad_out, grad_value, acc, grad_loc, grad_aw, stream);
-                });
-                if (rc != kNextPath) return rc;
-            }
-        }
+        const int variant = opt.bwd_variant ? opt.bwd_variant : (Lq == S ? 4 : 1);
+        const int rc = bwd_routed_or_band<TV>(variant, pb, value, loc, aw, grad_out, grad_value, grad_loc, grad_aw, stream);
+        if (rc != kNextPath) return rc;
     }
 
     // Direct path.  Levels summed in f64 LDS windows by their own kernel (msda_levelsum.h; fp32 compute only) are taken away from the
     // atomics below; when that is ALL levels (decoder-shaped calls) grad_value is written, not accumulated: no zero-fill, no atomics, and
     // for bf16 no scratch (the window is rounded at its one store).  bf16 takes all levels or none: otherwise every corner goes to the
     // fp32 scratch with row atomics.
-    const unsigned all_levels = all_levels_mask(L);
     unsigned ls_levels = 0;
     msda::LevelSumGeom lg;
     size_t ls_lds = 0;
     if constexpr (std::is_same<T, float>::value) {
         // (its plain per-level stores need the levels to tile [0, S) without overlap; check_problem only bounds them)
-        if (g_levelsum.load() && levels_tile(pb))
+        if (opt.levelsum && levels_tile(pb))
             ls_levels = msda::plan_levelsum(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), lg, ls_lds);
-        if (kBf16 && ls_levels != all_levels) ls_levels = 0;
+        if (kBf16 && ls_levels != all_levels_mask(L)) ls_levels = 0;
     }
+    const bool all_summed = ls_levels == all_levels_mask(L);
     // what the direct kernel accumulates grad_value into (the reference gets it from at::zeros_like, ms_deform_attn_cuda.cu:121)
-    T *acc = nullptr;
-    if constexpr (!kBf16) acc = grad_value;
-    if (ls_levels != all_levels) {
-        if constexpr (kBf16) {
-            if (!bf16_scratch(stream, n_value, &acc))
-                return fail(MSDA_ERR_BAD_DIMS, "bf16 backward of this shape needs an fp32 scratch buffer, which cannot be allocated "
-                                               "while the stream is being captured: run the call once outside the capture");
-        }
-        if ((e = hipMemsetAsync(acc, 0, sizeof(T) * n_value, stream)) != hipSuccess)
-            return hip_fail(e, kBf16 ? "zero-fill of the fp32 scratch" : "zero-fill of grad_value");
+    GradAcc<T, TV> acc(grad_value, n_value, stream);
+    if (!all_summed) {
+        if (!acc.have())
+            return fail(MSDA_ERR_BAD_DIMS, "bf16 backward of this shape needs an fp32 scratch buffer, which cannot be allocated "
+                                           "while the stream is being captured: run the call once outside the capture");
+        const hipError_t e = hipMemsetAsync(acc.ptr, 0, sizeof(T) * n_value, stream);
+        if (e != hipSuccess) return hip_fail(e, kBf16 ? "zero-fill of the fp32 scratch" : "zero-fill of grad_value");
     }
     // Float atomics run at full rate only as >= 128-B row segments (one dword per lane): with 32 or more
     // channels put ONE channel on a lane, so that a wave-instruction adds two whole 128-B rows.
     int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, grad_out});
-    const int cpl = kBf16 ? 0 : g_bwd_cpl.load();
+    const int cpl = kBf16 ? 0 : opt.bwd_cpl;
     if (cpl > 0) C = cpl <= C ? cpl : C;
-    else if (D * (int)sizeof(T) >= 128 && ls_levels != all_levels) C = 1;
+    else if (D * (int)sizeof(T) >= 128 && !all_summed) C = 1;
     msda::DirectGeom g = direct_geom(pb, C);
     const size_t lds = msda::direct_lds_bytes<T>(g);
     if (lds > 64 * 1024) return too_many_levels(L);
-    ProfileScope prof(1, 1, (int)sizeof(TV), pb, stream);
-    if constexpr (std::is_same<T, float>::value) {
-        // (forking the level-sum kernel onto a second stream beside the direct kernel was tried: the cross-stream fork / join costs
-        // more than the overlap gains on a 90 us call -- 113 vs 96 us; what runs the two jobs in one pass is the role kernel right below)
-        // decoder-shaped calls (every level summed in LDS, the split kernel for the other two gradients): both jobs in ONE launch whose
-        // workgroups are of two kinds (msda_roles.h: 65.9-66.7 against 70.0-70.2 us on call Dd); bwd_dd_roles = 0 keeps the two launches
-        // below.  bf16 storage keeps them too: the one-launch form has not been measured there.
-        if constexpr (!kBf16) {
-            if (g_bwd_dd_roles.load() && ls_levels == all_levels && g_bwd_split.load() && split_fits(pb, C) && split_small(pb) && P == 4 &&
-                aligned(16, {loc, aw})) {
-                e = launch_bwd_dd_roles(pb, value, shapes, lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, g, stream);
-                if (e == hipSuccess) {
-                    ++g_bwd_dd_roles_calls;
-                    return MSDA_OK;
+    // grad_value complete after the level-sum kernel: the location / weight gradients of a small call come from the split kernel
+    // (bwd_split = 0 keeps the 8-lane one) -- and, fp32 storage, both jobs from ONE launch whose workgroups are of two kinds (msda_roles.h:
+    // 65.9-66.7 against 70.0-70.2 us on call Dd; bwd_dd_roles = 0 keeps the two launches; bf16 storage keeps them too: the one-launch form
+    // has not been measured there).  (Forking the level-sum kernel onto a second stream beside the direct kernel was tried: the cross-stream
+    // fork / join costs more than the overlap gains on a 90 us call -- 113 vs 96 us.)
+    const bool split = all_summed && opt.bwd_split && split_fits(pb, C) && split_small(pb);
+    const bool roles = !kBf16 && opt.bwd_dd_roles && split && P == 4 && aligned(16, {loc, aw});
+    return run_path(1, 1, (int)sizeof(TV), Attempt::kNo, pb, stream, [&]() -> Launched {
+        hipError_t e;
+        if constexpr (std::is_same<T, float>::value) {
+            if constexpr (!kBf16) {
+                if (roles) {
+                    e = launch_bwd_dd_roles(pb, value, lt.shapes, lt.lsi, loc, aw, grad_out, grad_value, grad_loc, grad_aw, g, stream);
+                    if (e == hipSuccess) ++g_bwd_dd_roles_calls;
+                    if (e != hipErrorNotSupported) return {e, "launch of the level-sum / split role kernel"};
                 }
-                if (e != hipErrorNotSupported) return hip_fail(e, "launch of the level-sum / split role kernel");
+            }
+            if (ls_levels) {
+                bool at_lds_limit;
+                e = launch_bwd_levelsum<TV>(pb, loc, aw, grad_out, grad_value, lg, ls_lds, stream, &at_lds_limit);
+                if (e != hipSuccess && at_lds_limit) return {e, kBf16 ? "LDS limit" : "launch of the level-sum backward kernel"};
+                if (e != hipSuccess) return {e, "launch of the level-sum backward kernel", kTag};
+                g.gv_skip = ls_levels;
+            }
+            if (split) return {launch_bwd_split<TV>(pb, value, lt.shapes, lt.lsi, loc, aw, grad_out, grad_loc, grad_aw, g, stream), "launch of the split backward kernel", kTag};
+        }
+        with_channels<T>(C, [&](auto cc) {
+            hipLaunchKernelGGL((msda::bwd_direct_kernel<T, decltype(cc)::value, TV>), dim3(direct_grid(g)), dim3(msda::kDirectThreads), lds, stream,
+                               value, lt.shapes, lt.lsi, loc, aw, grad_out, acc.ptr, grad_loc, grad_aw, g);
+        });
+        if ((e = hipGetLastError()) != hipSuccess) return {e, "launch of the direct backward kernel", kTag};
+        if constexpr (kBf16) {
+            if (!all_summed) {      // one rounding of the fp32 sums
+                const size_t n4 = aligned(8, {grad_value}) ? n_value / 4 : 0;
+                hipLaunchKernelGGL(round_to_bf16_kernel, dim3(2048), dim3(256), 0, stream, acc.ptr, grad_value, n4, n_value);
+                return {hipGetLastError(), "rounding grad_value to bf16"};
             }
         }
-        if (ls_levels) {
-            // the P4 form loads a level's four locations / weights as 16-B vectors: only for 16-B aligned tensors (the ABI asks
-            // for element alignment only)
-            const bool vec = P == 4 && aligned(16, {loc, aw});
-            auto kern = vec ? &msda::bwd_levelsum_kernel<true, TV> : &msda::bwd_levelsum_kernel<false, TV>;
-            if ((e = msda::set_lds_limit(reinterpret_cast<const void *>(kern), ls_lds)) != hipSuccess)
-                return hip_fail(e, kBf16 ? "LDS limit" : "launch of the level-sum backward kernel");
-            hipLaunchKernelGGL(kern, dim3(msda::levelsum_grid(lg)), dim3(msda::kLsThreads), ls_lds, stream, loc, aw, grad_out, grad_value, lg);
-            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the level-sum backward kernel", kTag);
-            g.gv_skip = ls_levels;
-        }
-        // grad_value is complete: the location / weight gradients of a small call come from the split kernel (bwd_split = 0 keeps the 8-lane one)
-        if (g.gv_skip == all_levels && g_bwd_split.load() && split_fits(pb, C) && split_small(pb)) {
-            e = launch_bwd_split<TV>(pb, value, shapes, lsi, loc, aw, grad_out, grad_loc, grad_aw, g, stream);
-            if (e != hipSuccess) return hip_fail(e, "launch of the split backward kernel", kTag);
-            return MSDA_OK;
-        }
-    }
-    with_channels<T>(C, [&](auto cc) {
-        hipLaunchKernelGGL((msda::bwd_direct_kernel<T, decltype(cc)::value, TV>), dim3(direct_grid(g)), dim3(msda::kDirectThreads), lds, stream,
-                           value, shapes, lsi, loc, aw, grad_out, acc, grad_loc, grad_aw, g);
+        return {hipSuccess};
     });
-    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "launch of the direct backward kernel", kTag);
-    if constexpr (kBf16) {
-        if (ls_levels != all_levels) {      // one rounding of the fp32 sums
-            const size_t n4 = aligned(8, {grad_value}) ? n_value / 4 : 0;
-            hipLaunchKernelGGL(round_to_bf16_kernel, dim3(2048), dim3(256), 0, stream, acc, grad_value, n4, n_value);
-            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "rounding grad_value to bf16");
-        }
-    }
-    return MSDA_OK;
 }
 
 // ---- module-level element-wise kernels (msda_prep.h) -----------------------------------------------------------------------------
@@ -999,70 +1099,46 @@ int prep_backward_impl(const T *grad_loc, const T *grad_aw, const T *aw, const T
 // sampling_loc) runs the location / softmax kernel and then the forward of the same library, as two launches.  Results are those of
 // msda_prep_forward_* followed by msda_forward_* (the softmax sums in a different order: last-ulp differences).
 template <typename T, typename TV, typename TP>
-int forward_prep_impl(const TV *value, const int64_t *shapes, const int64_t *lsi, const TP *offsets, int64_t off_stride, const TP *logits,
-                      int64_t log_stride, const T *ref, int ref_dim, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step,
-                      TV *out, T *loc, T *aw, const int64_t *shapes_host, const int64_t *lsi_host, msda_stream_t stream_)
+int forward_prep_impl(const Options &opt, const TV *value, const LevelTables &lt, const TP *offsets, int64_t off_stride, const TP *logits,
+                      int64_t log_stride, const T *ref, int ref_dim, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step, TV *out,
+                      T *loc, T *aw, msda_stream_t stream_)
 {
     g_err[0] = 0;
-    if (!value || !shapes || !lsi || !offsets || !logits || !ref || !out || !loc || !aw) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
+    if (!value || !lt.shapes || !lt.lsi || !offsets || !logits || !ref || !out || !loc || !aw) return fail(MSDA_ERR_NULL_POINTER, "null pointer argument");
     if (ref_dim != 2 && ref_dim != 4) return fail(MSDA_ERR_BAD_DIMS, "reference points must have 2 or 4 components, got %d", ref_dim);
     if (off_stride < (int64_t)M * L * P * 2 || log_stride < (int64_t)M * L * P)
         return fail(MSDA_ERR_BAD_DIMS, "row stride smaller than a row (offsets %lld, logits %lld)", (long long)off_stride, (long long)log_stride);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const bool fused = g_fwd_prep_fused.load() && Lq != S && L * P <= msda::kPointBatch;
+    const PrepLoc<T, TV, TP> src{offsets, logits, off_stride, log_stride, ref, ref_dim, loc, aw};
+    Problem pb{N, S, M, D, L, Lq, P, {}, {}};
+    if (opt.fwd_prep_fused && Lq != S && L * P <= msda::kPointBatch) {      // decoder-shaped: one launch
+        if (int rc = checked_problem(pb, true, lt, im2col_step, stream, src.call_aligned(value, out, lt), src.kMisaligned)) return rc;
+        return direct_fwd<T, TV>(0, pb, value, lt, out, src, stream);
+    }
     // Encoder-shaped calls (round 5): the LDS-window kernel reads the raw projection itself -- softmax by the
-    // quad that owns the query, location arithmetic by the lane that resolves the point -- and writes sampling_loc / attn_weight as
-    // by-products: no prep_forward_kernel launch, no re-read of the two tensors.  While the locality monitor sends the call to the direct
-    // kernel (spread sampling points) the two-kernel form below runs, with that choice held.
+    // quad that owns the query, location arithmetic by the lane that resolves the point --: no prep_forward_kernel launch, no re-read of loc /
+    // aw.  While the locality monitor sends the call to the direct kernel the two-launch form below runs, with that choice held.
+    const GivenLoc<T, TV> given{loc, aw};
+    int variant = opt.fwd_variant;
+    bool checked = false;
     if constexpr (std::is_same<T, float>::value) {
-        if (g_fwd_prep_fused.load() >= 2 && !fused && P == 4 && g_fwd_variant.load() != 1) {
-            Problem pb{N, S, M, D, L, Lq, P, {}, {}};
-            if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-            constexpr size_t row_align = sizeof(TV) * 4;
-            const bool rows_ok = aligned(row_align, {value, out}) && aligned(2 * sizeof(TP), {offsets}) && off_stride % 2 == 0 &&
-                                 aligned(sizeof(TP), {logits}) && aligned(8, {ref, loc}) && aligned(4, {aw});
-            if (rows_ok && msda::plan_gather(N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data()).ok) {
-                const FwdChoice ch = choose_window_fwd(g_fwd_variant.load(), pb, loc, stream);
-                if (ch.variant == 2) {
-                    const msda::TiledPrepSrc src{offsets, logits, (long long)off_stride, (long long)log_stride, ref, ref_dim, loc, aw};
-                    return run_window_fwd(ch, 6, (int)sizeof(TV), pb, stream, "launch of the fused location / softmax / window-gather kernel", "",
-                                          [&](unsigned *probe) {
-                        return msda::launch_fwd_tiled_prep<TV, TP>(value, src, out, N, S, M, D, L, Lq, P, pb.shapes.data(), pb.lsi.data(), probe, stream);
-                    });
-                }
-                // the monitor chose the direct kernel: location / softmax kernel, then the direct forward (the choice is not asked for again)
-                if (int rc = prep_forward_impl<T, TP>(offsets, off_stride, logits, log_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P, loc, aw, stream_))
-                    return rc;
-                g_tl_fwd_variant = 1;
-                const int rc = forward_impl<T, TV>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
-                g_tl_fwd_variant = -1;
-                return rc;
-            }
+        if (opt.fwd_prep_fused >= 2 && P == 4 && variant != 1) {
+            if (int rc = checked_problem(pb, true, lt, im2col_step, stream, true, "")) return rc;      // (alignment: see below)
+            checked = true;
+            bool applies;
+            const int rc = window_fwd(variant, &applies, pb, value, out, src, stream);
+            if (rc != kNextPath) return rc;
+            variant = applies ? 1 : opt.fwd_variant;
         }
     }
-    if (!fused) {
-        if (int rc = prep_forward_impl<T, TP>(offsets, off_stride, logits, log_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P, loc, aw, stream_))
-            return rc;
-        return forward_impl<T, TV>(value, shapes, lsi, loc, aw, N, S, M, D, L, Lq, P, im2col_step, out, shapes_host, lsi_host, stream_);
-    }
-    Problem pb{N, S, M, D, L, Lq, P, {}, {}};
-    if (int rc = check_problem(pb, shapes, lsi, shapes_host, lsi_host, im2col_step, stream)) return rc;
-    if (!aligned(sizeof(TV), {value, out}) || !aligned(sizeof(T), {aw, ref}) || !aligned(2 * sizeof(T), {loc}) || !aligned(sizeof(TP), {offsets, logits}) ||
-        !aligned(8, {shapes, lsi}))
-        return fail(MSDA_ERR_MISALIGNED, "misaligned pointer (sampling_loc needs 2*sizeof(T))");
-    const int C = pick_channels<TV>(D, kMaxChannels<TV>, {value, out});
-    const msda::DirectGeom g = direct_geom(pb, C);
-    const size_t lds = msda::direct_lds_bytes<T>(g);
-    if (lds > 64 * 1024) return too_many_levels(L);
-    const msda::PrepSrc<TP> src{offsets, logits, off_stride, log_stride, ref_dim};
-    const dim3 grid(direct_grid(g)), block(msda::kDirectThreads);
-    ProfileScope prof(0, 5, (int)sizeof(TV), pb, stream);
-    with_channels<T>(C, [&](auto cc) {
-        constexpr int CC = decltype(cc)::value;
-        if (many_items(pb)) hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 6, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g);
-        else hipLaunchKernelGGL((msda::fwd_direct_prep_kernel<T, CC, 4, TV, TP>), grid, block, lds, stream, value, shapes, lsi, src, ref, loc, aw, out, g);
-    });
-    return launched("launch of the fused location / softmax / gather kernel");
+    // two launches: the location / softmax kernel, then the forward with the locations it wrote
+    if (int rc = prep_forward_impl<T, TP>(offsets, off_stride, logits, log_stride, ref, ref_dim, lt.shapes_host, N, Lq, M, L, P, loc, aw, stream_))
+        return rc;
+    if (checked) {      // what is left of the check: the alignment msda_forward_* demands
+        if (!given.call_aligned(value, out, lt)) return misaligned_fail(given.kMisaligned);
+    } else if (int rc = checked_problem(pb, true, lt, im2col_step, stream, given.call_aligned(value, out, lt), given.kMisaligned))
+        return rc;
+    return forward_body<T, TV>(variant, pb, value, lt, given, out, stream);
 }
 
 // The options: one table read by msda_set_option and msda_get_option.  A value is accepted when it lies in [lo, hi] and, where `values`
@@ -1105,6 +1181,11 @@ const Option *find_option(const char *key)
         if (key && !strcmp(key, o.key)) return &o;
     return nullptr;
 }
+
+// a storage pointer of the ABI as the kernels take it: bf16 travels as uint16_t
+template <typename X> X *kptr(X *p) { return p; }
+const msda::bf16_t *kptr(const uint16_t *p) { return reinterpret_cast<const msda::bf16_t *>(p); }
+msda::bf16_t *kptr(uint16_t *p) { return reinterpret_cast<msda::bf16_t *>(p); }
 }  // namespace
 
 extern "C" {
@@ -1248,131 +1329,50 @@ int msda_profile_collect(msda_profile_record *records, int max_records, int *n_r
     return MSDA_OK;
 }
 
-int msda_forward_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                     const float *sampling_loc, const float *attn_weight, int N, int S, int M, int D, int L, int Lq,
-                     int P, int im2col_step, float *out, const int64_t *shapes_host, const int64_t *level_start_host,
-                     msda_stream_t stream)
-{
-    return forward_impl<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
-                               im2col_step, out, shapes_host, level_start_host, stream);
-}
-
-int msda_forward_f64(const double *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                     const double *sampling_loc, const double *attn_weight, int N, int S, int M, int D, int L, int Lq,
-                     int P, int im2col_step, double *out, const int64_t *shapes_host, const int64_t *level_start_host,
-                     msda_stream_t stream)
-{
-    return forward_impl<double>(value, spatial_shapes, level_start, sampling_loc, attn_weight, N, S, M, D, L, Lq, P,
-                                im2col_step, out, shapes_host, level_start_host, stream);
-}
-
-int msda_backward_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                      const float *sampling_loc, const float *attn_weight, const float *grad_out, int N, int S, int M,
-                      int D, int L, int Lq, int P, int im2col_step, float *grad_value, float *grad_sampling_loc,
-                      float *grad_attn_weight, const int64_t *shapes_host, const int64_t *level_start_host,
-                      msda_stream_t stream)
-{
-    return backward_impl<float>(value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_out, N, S, M, D, L,
-                                Lq, P, im2col_step, grad_value, grad_sampling_loc, grad_attn_weight, shapes_host,
-                                level_start_host, stream);
-}
-
-int msda_backward_f64(const double *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                      const double *sampling_loc, const double *attn_weight, const double *grad_out, int N, int S,
-                      int M, int D, int L, int Lq, int P, int im2col_step, double *grad_value,
-                      double *grad_sampling_loc, double *grad_attn_weight, const int64_t *shapes_host,
-                      const int64_t *level_start_host, msda_stream_t stream)
-{
-    return backward_impl<double>(value, spatial_shapes, level_start, sampling_loc, attn_weight, grad_out, N, S, M, D, L,
-                                 Lq, P, im2col_step, grad_value, grad_sampling_loc, grad_attn_weight, shapes_host,
-                                 level_start_host, stream);
-}
-
-int msda_forward_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                      const float *sampling_loc, const float *attn_weight, int N, int S, int M, int D, int L, int Lq, int P,
-                      int im2col_step, uint16_t *out, const int64_t *shapes_host, const int64_t *level_start_host,
-                      msda_stream_t stream)
-{
-    return forward_impl<float, msda::bf16_t>(reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, sampling_loc,
-                             attn_weight, N, S, M, D, L, Lq, P, im2col_step, reinterpret_cast<msda::bf16_t *>(out), shapes_host,
-                             level_start_host, stream);
-}
-
-int msda_backward_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start,
-                       const float *sampling_loc, const float *attn_weight, const uint16_t *grad_out, int N, int S, int M,
-                       int D, int L, int Lq, int P, int im2col_step, uint16_t *grad_value, float *grad_sampling_loc,
-                       float *grad_attn_weight, const int64_t *shapes_host, const int64_t *level_start_host,
-                       msda_stream_t stream)
-{
-    return backward_impl<float, msda::bf16_t>(reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, sampling_loc,
-                              attn_weight, reinterpret_cast<const msda::bf16_t *>(grad_out), N, S, M, D, L, Lq, P, im2col_step,
-                              reinterpret_cast<msda::bf16_t *>(grad_value), grad_sampling_loc, grad_attn_weight, shapes_host,
-                              level_start_host, stream);
-}
-
-int msda_forward_prep_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start, const float *offsets,
-                          int64_t off_stride, const float *logits, int64_t log_stride, const float *ref, int ref_dim, int N, int S, int M, int D,
-                          int L, int Lq, int P, int im2col_step, float *out, float *sampling_loc, float *attn_weight,
-                          const int64_t *shapes_host, const int64_t *level_start_host, msda_stream_t stream)
-{
-    return forward_prep_impl<float, float, float>(value, spatial_shapes, level_start, offsets, off_stride, logits, log_stride, ref, ref_dim, N, S, M,
-                                                  D, L, Lq, P, im2col_step, out, sampling_loc, attn_weight, shapes_host, level_start_host, stream);
-}
-int msda_forward_prep_f64(const double *value, const int64_t *spatial_shapes, const int64_t *level_start, const double *offsets,
-                          int64_t off_stride, const double *logits, int64_t log_stride, const double *ref, int ref_dim, int N, int S, int M, int D,
-                          int L, int Lq, int P, int im2col_step, double *out, double *sampling_loc, double *attn_weight,
-                          const int64_t *shapes_host, const int64_t *level_start_host, msda_stream_t stream)
-{
-    return forward_prep_impl<double, double, double>(value, spatial_shapes, level_start, offsets, off_stride, logits, log_stride, ref, ref_dim, N, S,
-                                                     M, D, L, Lq, P, im2col_step, out, sampling_loc, attn_weight, shapes_host, level_start_host,
-                                                     stream);
-}
-int msda_forward_prep_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start, const uint16_t *offsets,
-                           int64_t off_stride, const uint16_t *logits, int64_t log_stride, const float *ref, int ref_dim, int N, int S, int M,
-                           int D, int L, int Lq, int P, int im2col_step, uint16_t *out, float *sampling_loc, float *attn_weight,
-                           const int64_t *shapes_host, const int64_t *level_start_host, msda_stream_t stream)
-{
-    return forward_prep_impl<float, msda::bf16_t, msda::bf16_t>(
-        reinterpret_cast<const msda::bf16_t *>(value), spatial_shapes, level_start, reinterpret_cast<const msda::bf16_t *>(offsets), off_stride,
-        reinterpret_cast<const msda::bf16_t *>(logits), log_stride, ref, ref_dim, N, S, M, D, L, Lq, P, im2col_step,
-        reinterpret_cast<msda::bf16_t *>(out), sampling_loc, attn_weight, shapes_host, level_start_host, stream);
-}
-
-#define MSDA_PREP_EXPORTS(SFX, T)                                                                                                  \
-    int msda_prep_forward_##SFX(const T *offsets, int64_t off_stride, const T *logits, int64_t log_stride, const T *ref, int ref_dim, \
-                                const int64_t *shapes_host, int N, int Lq, int M, int L, int P, T *loc, T *aw, msda_stream_t stream)  \
-    {                                                                                                                             \
-        return prep_forward_impl<T>(offsets, off_stride, logits, log_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P, loc, aw,    \
-                                    stream);                                                                                      \
-    }                                                                                                                             \
-    int msda_prep_backward_##SFX(const T *grad_loc, const T *grad_aw, const T *aw, const T *offsets, int64_t off_stride,           \
-                                 const T *ref, int ref_dim, const int64_t *shapes_host, int N, int Lq, int M, int L, int P,         \
-                                 T *grad_offsets, int64_t goff_stride, T *grad_logits, int64_t glog_stride, T *grad_ref,            \
-                                 msda_stream_t stream)                                                                            \
-    {                                                                                                                             \
-        return prep_backward_impl<T>(grad_loc, grad_aw, aw, offsets, off_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P,         \
-                                     grad_offsets, goff_stride, grad_logits, glog_stride, grad_ref, stream);                       \
+// The operator's entry points of one suffix: T the compute type (sampling_loc, attn_weight, reference points and their gradients), TA the
+// storage type as the ABI spells it (uint16_t for bf16), TV as the kernels do (kptr turns one into the other).
+#define MSDA_EXPORTS(SFX, T, TA, TV)                                                                                                                 \
+    int msda_forward_##SFX(const TA *value, const int64_t *spatial_shapes, const int64_t *level_start, const T *sampling_loc,                        \
+                           const T *attn_weight, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step, TA *out,                        \
+                           const int64_t *shapes_host, const int64_t *level_start_host, msda_stream_t stream)                                        \
+    {                                                                                                                                                \
+        const LevelTables lt{spatial_shapes, level_start, shapes_host, level_start_host};                                                            \
+        return forward_impl<T, TV>(Options{}, kptr(value), lt, sampling_loc, attn_weight, N, S, M, D, L, Lq, P, im2col_step, kptr(out), stream); \
+    }                                                                                                                                                \
+    int msda_backward_##SFX(const TA *value, const int64_t *spatial_shapes, const int64_t *level_start, const T *sampling_loc,                       \
+                            const T *attn_weight, const TA *grad_out, int N, int S, int M, int D, int L, int Lq, int P, int im2col_step,             \
+                            TA *grad_value, T *grad_sampling_loc, T *grad_attn_weight, const int64_t *shapes_host,                                   \
+                            const int64_t *level_start_host, msda_stream_t stream)                                                                   \
+    {                                                                                                                                                \
+        const LevelTables lt{spatial_shapes, level_start, shapes_host, level_start_host};                                                            \
+        return backward_impl<T, TV>(Options{}, kptr(value), lt, sampling_loc, attn_weight, kptr(grad_out), N, S, M, D, L, Lq, P, im2col_step,   \
+                                    kptr(grad_value), grad_sampling_loc, grad_attn_weight, stream);                                                  \
+    }                                                                                                                                                \
+    int msda_forward_prep_##SFX(const TA *value, const int64_t *spatial_shapes, const int64_t *level_start, const TA *offsets, int64_t off_stride,   \
+                                const TA *logits, int64_t log_stride, const T *ref, int ref_dim, int N, int S, int M, int D, int L, int Lq, int P,   \
+                                int im2col_step, TA *out, T *sampling_loc, T *attn_weight, const int64_t *shapes_host,                               \
+                                const int64_t *level_start_host, msda_stream_t stream)                                                               \
+    {                                                                                                                                                \
+        const LevelTables lt{spatial_shapes, level_start, shapes_host, level_start_host};                                                            \
+        return forward_prep_impl<T, TV, TV>(Options{}, kptr(value), lt, kptr(offsets), off_stride, kptr(logits), log_stride, ref, ref_dim, N,   \
+                                            S, M, D, L, Lq, P, im2col_step, kptr(out), sampling_loc, attn_weight, stream);                           \
+    }                                                                                                                                                \
+    int msda_prep_forward_##SFX(const TA *offsets, int64_t off_stride, const TA *logits, int64_t log_stride, const T *ref, int ref_dim,              \
+                                const int64_t *shapes_host, int N, int Lq, int M, int L, int P, T *loc, T *aw, msda_stream_t stream)                 \
+    {                                                                                                                                                \
+        return prep_forward_impl<T, TV>(kptr(offsets), off_stride, kptr(logits), log_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P, loc, aw,    \
+                                        stream);                                                                                                     \
+    }                                                                                                                                                \
+    int msda_prep_backward_##SFX(const T *grad_loc, const T *grad_aw, const T *aw, const TA *offsets, int64_t off_stride, const T *ref,              \
+                                 int ref_dim, const int64_t *shapes_host, int N, int Lq, int M, int L, int P, TA *grad_offsets,                      \
+                                 int64_t goff_stride, TA *grad_logits, int64_t glog_stride, T *grad_ref, msda_stream_t stream)                       \
+    {                                                                                                                                                \
+        return prep_backward_impl<T, TV>(grad_loc, grad_aw, aw, kptr(offsets), off_stride, ref, ref_dim, shapes_host, N, Lq, M, L, P,                \
+                                         kptr(grad_offsets), goff_stride, kptr(grad_logits), glog_stride, grad_ref, stream);                         \
     }
-MSDA_PREP_EXPORTS(f32, float)
-MSDA_PREP_EXPORTS(f64, double)
-#undef MSDA_PREP_EXPORTS
-
-int msda_prep_forward_bf16(const uint16_t *offsets, int64_t off_stride, const uint16_t *logits, int64_t log_stride, const float *ref,
-                           int ref_dim, const int64_t *shapes_host, int N, int Lq, int M, int L, int P, float *loc, float *aw,
-                           msda_stream_t stream)
-{
-    return prep_forward_impl<float, msda::bf16_t>(reinterpret_cast<const msda::bf16_t *>(offsets), off_stride,
-                                                  reinterpret_cast<const msda::bf16_t *>(logits), log_stride, ref, ref_dim, shapes_host, N,
-                                                  Lq, M, L, P, loc, aw, stream);
-}
-int msda_prep_backward_bf16(const float *grad_loc, const float *grad_aw, const float *aw, const uint16_t *offsets, int64_t off_stride,
-                            const float *ref, int ref_dim, const int64_t *shapes_host, int N, int Lq, int M, int L, int P,
-                            uint16_t *grad_offsets, int64_t goff_stride, uint16_t *grad_logits, int64_t glog_stride, float *grad_ref,
-                            msda_stream_t stream)
-{
-    return prep_backward_impl<float, msda::bf16_t>(grad_loc, grad_aw, aw, reinterpret_cast<const msda::bf16_t *>(offsets), off_stride, ref,
-                                                   ref_dim, shapes_host, N, Lq, M, L, P, reinterpret_cast<msda::bf16_t *>(grad_offsets),
-                                                   goff_stride, reinterpret_cast<msda::bf16_t *>(grad_logits), glog_stride, grad_ref, stream);
-}
+MSDA_EXPORTS(f32, float, float, float)
+MSDA_EXPORTS(f64, double, double, double)
+MSDA_EXPORTS(bf16, float, uint16_t, msda::bf16_t)
+#undef MSDA_EXPORTS
 
 }  // extern "C"
