@@ -13,12 +13,18 @@ box logits), so that ONE number covers a whole forward + backward of the path:
     6 decoder layers (+ box refinement) -> class / box / distillation heads -> frozen teacher -> ROIAlign -> attention pool ->
     matcher -> losses -> backward through all of it.
 
-bf16 activations wherever the library has a bf16 path (backbone, encoder, decoder), fp32 master parameters.  The optimizer step and
-the data pipeline are not part of it (and not part of this repository's scope).
+bf16 activations wherever the library has a bf16 path (backbone, encoder, decoder), fp32 master parameters.  The timed step of ``run``,
+``run_graphed``, ``run_graphed_device`` and ``run_ddp`` ends with gradient clipping and the AdamW step (reference engine.py:105-113); only
+``run``'s ``graph_replay`` diagnostic is forward + backward alone.  The data pipeline is not part of it (nor of this repository's scope).
+Layout: ``SECTIONS`` under one driver, one ``TrainLoop``, the command line through ``cli_kwargs``.
 """
+import contextlib
+import functools
+import inspect
 import math
 import sys
 import time
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -35,11 +41,15 @@ from richsem_amd.fed_loss import FedClassSampler, MaskedFocalNegativeSum, class_
 from richsem_amd.functions.linear import Lin256Function, VersionCache, pack_linear256
 from richsem_amd.matcher import (BoxPairLoss, CostPlan, FocalNegativeSum, FocalPositiveSum, HungarianMatcher, LateStatus,
                                  pairs_from_query_of_target)
+from richsem_amd.optim import ClipAdamW
+from richsem_amd.repack import RepackPlan
 from richsem_amd.modules import (MLP, refine_boxes, DeformableTransformerDecoderLayer, DeformableTransformerEncoderLayer, TransformerDecoder,
                                  clip_box_targets, get_reference_points, inverse_sigmoid)
 from richsem_amd.two_stage import ClassScorer
 
 NUM_CLASSES, NUM_QUERIES, DN_NUMBER, PROJ = 1204, 900, 100, 1024
+# the model part in order: section ``name`` is the method ``Step.<name>_section`` (four bare names are sub-modules, so state dict keys)
+SECTIONS = ("backbone", "input_proj", "encoder", "two_stage", "dn", "decoder", "heads")
 
 
 # ---- small helpers of the reference, restated (host-side torch ops) -----------------------------------------------------------------
@@ -136,7 +146,6 @@ class Step(nn.Module):
         self.teacher = ModifiedResNetTeacher(W.clip_rn50_state_dict(seed=seed + 2), heads=32)      # frozen: not a sub-module
         self.matcher = HungarianMatcher(cost_class=2.0, cost_bbox=5.0, cost_giou=2.0)
         self.scorer = ClassScorer(2)
-        self.times = {}
         self._eo_pack = VersionCache()
         self.timing = True
         self.stop_at = None       # (tools/capture_probe.py: end the step after this section with a surrogate loss)
@@ -190,15 +199,16 @@ class Step(nn.Module):
         return images.to(dev), mask.to(dev), targets
 
     def _mark(self, name):
-        if not self.timing:       # (timing events cannot be recorded while the stream is being captured)
-            return
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        self._events.append((name, ev))
+        if self.timing:       # (timing events cannot be recorded while the stream is being captured)
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            self._events.append((name, ev))
 
     def class_logits(self, hs):
-        """CLIPAlign.forward / forward_hs (richsem.py:182-205)"""
-        f = F.linear(hs, self.dino_visual_proj.weight.to(hs.dtype))
+        return self.text_logits(F.linear(hs, self.dino_visual_proj.weight.to(hs.dtype)))
+
+    def text_logits(self, f):
+        """scaled cosine of ``f`` against the frozen text side (CLIPAlign.forward / forward_hs, richsem.py:182-205)"""
         f = f / f.norm(dim=-1, keepdim=True)
         t = self.text_embed / self.text_embed.norm(dim=-1, keepdim=True)
         return (self.logit_scale.exp() * (f @ t.to(f.dtype).t())).float()
@@ -249,102 +259,98 @@ class Step(nn.Module):
             self.cost_plan = CostPlan(targets, dev, torch.float32)
         return st
 
-    def forward(self, images, mask, targets, indices=None, topk=None):
-        """``indices``: the matcher's assignment held fixed (graph capture, A/B tests); ``topk``: the two-stage selection held fixed"""
-        adt = self.act_dtype
-        self._events = []
-        self._mark("start")
-        N, dev = images.shape[0], images.device
-        st = geo = self.static
-        if self.device_geometry:      # the step's first device work: the geometry of the batch whose sizes ``self.sizes`` holds NOW
-            geo = self.last_geometry = batch_geometry(self.sizes, (self.H, self.Wpad), st["shapes"], out=self._geometry)
-        shapes, spatial, lsi, mask_flat, valid_ratios = st["shapes"], st["spatial"], st["lsi"], geo["mask_flat"], geo["valid_ratios"]
-        # ---- backbone + input projections (richsem.py:581-612) -------------------------------------------------------------------
-        feats = self.backbone(images)
-        self._mark("backbone")
-        if self.stop_at == "backbone":
-            return sum(f.float().sum() for f in feats)
-        srcs, got_shapes = self.input_proj(feats, out_dtype=adt)
-        assert got_shapes == shapes
-        src = torch.cat(srcs, 1)
-        pos_flat = (geo["pos_sine"] + st["level_onehot"] @ self.level_embed).to(adt)           # sine part + level embedding (:596-612)
-        self._mark("input_proj")
-        if self.stop_at == "input_proj":
-            return src.float().sum() + pos_flat.float().sum()
-        # ---- encoder (deformable_transformer.py:319) -------------------------------------------------------------------------------
-        ref = geo["ref"]
-        memory = src
+    # ---- the sections: ``s`` is the state of ONE call (run_sections makes it); each returns the terms of its surrogate loss ------------
+    def backbone_section(self, s):      # backbone (richsem.py:581-595)
+        s.feats = self.backbone(s.images)
+        return (s.feats,)
+
+    def input_proj_section(self, s):      # input projections, sine part + level embedding of the position (:596-612)
+        srcs, got_shapes = self.input_proj(s.feats, out_dtype=self.act_dtype)
+        assert got_shapes == s.st["shapes"]
+        s.src = torch.cat(srcs, 1)
+        s.pos_flat = (s.geo["pos_sine"] + s.st["level_onehot"] @ self.level_embed).to(self.act_dtype)
+        return s.src, s.pos_flat
+
+    def encoder_section(self, s):      # encoder (deformable_transformer.py:319)
+        s.memory = s.src
         for layer in self.encoder:
-            memory = layer(memory, pos_flat, ref, spatial, lsi, mask_flat)
-        self._mark("encoder")
-        if self.stop_at == "encoder":
-            return memory.float().sum()
-        # ---- two-stage query selection (:352-380) ----------------------------------------------------------------------------------
-        eo = self.enc_output
+            s.memory = layer(s.memory, s.pos_flat, s.geo["ref"], s.st["spatial"], s.st["lsi"], s.geo["mask_flat"])
+        return (s.memory,)
+
+    def two_stage_section(self, s):
+        """two-stage query selection (:352-380); ``s.topk``: the selection held fixed.  Its two outputs reach the loss past the decoder (the
+        decoder's reference points are detached), so they stay in every later surrogate: ``s.carried``"""
+        adt, geo, eo = self.act_dtype, s.geo, self.enc_output
         if adt == torch.bfloat16:
             pk = self._eo_pack.get((eo.weight, eo.bias), lambda: pack_linear256([eo.weight], [eo.bias]))
-            output_memory = Lin256Function.apply(memory.masked_fill(geo["zeroed"], 0.0), pk, None, False, eo.weight, eo.bias)   # bf16, lin256
+            output_memory = Lin256Function.apply(s.memory.masked_fill(geo["zeroed"], 0.0), pk, None, False, eo.weight, eo.bias)   # bf16, lin256
         else:
-            output_memory = eo(memory.masked_fill(geo["zeroed"], 0.0))
+            output_memory = eo(s.memory.masked_fill(geo["zeroed"], 0.0))
         output_memory = F.layer_norm(output_memory, (256,), self.enc_output_norm.weight.to(adt), self.enc_output_norm.bias.to(adt),
                                      self.enc_output_norm.eps)
-        if topk is None:
-            topk = self.scorer.topk_proposals(output_memory, NUM_QUERIES)                              # no logit tensor (two_stage.py)
-        self.last_topk = topk
+        if s.topk is None:
+            s.topk = self.scorer.topk_proposals(output_memory, NUM_QUERIES)                            # no logit tensor (two_stage.py)
+        self.last_topk = s.topk
         coord_unselected = self.enc_out_bbox_embed(output_memory).float() + geo["proposals"]
-        refpoint_undetach = torch.gather(coord_unselected, 1, topk[..., None].expand(-1, -1, 4))
-        tgt_undetach = torch.gather(output_memory, 1, topk[..., None].expand(-1, -1, 256)).float()
-        interm = {"pred_logits": self.class_logits(tgt_undetach), "pred_boxes": refpoint_undetach.sigmoid()}
-        self._mark("two_stage")
-        if self.stop_at == "two_stage":
-            return interm['pred_logits'].sum() + interm['pred_boxes'].sum()
-        # ---- denoising queries (dn_components.py:11-193): layout on the library's kernels, noise as torch ops -----------------------
-        known_num, lay = st["known_num"], st["lay"]
-        pad, groups = lay["pad_size"], lay["num_dn_group"]
+        s.refpoint_undetach = torch.gather(coord_unselected, 1, s.topk[..., None].expand(-1, -1, 4))
+        tgt_undetach = torch.gather(output_memory, 1, s.topk[..., None].expand(-1, -1, 256)).float()
+        s.carried = (self.class_logits(tgt_undetach), s.refpoint_undetach.sigmoid())      # the two-stage logits and boxes
+        return ()
+
+    def dn_section(self, s):      # denoising queries (dn_components.py:11-193): layout on the library's kernels, noise as torch ops
+        N, dev, lay = s.images.shape[0], s.images.device, s.st["lay"]
         if self.device_dn:      # (one launch: noise, embedding, block and mask)
-            q_label, q_bbox, tgt_mask = self._device_dn_queries(N, pad, dev)
+            q_label, q_bbox, s.tgt_mask = self._device_dn_queries(N, lay["pad_size"], dev)
         else:
-            (q_label, q_bbox), tgt_mask = self._torch_dn_queries(N, pad, groups, targets, dev), lay["attn_mask"]
-        tgt = torch.cat((q_label, self.tgt_embed.weight[None].expand(N, -1, -1)), 1)                   # embed_init_tgt
-        refpoints = torch.cat((q_bbox, refpoint_undetach.detach()), 1)
-        self._mark("dn")
-        if self.stop_at == "dn":
-            return tgt.sum() + refpoints.sum() + interm['pred_logits'].sum() + interm['pred_boxes'].sum()
-        # ---- decoder (:427) -----------------------------------------------------------------------------------------------------------
-        hs, refs = self.decoder(tgt=tgt.transpose(0, 1).to(adt), memory=memory.transpose(0, 1), tgt_mask=tgt_mask,
-                                memory_key_padding_mask=mask_flat, refpoints_unsigmoid=refpoints.transpose(0, 1), level_start_index=lsi,
-                                spatial_shapes=spatial, valid_ratios=valid_ratios)
-        self._mark("decoder")
-        if self.stop_at == "decoder":
-            return sum(h.float().sum() for h in hs) + sum(r.sum() for r in refs) + interm['pred_logits'].sum() + interm['pred_boxes'].sum()
-        # ---- heads (richsem.py:705-733) -------------------------------------------------------------------------------------------------
-        hs_stack = torch.stack(hs)                                                                     # (6, N, pad + 900, 256)
-        coords = torch.stack([refine_boxes(self.decoder.bbox_embed[l](hs[l]), refs[l]) for l in range(6)])      # richsem.py:705-715
-        logits = self.class_logits(hs_stack)                                                           # (6, N, 1092, 1204)
-        clip_hs = F.linear(hs[-1], self.proj_dino_hs.weight.to(hs[-1].dtype), self.proj_dino_hs.bias.to(hs[-1].dtype))
-        clip_hs = clip_hs / clip_hs.norm(dim=-1, keepdim=True)
-        tn = self.text_embed / self.text_embed.norm(dim=-1, keepdim=True)
-        clip_logits = (self.logit_scale.exp() * (clip_hs @ tn.to(clip_hs.dtype).t())).float()          # (N, 1092, 1204)
-        self._mark("heads")
-        if self.stop_at == "heads":
-            return coords.sum() + logits.sum() + clip_logits.sum() + interm['pred_logits'].sum() + interm['pred_boxes'].sum()
-        # ---- frozen teacher -> ROIAlign -> attention pool -> text logits (richsem.py:614-629, :741-768) ----------------------------------
-        if self._model_only == "student":      # (model_part without the frozen teacher: run_graphed launches it beside the host's matching)
-            return logits, coords, interm["pred_logits"], interm["pred_boxes"], clip_logits
-        t_logits = self.teacher_part(images, targets)
-        self._mark("teacher")
-        if self._model_only:      # (model_part: the step up to the matcher, as tensors)
-            return logits, coords, interm["pred_logits"], interm["pred_boxes"], clip_logits, t_logits
+            (q_label, q_bbox), s.tgt_mask = self._torch_dn_queries(N, lay["pad_size"], lay["num_dn_group"], s.targets, dev), lay["attn_mask"]
+        s.tgt = torch.cat((q_label, self.tgt_embed.weight[None].expand(N, -1, -1)), 1)                 # embed_init_tgt
+        s.refpoints = torch.cat((q_bbox, s.refpoint_undetach.detach()), 1)
+        return s.tgt, s.refpoints
+
+    def decoder_section(self, s):      # decoder (:427)
+        s.hs, s.refs = self.decoder(tgt=s.tgt.transpose(0, 1).to(self.act_dtype), memory=s.memory.transpose(0, 1), tgt_mask=s.tgt_mask,
+                                    memory_key_padding_mask=s.geo["mask_flat"], refpoints_unsigmoid=s.refpoints.transpose(0, 1),
+                                    level_start_index=s.st["lsi"], spatial_shapes=s.st["spatial"], valid_ratios=s.geo["valid_ratios"])
+        return s.hs, s.refs
+
+    def heads_section(self, s):      # heads (richsem.py:705-733)
+        hs, refs = s.hs, s.refs
+        s.coords = torch.stack([refine_boxes(self.decoder.bbox_embed[l](hs[l]), refs[l]) for l in range(6)])      # richsem.py:705-715
+        s.logits = self.class_logits(torch.stack(hs))                                 # (6, N, pad + 900, 256) -> (6, N, 1092, 1204)
+        s.clip_logits = self.text_logits(F.linear(hs[-1], self.proj_dino_hs.weight.to(hs[-1].dtype), self.proj_dino_hs.bias.to(hs[-1].dtype)))
+        return s.coords, s.logits, s.clip_logits      # (the last: (N, 1092, 1204))
+
+    def run_sections(self, images, targets, topk=None):
+        """the one driver: every section of ``SECTIONS`` on a fresh state, a timing mark after each -> (state, None); or, where ``stop_at``
+        names a section, (state, its surrogate loss) with the later sections not run.  The surrogate sums the section's terms and the
+        carried ones -- a list among them summed on its own first --, so its backward reaches all the work up to there"""
+        self._events = []
+        self._mark("start")
+        s = SimpleNamespace(images=images, targets=targets, topk=topk, st=self.static, geo=self.static, carried=())
+        if self.device_geometry:      # the step's first device work: the geometry of the batch whose sizes ``self.sizes`` holds NOW
+            s.geo = self.last_geometry = batch_geometry(self.sizes, (self.H, self.Wpad), s.st["shapes"], out=self._geometry)
+        for name in SECTIONS:
+            terms = getattr(self, name + "_section")(s)
+            self._mark(name)
+            if self.stop_at == name:
+                sums = [sum(x.float().sum() for x in t) if isinstance(t, (list, tuple)) else t.float().sum() for t in (*terms, *s.carried)]
+                return s, sum(sums[1:], sums[0])
+        return s, None
+
+    def forward(self, images, mask, targets, indices=None, topk=None):
+        """``model_part``, matcher, ``loss_part`` -> the loss (with ``stop_at``: the section's surrogate).  ``indices``: the matcher's
+        assignment held fixed (graph capture, A/B tests); ``topk``: the two-stage selection held fixed"""
+        out = self.model_part(images, mask, targets, topk=topk)
+        if torch.is_tensor(out):
+            return out
         # ---- matcher (matcher.py:30-78, one host copy for the 7 outputs) -------------------------------------------------------------------
-        if indices is None and self.device_matcher:
-            indices = self.match_device(logits, coords, interm["pred_logits"], interm["pred_boxes"], targets)
-        elif indices is None:
-            indices = self.match(logits, coords, interm["pred_logits"], interm["pred_boxes"], targets)
+        if indices is None:
+            indices = (self.match_device if self.device_matcher else self.match)(*out[:4], targets)
         packed = indices if (isinstance(indices, tuple) and torch.is_tensor(indices[0])) else self.pack_indices(indices, targets)
         if packed is not indices:
             self.last_indices = indices
         self._mark("matcher")
-        loss = self.loss_part(logits, coords, interm["pred_logits"], interm["pred_boxes"], clip_logits, t_logits, *packed)
+        loss = self.loss_part(*out, *packed)
         self._mark("criterion")
         return loss
 
@@ -383,7 +389,6 @@ class Step(nn.Module):
         self.last_dn = {"noised_label": noised_label, "noised_box": d["out"]["noised_box"], "meta": meta}
         return q_label, q_bbox, tgt_mask
 
-    _model_only = False
     frozen_noise = None
     frozen_fed = None
 
@@ -420,15 +425,23 @@ class Step(nn.Module):
         g = torch.Generator(device=dev).manual_seed(seed)
         self.frozen_fed, _ = self.fed_sampler.sample(labels, self.fed_groups(), generator=g)
 
-    def model_part(self, images, mask=None, targets=None, teacher=True):
-        """the step up to the matcher: -> (logits (6, N, Q, C), boxes (6, N, Q, 4), two-stage logits, two-stage boxes, distillation logits,
-        the teacher's box logits -- unless ``teacher`` is False): tensors in, tensors out, nothing read back to the host -- the part
-        ``run_graphed`` captures"""
-        self._model_only = True if teacher else "student"
-        try:
-            return self.forward(images, mask, self._targets if targets is None else targets)
-        finally:
-            self._model_only = False
+    def model_part(self, images, mask=None, targets=None, teacher=True, topk=None):
+        """the step up to the matcher: -> (logits (6, N, Q, C), boxes (6, N, Q, 4), two-stage logits (N, 900, C), two-stage boxes
+        (N, 900, 4), distillation logits (N, Q, C), the teacher's box logits (targets, C) -- unless ``teacher`` is False: ``run_graphed``
+        launches the frozen teacher beside the host's matching): tensors in, tensors out, nothing read back to the host -- the part
+        ``run_graphed`` captures.  ``topk``: the two-stage selection held fixed; ``mask`` is not read (``prepare`` was); with ``stop_at`` the
+        section's surrogate loss, a scalar, instead"""
+        targets = self._targets if targets is None else targets
+        s, surrogate = self.run_sections(images, targets, topk)
+        if surrogate is not None:
+            return surrogate
+        out = (s.logits, s.coords, *s.carried, s.clip_logits)
+        if not teacher:
+            return out
+        # ---- frozen teacher -> ROIAlign -> attention pool -> text logits (richsem.py:614-629, :741-768) ----------------------------------
+        t_logits = self.teacher_part(images, targets)
+        self._mark("teacher")
+        return out + (t_logits,)
 
     @torch.no_grad()
     def teacher_part(self, images, targets=None):
@@ -583,31 +596,26 @@ def synthetic_image_counts(C, seed=1203):
 
 
 CLIP_MAX_NORM = 0.1      # reference config/RichSem/baseline_4scale.py:19 (clip_max_norm), engine.py:110-112
-
-
 LR = 1e-4
 
 
-def make_optimizer(params, lr=LR, library=False):
-    """AdamW as the reference builds it (main.py:213-214; lr / weight_decay of config/RichSem/baseline_4scale.py:7,14), one fused launch per
+def make_optimizer(params, lr=LR, library=False, fused=True):
+    """AdamW as the reference builds it (main.py:213-214; lr / weight decay of config/RichSem/baseline_4scale.py:7,14), one fused launch per
     step (fused optimizers do not bump the parameters' version counters; richsem_amd/param_cache.py's step hook does, so the bf16 layers'
     packed weights follow every step).  ``library``: richsem_amd.optim.ClipAdamW instead -- gradient clipping and AdamW in two launches of
-    the library's own (opt-in: ``--library-optimizer``)"""
+    the library's own (opt-in: ``--library-optimizer``).  ``fused=False``: torch's own choice of implementation (run_ddp on CPU tensors)"""
+    kw = dict(lr=lr, weight_decay=1e-4)
     if library:
-        from richsem_amd.optim import ClipAdamW
-        return ClipAdamW(params, lr=lr, weight_decay=1e-4, max_norm=CLIP_MAX_NORM)
-    return torch.optim.AdamW(params, lr=lr, weight_decay=1e-4, fused=True)
+        return ClipAdamW(params, max_norm=CLIP_MAX_NORM, **kw)
+    return torch.optim.AdamW(params, fused=fused or None, **kw)
 
 
 def optimizer_step(opt, params):
     """what follows ``losses.backward()`` in the reference's training loop (engine.py:109-113): gradient clipping to clip_max_norm, AdamW step.
     No host synchronisation: the norm stays on the device (``error_if_nonfinite`` is off as in the reference's call).  The library's optimizer
     clips inside its own step."""
-    from richsem_amd.optim import ClipAdamW
-    if isinstance(opt, ClipAdamW):      # make_optimizer(library=True)
-        opt.step()
-        return
-    torch.nn.utils.clip_grad_norm_(params, CLIP_MAX_NORM, foreach=True)
+    if not isinstance(opt, ClipAdamW):      # (make_optimizer(library=True) clips inside its step)
+        torch.nn.utils.clip_grad_norm_(params, CLIP_MAX_NORM, foreach=True)
     opt.step()
 
 
@@ -617,21 +625,16 @@ class GroupedRepack:
     step (``after_step``).  The captured forms of the step then hold no pack launch; ``plan`` is None when the switch is off."""
 
     def __init__(self, on):
-        self.plan = None
-        if on:
-            from richsem_amd.repack import RepackPlan
-            self.plan = RepackPlan()
+        self.plan = RepackPlan() if on else None
         self._recorded = self._attached = False
 
     def recording(self):
-        import contextlib
         if self.plan is None or self._recorded:
             return contextlib.nullcontext()
         self._recorded = True
         return self.plan.record()
 
     def attach(self, opt):
-        from richsem_amd.optim import ClipAdamW
         if self.plan is not None and isinstance(opt, ClipAdamW):
             opt.attach_repack(self.plan)
             self._attached = True
@@ -641,40 +644,76 @@ class GroupedRepack:
             self.plan.refresh()
 
 
-def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, library=False,
-        grouped_repack=False, **step_kwargs):
-    """time `steps` composed steps (forward + loss + backward); returns the dict bench.py attaches as ``full_step`` (tests: ``lr``,
-    ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model", its plan under "repack" --, ``step_kwargs``: a
-    smaller Step; ``library``: make_optimizer's switch, ``grouped_repack``: :class:`GroupedRepack`'s, both passed on to run_graphed)"""
+class TrainLoop:
+    """The one training loop (reference engine.py:100-113) of ``run``, ``run_graphed`` and ``run_graphed_device``: clear the gradients, run
+    the body, backward -- :meth:`forward_backward` --, then gradient clipping + optimizer step + the re-pack -- :meth:`update`; :meth:`step`
+    is both.  ``opt`` is None where ``optimizer`` is False: ``update`` then does nothing.  (``run_ddp`` keeps a loop of its own: see there.)"""
+
+    def __init__(self, model, repack, lr=LR, library=False, optimizer=True):
+        self.params = [p for p in model.parameters() if p.requires_grad]
+        self.opt = make_optimizer(self.params, lr, library) if optimizer else None
+        self.repack = repack
+        repack.attach(self.opt)
+
+    def forward_backward(self, body, fwd=None):      # ``fwd``: an event recorded between the two (``run`` times the backward from it)
+        for p in self.params:
+            p.grad = None
+        loss = body()
+        if fwd is not None:
+            fwd.record()
+        loss.backward()
+        return loss
+
+    def update(self):
+        if self.opt is not None:
+            optimizer_step(self.opt, self.params)
+            self.repack.after_step()
+
+    def step(self, body):
+        loss = self.forward_backward(body)
+        self.update()
+        return loss
+
+
+def _setup(n_img, dev, noise_seed, fed_seed, timing, **step_kwargs):
+    """-> (model, images, mask, targets): a Step prepared for its batch, noise and federated draws frozen where a seed is given; ``timing``:
+    whether its forward records section events (they cannot be recorded while a stream is captured)"""
     model = Step(n_img=n_img, dev=dev, **step_kwargs)
-    model.stop_at = stop_at      # (profiling aid: the step cut off after a section, see tools/step_sections.sh)
+    model.timing = timing
     images, mask, targets = model.batch()
     model.prepare(mask, targets)
+    model._mask = mask
     if noise_seed is not None:
         model.freeze_noise(noise_seed)
-    params = [p for p in model.parameters() if p.requires_grad]
-    opt = make_optimizer(params, lr, library)
+    if fed_seed is not None:
+        model.freeze_fed(fed_seed)
+    return model, images, mask, targets
+
+
+def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_seed=None, return_model=False, library=False,
+        grouped_repack=False, **step_kwargs):
+    """time `steps` composed steps (forward + loss + backward + optimizer step); returns the dict bench.py attaches as ``full_step``
+    (tests: ``lr``, ``noise_seed`` (Step.freeze_noise), ``return_model`` -- the trained Step under "model", its plan under "repack" --,
+    ``step_kwargs``: Step's keywords, a smaller Step for instance; ``library``: make_optimizer's switch, ``grouped_repack``:
+    :class:`GroupedRepack`'s; all three passed on whole to run_graphed, so ``graphed_sections`` times the same Step)"""
+    model, images, mask, targets = _setup(n_img, dev, noise_seed, None, True, **step_kwargs)
+    model.stop_at = stop_at      # (profiling aid: the step cut off after a section, see tools/step_sections.sh)
     repack = GroupedRepack(grouped_repack)
-    repack.attach(opt)
+    loop = TrainLoop(model, repack, lr, library)
 
     def step(indices=None, optimize=True):
-        for p in params:
-            p.grad = None
+        # what only this harness does: it records the event between forward and backward, and its captured form leaves the optimizer out
+        fwd = torch.cuda.Event(enable_timing=True) if model.timing else None
         with repack.recording():      # (the first step only, and only with grouped_repack)
-            loss = model(images, mask, targets, indices)
-            fwd = None
-            if model.timing:
-                fwd = torch.cuda.Event(enable_timing=True)
-                fwd.record()
-            loss.backward()
+            loss = loop.forward_backward(lambda: model(images, mask, targets, indices), fwd)
         if optimize:
-            optimizer_step(opt, params)
-            repack.after_step()
+            loop.update()
         return loss, fwd
 
     rows, totals, bwds = {}, [], []
     with capture_stream() as side:      # warm-up, the timed eager steps and the captures below: ONE stream
-        pinned = pin_grad_accumulators(params)      # noqa: F841  (kept alive to the end of run(): every graph below reuses these nodes)
+        # the trained parameters are handed over here, all parameters in the graphed forms: pin_grad_accumulators skips the frozen ones
+        pinned = pin_grad_accumulators(loop.params)      # noqa: F841  (kept alive to the end of run(): every graph below reuses these nodes)
         for _ in range(warmup):
             step()
         torch.cuda.synchronize()
@@ -698,8 +737,7 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
            "forward_rows_ms": {k: round(sum(v) / len(v), 3) for k, v in rows.items()},
            "backward_ms": round(sum(bwds) / len(bwds), 2)}
     if return_model:
-        out["model"] = model
-        out["repack"] = repack.plan
+        out.update(model=model, repack=repack.plan)
     if not graph:
         return out
     # the device part as a captured graph: the assignment of the last eager step held fixed (the matcher's host round trip cannot be captured)
@@ -715,13 +753,12 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
                 step(indices, optimize=False)
         torch.cuda.synchronize()
         g = capture(lambda: step(indices, optimize=False), side)[0]      # the stream that was warmed up; the step's result dropped
-        g.replay()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(steps):
-            g.replay()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / steps * 1e3
+        return _time_steps(g.replay, steps, 1)[0]
+
+    def failed(e):      # a capture failure must not take the bench line down
+        import traceback
+        traceback.print_exc(file=sys.stderr)
+        return f"{type(e).__name__}: {str(e)[:300]}"
 
     try:
         rep = replay_ms(None)
@@ -732,73 +769,35 @@ def run(n_img, dev, steps=5, warmup=2, graph=True, stop_at=None, lr=LR, noise_se
         # GPU time per row, forward + backward: replay time of the step cut off after each section (a surrogate loss = the sum of the
         # section's outputs), differenced; "criterion" = the rest (teacher + matcher-less losses and their backward into the heads)
         prev, table = 0.0, {}
-        for name in ("backbone", "input_proj", "encoder", "two_stage", "dn", "decoder", "heads"):
+        for name in SECTIONS:
             t = replay_ms(name)
             table[name] = round(t - prev, 2)
             prev = t
         table["teacher+criterion"] = round(rep - prev, 2)
         out["graph_replay"]["rows_fwd_bwd_ms"] = table
-    except Exception as e:      # a capture failure must not take the bench line down
-        import traceback
-        traceback.print_exc(file=sys.stderr)
-        out.setdefault("graph_replay", {})["error"] = f"{type(e).__name__}: {str(e)[:300]}"
+    except Exception as e:      # noqa: BLE001
+        out.setdefault("graph_replay", {})["error"] = failed(e)
     finally:
         model.stop_at = None
     try:
         del model
         torch.cuda.empty_cache()
-        fed = {k: v for k, v in step_kwargs.items() if k in ("fed_loss", "fed_num_sample_cats", "class_image_counts", "boxes_per_image", "device_distill", "device_geometry", "device_dn")}
-        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, library=library, grouped_repack=grouped_repack, **fed)
+        out["graphed_sections"] = run_graphed(n_img, dev, steps=steps, warmup=warmup, library=library, grouped_repack=grouped_repack, **step_kwargs)
     except Exception as e:      # noqa: BLE001
-        import traceback
-        traceback.print_exc(file=sys.stderr)
-        out["graphed_sections"] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
+        out["graphed_sections"] = {"error": failed(e)}
     return out
 
 
-class _ModelPart(nn.Module):
-    """the step up to the matcher as a module of tensors (what torch.cuda.make_graphed_callables captures, forward and backward)"""
+class _Part(nn.Module):
+    """``fn``, a function of tensors, as a module (what torch.cuda.make_graphed_callables captures, forward and backward) over the
+    parameters of ``step`` -- None for the criterion, which has none of its own"""
 
-    def __init__(self, step):
+    def __init__(self, step, fn):
         super().__init__()
-        self.step = step
-
-    def forward(self, images):
-        return self.step.model_part(images, self.step._mask, teacher=False)
-
-
-class _WholeStep(nn.Module):
-    """the whole step -- model, cost blocks, on-device assignment, teacher, criterion -- as one module of tensors (Step(device_matcher=True))"""
-
-    def __init__(self, step):
-        super().__init__()
-        self.step = step
-
-    def forward(self, images):
-        return self.step(images, self.step._mask, self.step._targets)
-
-
-class _LossPart(nn.Module):
-    def __init__(self, step):
-        super().__init__()
-        self.step = [step]      # (not a sub-module: the criterion has no parameters of its own)
+        self.step, self.fn = step, fn
 
     def forward(self, *tensors):
-        return self.step[0].loss_part(*tensors)
-
-
-def _graphed_setup(n_img, dev, noise_seed, fed_seed, **step_kwargs):
-    """-> (model, images, mask, targets): an untimed Step prepared for its batch, noise and federated draws frozen where a seed is given"""
-    model = Step(n_img=n_img, dev=dev, **step_kwargs)
-    model.timing = False
-    images, mask, targets = model.batch()
-    model.prepare(mask, targets)
-    model._mask = mask
-    if noise_seed is not None:
-        model.freeze_noise(noise_seed)
-    if fed_seed is not None:
-        model.freeze_fed(fed_seed)
-    return model, images, mask, targets
+        return self.fn(*tensors)
 
 
 def _time_steps(step, steps, warmup):
@@ -813,15 +812,16 @@ def _time_steps(step, steps, warmup):
     return (time.perf_counter() - t0) / steps * 1e3, loss
 
 
-def _graphed_result(what, n_img, ms, loss, model, params, optimizer, grads_extra=None, model_extra=None, library=False):
-    """the dict of run_graphed / run_graphed_device; ``grads_extra`` / ``model_extra``: None, or the keys that go with "grads" / "model\""""
+def _graphed_result(what, n_img, ms, loss, params, optimizer, library):
+    """the keys every call of run_graphed / run_graphed_device returns; the caller adds what ``return_grads`` / ``return_model`` ask for"""
     return {"what": what, "optimizer": ("ClipAdamW(max_norm=0.1): clipping + AdamW in two library launches" if library else
                                         "AdamW(fused) + clip_grad_norm_(0.1)") if optimizer else None,
             "ms": round(ms, 2), "img_per_s": round(n_img / (ms * 1e-3), 2), "loss": float(loss.detach()),
-            "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None))),
-            **({"grads": {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None},
-                **grads_extra, "topk": model.last_topk.clone()} if grads_extra is not None else {}),
-            **({"model": model, **model_extra} if model_extra is not None else {})}
+            "grad_norm": float(torch.sqrt(sum((p.grad.float() ** 2).sum() for p in params if p.grad is not None)))}
+
+
+def _grads(model):
+    return {n: p.grad.detach().float().clone() for n, p in model.named_parameters() if p.grad is not None}
 
 
 def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False, fed_seed=None,
@@ -839,8 +839,8 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
     if device_matcher:
         return run_graphed_device(n_img, dev, steps=steps, warmup=warmup, optimizer=optimizer, noise_seed=noise_seed, return_grads=return_grads, lr=lr,
                                   return_model=return_model, fed_seed=fed_seed, library=library, grouped_repack=grouped_repack, **step_kwargs)
-    model, images, mask, targets = _graphed_setup(n_img, dev, noise_seed, fed_seed, **step_kwargs)
-    part_a, part_b = _ModelPart(model), _LossPart(model)
+    model, images, mask, targets = _setup(n_img, dev, noise_seed, fed_seed, False, **step_kwargs)
+    part_a, part_b = _Part(model, lambda x: model.model_part(x, mask, teacher=False)), _Part(None, model.loss_part)
     repack = GroupedRepack(grouped_repack)
     with capture_stream() as side:      # the eager warm-up, the captures and the training steps (richsem_amd/capture.py)
         pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (before anything touches a parameter; alive to the end)
@@ -861,36 +861,31 @@ def run_graphed(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, 
             model.teacher_part(images)
         torch.cuda.synchronize()
         teacher_graph, t_static = capture(lambda: model.teacher_part(images), side)
-        params = [p for p in model.parameters() if p.requires_grad]
-        opt = make_optimizer(params, lr, library) if optimizer else None
-        repack.attach(opt)
+        loop = TrainLoop(model, repack, lr, library, optimizer)
         last = {}
 
-        def step():
-            for p in params:
-                p.grad = None
+        def body():
             outs = ga(images)
             with torch.no_grad():
                 pending = model.match_begin(*outs[:4], targets)           # device cost blocks -> one host copy, enqueued
                 teacher_graph.replay()
                 assign = model.match_end(pending)                         # wait for the copy, scipy (matcher.py) -- under the teacher
             last["assign"] = assign
-            loss = gb(*outs, t_static, *model.pack_indices(assign, targets))
-            loss.backward()
-            if opt is not None:
-                optimizer_step(opt, params)
-                repack.after_step()
-            return loss
+            return gb(*outs, t_static, *model.pack_indices(assign, targets))
 
+        step = functools.partial(loop.step, body)
         ms, loss = _time_steps(step, steps, warmup)
-    return _graphed_result(
+    out = _graphed_result(
         "the same step with its two device-only parts (model up to the matcher; criterion) captured forward + backward by "
         "torch.cuda.make_graphed_callables and the Hungarian assignment live on the host between them every step, under the frozen "
         "teacher's forward (a HIP graph of its own, replayed while the host waits for the cost blocks and solves the assignments)"
         + ("; then gradient clipping (0.1) + fused AdamW step (reference engine.py:105-113): a TRAINING step, the same thing "
-           "full_step_ddp measures at N > 1" if optimizer else "; no optimizer step"),
-        n_img, ms, loss, model, params, optimizer, {"indices": last["assign"]} if return_grads else None,
-        {"ga": ga, "images": images, "step": lambda: _on_stream(side, step), "repack": repack.plan} if return_model else None, library=library)
+           "full_step_ddp measures at N > 1" if optimizer else "; no optimizer step"), n_img, ms, loss, loop.params, optimizer, library)
+    if return_grads:
+        out.update(grads=_grads(model), indices=last["assign"], topk=model.last_topk.clone())
+    if return_model:
+        out.update(model=model, ga=ga, images=images, step=lambda: _on_stream(side, step), repack=repack.plan)
+    return out
 
 
 def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed=None, return_grads=False, lr=LR, return_model=False,
@@ -900,8 +895,8 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
     gradient clipping + fused AdamW.  The assignment is live: every replay solves it for that replay's model outputs.  The solver's status
     is copied to pinned memory after the replay and read one step late (a non-zero entry raises ValueError then).  Returns what
     :func:`run_graphed` returns; with ``return_model`` also "query_of_target" / "status": the static tensors every replay rewrites."""
-    model, images, _, _ = _graphed_setup(n_img, dev, noise_seed, fed_seed, device_matcher=True, **step_kwargs)
-    whole = _WholeStep(model)
+    model, images, _, _ = _setup(n_img, dev, noise_seed, fed_seed, False, device_matcher=True, **step_kwargs)
+    whole = _Part(model, lambda x: model(x, model._mask, model._targets))      # model, cost blocks, assignment, teacher, criterion
     repack = GroupedRepack(grouped_repack)
     with capture_stream() as side:
         pinned = pin_grad_accumulators(model.parameters())      # noqa: F841  (alive to the end)
@@ -914,31 +909,28 @@ def run_graphed_device(n_img, dev, steps=5, warmup=2, optimizer=True, noise_seed
         gw = graphed_callables(whole, (images,), allow_unused_input=True)
         torch.cuda.synchronize()
         model.late_status.flush()      # (the warm-up iterations ran eagerly and pushed theirs)
-        params = [p for p in model.parameters() if p.requires_grad]
-        opt = make_optimizer(params, lr, library) if optimizer else None
-        repack.attach(opt)
+        loop = TrainLoop(model, repack, lr, library, optimizer)
 
         def step(batch_images=images):
-            for p in params:
-                p.grad = None
-            loss = gw(batch_images)
-            loss.backward()
-            model.late_status.push(model.last_status)      # (raises for the PREVIOUS step's status)
-            if opt is not None:
-                optimizer_step(opt, params)
-                repack.after_step()
+            loss = loop.forward_backward(lambda: gw(batch_images))
+            # what only this harness does: the solver's status goes to the host between backward and optimizer (raises for the PREVIOUS step's)
+            model.late_status.push(model.last_status)
+            loop.update()
             return loss
 
         ms, loss = _time_steps(step, steps, warmup)
         model.late_status.flush()
-    return _graphed_result(
+    out = _graphed_result(
         "the same training step with the Hungarian assignment solved on the device (msda_lsap_*): model, cost blocks, assignment, "
         "frozen teacher and criterion captured forward + backward as ONE graphed callable, no host wait between the step's first "
         "and last kernel; the solver's status is read one step late"
-        + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"),
-        n_img, ms, loss, model, params, optimizer, {} if return_grads else None,
-        {"ga": gw, "images": images, "step": lambda *a: _on_stream(side, lambda: step(*a)),
-         "query_of_target": model.last_qot, "status": model.last_status, "repack": repack.plan} if return_model else None, library=library)
+        + ("; then gradient clipping (0.1) + fused AdamW step" if optimizer else "; no optimizer step"), n_img, ms, loss, loop.params, optimizer, library)
+    if return_grads:
+        out.update(grads=_grads(model), topk=model.last_topk.clone())
+    if return_model:
+        out.update(model=model, ga=gw, images=images, step=lambda *a: _on_stream(side, lambda: step(*a)),
+                   query_of_target=model.last_qot, status=model.last_status, repack=repack.plan)
+    return out
 
 
 def _on_stream(stream, fn):
@@ -958,25 +950,23 @@ def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None
     ``no_sync()``: no all-reduce) and the job's images per second.  ``make_model``: a stand-in module factory (tests/test_dist_gloo.py
     runs the protocol on CPU with gloo; the module needs ``batch()`` -> forward arguments and optionally ``prepare(*batch()[1:])``;
     ``return_model``: the trained module under "model")."""
-    import contextlib
     from torch.nn.parallel import DistributedDataParallel as DDP
-    world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
+    live = dist is not None and dist.is_initialized()
+    world = dist.get_world_size() if live else 1
     model = make_model() if make_model is not None else Step(n_img=n_img, seed=0, dev=dev)      # (same weights on every rank; DDP broadcasts anyway)
     if hasattr(model, "timing"):
         model.timing = False
-    rank = dist.get_rank() if world > 1 or (dist is not None and dist.is_initialized()) else 0
-    batch = model.batch(seed=rank) if make_model is None else model.batch()
+    batch = model.batch(seed=dist.get_rank() if live else 0) if make_model is None else model.batch()
     if make_model is None:
         model.prepare(batch[1], batch[2])
     is_cuda = torch.device(dev).type == "cuda"
-    if dist is not None and dist.is_initialized():
-        ddp = DDP(model, device_ids=[torch.device(dev).index] if is_cuda else None, gradient_as_bucket_view=True, broadcast_buffers=False)
-    else:
-        ddp = model
+    ddp = DDP(model, device_ids=[torch.device(dev).index] if is_cuda else None, gradient_as_bucket_view=True,
+              broadcast_buffers=False) if live else model
     params = [p for p in model.parameters() if p.requires_grad]
-    opt = (torch.optim.AdamW(params, lr=lr, weight_decay=1e-4, fused=True) if is_cuda else
-           torch.optim.AdamW(params, lr=lr, weight_decay=1e-4)) if optimizer else None      # main.py:213-214
+    opt = make_optimizer(params, lr, fused=is_cuda) if optimizer else None
 
+    # Not TrainLoop: this loop clears through the optimizer (zero_grad(set_to_none=True)), runs forward + backward under DDP's no_sync()
+    # for the second timing, and clips with clip_grad_norm_'s default ``foreach`` (tests/test_dist_gloo.py runs it on CPU tensors)
     def step(sync=True):
         if opt is not None:
             opt.zero_grad(set_to_none=True)
@@ -993,7 +983,7 @@ def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None
         return loss
 
     def fence():
-        if dist is not None and dist.is_initialized():
+        if live:
             dist.barrier()
         if is_cuda:
             torch.cuda.synchronize()
@@ -1007,7 +997,7 @@ def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None
             loss = step(sync)
         fence()
         el = time.perf_counter() - t0
-        if dist is not None and dist.is_initialized() and world > 1:
+        if live and world > 1:
             t = torch.tensor([el], dtype=torch.float64, device=backend_device or (dev if is_cuda else "cpu"))
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
@@ -1025,53 +1015,62 @@ def run_ddp(n_img, dev, dist, steps=5, warmup=2, optimizer=True, make_model=None
             **({"model": model} if return_model else {})}
 
 
-if __name__ == "__main__":
+# ---- the command line: one table of (flag, keyword, help); cli_kwargs turns the parsed flags into keywords ----------------------------------
+SWITCHES = (
+    ("--fed-loss", "fed_loss", "the criterion's federated loss (use_fed_loss, 50 classes per draw; synthetic class weights: Step.loss_part)"),
+    ("--device-distill", "device_distill", "the criterion's KL distillation term as one row kernel (distill.DistillKL) instead of the PyTorch "
+     "composition: Step.loss_part"),
+    ("--device-dn", "device_dn", "the denoising queries (label / box noise, label embedding, padded query block, mask) from one kernel that reads "
+     "the target counts on the device (richsem_amd/dn.py) instead of torch ops on the host's layout: Step.dn_section"),
+    ("--device-geometry", "device_geometry", "the batch's geometry tensors (masks, valid ratios, reference points, sine position, anchors) from "
+     "one kernel inside the step (richsem_amd/geometry.py) instead of torch ops in prepare(): Step.run_sections"),
+    ("--library-optimizer", "library", "richsem_amd.optim.ClipAdamW (gradient clipping + AdamW in two launches of the library's own) instead "
+     "of clip_grad_norm_ + torch's fused AdamW"),
+    ("--grouped-repack", "grouped_repack", "every derived form of the parameters (bf16 casts, packed weights) refreshed from the masters in ONE "
+     "launch after the optimizer step (richsem_amd/repack.py) instead of rebuilt by every cache inside the captured graphs"),
+)
+
+
+def parse_args(argv=None):
     import argparse
-    import json
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--images", type=int, default=2)
+    for name, default in (("--steps", 5), ("--warmup", 2), ("--images", 2)):
+        ap.add_argument(name, type=int, default=default)
     ap.add_argument("--no-graph", action="store_true", help="eager steps only (the form profiled for profiles/*_step_kernels.md)")
-    ap.add_argument("--stop-at", default=None, help="profiling aid: cut the step off after this section (implies --no-graph)")
-    ap.add_argument("--fed-loss", action="store_true", help="the criterion's federated loss (use_fed_loss, 50 classes per draw; synthetic class "
-                                                           "weights: Step.loss_part)")
+    ap.add_argument("--stop-at", default=None, help="profiling aid: cut the step off after this section (implies --no-graph): " + ", ".join(SECTIONS))
     ap.add_argument("--boxes-per-image", type=int, default=12, help="targets per synthetic image (default 12)")
-    ap.add_argument("--device-distill", action="store_true", help="the criterion's KL distillation term as one row kernel (distill.DistillKL) "
-                                                                   "instead of the PyTorch composition: Step.loss_part")
-    ap.add_argument("--device-dn", action="store_true", help="the denoising queries (label / box noise, label embedding, padded query block, mask) from "
-                                                              "one kernel that reads the target counts on the device (richsem_amd/dn.py) instead "
-                                                              "of torch ops on the host's layout: Step.forward")
-    ap.add_argument("--device-geometry", action="store_true", help="the batch's geometry tensors (masks, valid ratios, reference points, sine position, "
-                                                                    "anchors) from one kernel inside the step (richsem_amd/geometry.py) instead of "
-                                                                    "torch ops in prepare(): Step.forward")
-    ap.add_argument("--device-matcher", action="store_true", help="time the graphed training step in both forms: the Hungarian assignment on the "
-                                                                  "host between two captured parts (twice, to show its spread) and on the device "
-                                                                  "inside one captured step")
-    ap.add_argument("--library-optimizer", action="store_true", help="richsem_amd.optim.ClipAdamW (gradient clipping + AdamW in two launches of the "
-                                                                      "library's own) instead of clip_grad_norm_ + torch's fused AdamW")
-    ap.add_argument("--grouped-repack", action="store_true", help="every derived form of the parameters (bf16 casts, packed weights) refreshed from "
-                                                                   "the masters in ONE launch after the optimizer step (richsem_amd/repack.py) "
-                                                                   "instead of rebuilt by every cache inside the captured graphs")
-    a_ = ap.parse_args()
-    dn_kw = {"device_dn": True} if a_.device_dn else {}
-    if a_.library_optimizer:
-        dn_kw["library"] = True
-    if a_.grouped_repack:
-        dn_kw["grouped_repack"] = True
-    if a_.device_matcher:
-        kw = dict(**dn_kw, steps=a_.steps, warmup=a_.warmup, boxes_per_image=a_.boxes_per_image, **({"fed_loss": True} if a_.fed_loss else {}),
-                  **({"device_distill": True} if a_.device_distill else {}), **({"device_geometry": True} if a_.device_geometry else {}))
-        res = {"boxes_per_image": a_.boxes_per_image}
-        for name, dm in (("host_matcher", False), ("host_matcher_again", False), ("device_matcher", True)):
-            r = run_graphed(a_.images, torch.device("cuda", 0), device_matcher=dm, **kw)
-            res[name] = {k: r[k] for k in ("ms", "img_per_s", "loss")}
-            torch.cuda.empty_cache()
-            print(json.dumps({name: res[name]}), file=sys.stderr, flush=True)
-        print(json.dumps(res, indent=1))
-        sys.exit(0)
-    print(json.dumps(run(a_.images, torch.device("cuda", 0), a_.steps, a_.warmup, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at,
-                         **({"fed_loss": True} if a_.fed_loss else {}), **({"device_distill": True} if a_.device_distill else {}),
-                         **({"device_geometry": True} if a_.device_geometry else {}), **dn_kw,
-                         **({"boxes_per_image": a_.boxes_per_image} if a_.boxes_per_image != 12 else {})),
-                     indent=1))
+    ap.add_argument("--device-matcher", action="store_true", help="time the graphed training step in both forms: the Hungarian assignment on the host "
+                    "between two captured parts (twice, to show its spread) and on the device inside one captured step")
+    for flag, _, text in SWITCHES:
+        ap.add_argument(flag, action="store_true", help=text)
+    return ap.parse_args(argv)
+
+
+def cli_kwargs(a_):
+    """the parsed command line -> (Step's keywords, the harness's): a switch of the table goes to Step where Step takes its keyword, to the
+    harness otherwise, and only where its flag is given"""
+    on = {kw: True for flag, kw, _ in SWITCHES if getattr(a_, flag[2:].replace("-", "_"))}
+    of_step = inspect.signature(Step.__init__).parameters
+    return ({"boxes_per_image": a_.boxes_per_image, **{k: v for k, v in on.items() if k in of_step}},
+            {"steps": a_.steps, "warmup": a_.warmup, **{k: v for k, v in on.items() if k not in of_step}})
+
+
+def main(argv=None):
+    import json
+    a_ = parse_args(argv)
+    step_kw, harness_kw = cli_kwargs(a_)
+    dev = torch.device("cuda", 0)
+    if not a_.device_matcher:
+        print(json.dumps(run(a_.images, dev, graph=not (a_.no_graph or a_.stop_at), stop_at=a_.stop_at, **harness_kw, **step_kw), indent=1))
+        return
+    res = {"boxes_per_image": a_.boxes_per_image}
+    for name, dm in (("host_matcher", False), ("host_matcher_again", False), ("device_matcher", True)):
+        r = run_graphed(a_.images, dev, device_matcher=dm, **harness_kw, **step_kw)
+        res[name] = {k: r[k] for k in ("ms", "img_per_s", "loss")}
+        torch.cuda.empty_cache()
+        print(json.dumps({name: res[name]}), file=sys.stderr, flush=True)
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()

@@ -272,12 +272,8 @@ STEP_TOL = 1e-2
 
 def _step_outputs(model, images, mask, targets, topk=None):
     """the model part (no teacher) with the two-stage selection ``topk`` held fixed (None: the model's own)"""
-    model._model_only = "student"
-    try:
-        with torch.no_grad():
-            return [t.detach().float().clone() for t in model.forward(images, mask, targets, None, topk)]
-    finally:
-        model._model_only = False
+    with torch.no_grad():
+        return [t.detach().float().clone() for t in model.model_part(images, mask, targets, teacher=False, topk=topk)]
 
 
 def _fresh_step(state=None, seed=0):
