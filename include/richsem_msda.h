@@ -739,6 +739,30 @@ int msda_cls_pack(const float *G, int classes, const float *A, int d_model, uint
 int msda_cls_max_scores(const void *x, int x_is_bf16, const uint16_t *packed, int tokens, int d_model, int classes, float scale,
                         int parts, float *scores, msda_stream_t stream);
 
+/* ---- class head: the CLIP-text logits themselves, forward and backward (reference models/richsem/richsem.py:182-205, CLIPAlign.forward /
+ * forward_hs in the shipped configuration; csrc/cls_head_mfma.hip) -----------------------------------------------------------------
+ *     n2 = x . (A x),   logits[row, c] = scale * (G x)_c / sqrt(n2)                        G, A as for msda_cls_pack
+ *     dx = (scale / n) G^T g - (beta / n2) (A x),   beta = sum_c g_c logits_c,   n = sqrt(n2)
+ *     dGA = [dG (classes x 256); dA (256 x 256)] = Y^T x,   Y = [ (scale / n) g | -(beta / (2 n2)) x ]   (the caller forms
+ *     dWp = T^^T dG + Wp (dA + dA^T))
+ * msda_cls_head_pack writes its own operand (msda_cls_head_packed_elems uint16 elements: A's tiles in front of G's, then G^T for the
+ * backward); the layout of msda_cls_pack is a different one and is not accepted here.  x (tokens, 256) fp32, or bf16 when x_is_bf16;
+ * logits, g (tokens, classes) fp32, dense; n2, beta (tokens) fp32; dx (tokens, 256) in x's type.  parts as for msda_cls_max_scores; in
+ * the backward parts = 2 also splits g (hi + lo), parts = 1 rounds every operand to bf16 once.  msda_cls_head_backward_rows WRITES beta,
+ * msda_cls_head_backward_weights READS it: rows first.  The weights call sums splits of 512 rows through `workspace`
+ * (msda_cls_head_workspace_bytes) in a fixed order -- no atomics, the same bits on every run.  No call allocates or synchronises; all
+ * can be captured into a graph.  d_model must be 256; 1 <= classes <= 8192; tokens >= 1; x, packed, dx, workspace and dGA 16-byte
+ * aligned.  A row x = 0 yields NaN logits and NaN dx in that row only, and a NaN dGA (as the reference's f / |f| does). */
+int msda_cls_head_packed_elems(int classes, int64_t *elems);
+int msda_cls_head_pack(const float *G, int classes, const float *A, int d_model, uint16_t *packed, msda_stream_t stream);
+int msda_cls_head_forward(const void *x, int x_is_bf16, const uint16_t *packed, int tokens, int d_model, int classes, float scale,
+                          int parts, float *logits, float *n2, msda_stream_t stream);
+int msda_cls_head_backward_rows(const float *g, const float *logits, const float *n2, const void *x, int x_is_bf16, const uint16_t *packed,
+                                int tokens, int d_model, int classes, float scale, int parts, void *dx, float *beta, msda_stream_t stream);
+int msda_cls_head_workspace_bytes(int tokens, int classes, int64_t *bytes);
+int msda_cls_head_backward_weights(const float *g, const float *n2, const float *beta, const void *x, int x_is_bf16, int tokens, int d_model,
+                                   int classes, float scale, int parts, void *workspace, float *dGA, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller
