@@ -763,6 +763,26 @@ int msda_cls_head_workspace_bytes(int tokens, int classes, int64_t *bytes);
 int msda_cls_head_backward_weights(const float *g, const float *n2, const float *beta, const void *x, int x_is_bf16, int tokens, int d_model,
                                    int classes, float scale, int parts, void *workspace, float *dGA, msda_stream_t stream);
 
+/* ---- Swin shifted-window attention, forward and backward (reference models/richsem/swin_transformer.py:108-139 inside :183-239, mask
+ * of :353-369; csrc/swin_attn_mfma.hip) -- map layout in, map layout out: roll, window partition / reverse are index arithmetic ----------
+ *     out = softmax(q k^T / sqrt(32) + bias + mask) v   per (image, window, head)
+ * qkv (B, Hp, Wp, 3 channels) bf16 dense, last dimension ordered (3, heads, 32); table ((2 window - 1)^2, heads) fp32; out, dout
+ * (B, Hp, Wp, channels) bf16; lse (B, Hp, Wp, heads) fp32, written by the forward and read by the backward; dqkv as qkv, dtable as table.
+ * Window (wy, wx) holds rolled coordinates (wy window + i, wx window + j), token t = i window + j, living at ((py + shift) mod Hp,
+ * (px + shift) mod Wp); bias of (t, t') = table[(i - i' + window - 1)(2 window - 1) + (j - j' + window - 1), head]; for shift > 0 pairs of
+ * different regions (3 r(py, Hp) + r(px, Wp), r(c, n) = [c >= n - window] + [c >= n - shift]) get the reference's additive -100.
+ * The backward writes every element of dqkv once (no pre-zeroed output) and sums dtable through `workspace`
+ * (msda_swin_attn_workspace_bytes, contents irrelevant on entry) in a fixed order: no atomics, the same bits on every call.  No call
+ * allocates or synchronises.  Limits: channels == 32 heads, window^2 <= 144, 0 <= shift < window, Hp and Wp multiples of window, B >= 1
+ * (MSDA_ERR_BAD_DIMS); B Hp Wp < 2^31, heads <= 65535 (MSDA_ERR_TOO_LARGE); qkv, out, dout, dqkv 16-byte aligned, the fp32 buffers 4
+ * (MSDA_ERR_MISALIGNED). */
+int msda_swin_attn_workspace_bytes(int B, int Hp, int Wp, int channels, int heads, int window, int64_t *bytes);
+int msda_swin_attn_forward_bf16(const uint16_t *qkv, const float *table, int B, int Hp, int Wp, int channels, int heads, int window,
+                                int shift, uint16_t *out, float *lse, msda_stream_t stream);
+int msda_swin_attn_backward_bf16(const uint16_t *qkv, const float *table, const uint16_t *out, const float *lse, const uint16_t *dout, int B,
+                                 int Hp, int Wp, int channels, int heads, int window, int shift, uint16_t *dqkv, float *dtable,
+                                 void *workspace, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

@@ -1,0 +1,400 @@
+"""The Swin backbone with its shifted-window attention as one kernel per direction.
+
+Reference: models/richsem/swin_transformer.py.  :func:`window_attention` computes, per (image, window, head),
+``softmax(q k^T / sqrt(32) + relative-position bias + region mask) v`` on MAP-layout operands -- ``qkv`` (B, Hp, Wp, 3 C) with the last
+dimension ordered (3, heads, 32) -- and returns (B, Hp, Wp, C): the reference's ``torch.roll``, ``window_partition``, bias gather, mask
+tensor, ``window_reverse`` and second roll are index arithmetic inside the kernels (csrc/swin_attn_mfma.hip; C ABI ``msda_swin_attn_*``).
+Its backward writes ``dqkv`` once and ``dtable`` with a fixed summation order (bitwise reproducible).
+
+The classes mirror the reference's -- constructor arguments and state-dict keys (``relative_position_index`` included), so a reference
+checkpoint loads with ``strict=True`` both ways.  bf16 tensors on the device take the kernels; CPU tensors and fp32 / fp64 tensors run
+:func:`window_attention_torch`, the same formula as a plain torch composition over map indices (what makes the mirrors testable in
+float64).  A bf16 device tensor never falls back to the composition: a missing library or a head dimension other than 32 raises.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+__all__ = ["window_attention", "window_attention_torch", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer",
+           "PatchEmbed", "SwinTransformer", "Mlp", "DropPath"]
+
+HEAD_DIM = 32      # what the kernels are built for (every Swin variant of the reference: swin_transformer.py:676-710)
+
+
+# ---- the map <-> window index arithmetic ---------------------------------------------------------------------------------------------
+def window_pixels(Hp, Wp, window, shift, device=None):
+    """-> (pix, region), both (windows, window^2) int64: token t = i * window + j of window (wy, wx) has rolled coordinates
+    (py, px) = (wy * window + i, wx * window + j), lives at pixel ((py + shift) % Hp) * Wp + (px + shift) % Wp of the map and belongs to
+    region 3 r(py, Hp) + r(px, Wp), r(c, n) = [c >= n - window] + [c >= n - shift] (all zero for shift = 0)"""
+    py, px = torch.arange(Hp, device=device), torch.arange(Wp, device=device)
+    pix = ((py + shift) % Hp)[:, None] * Wp + ((px + shift) % Wp)[None, :]
+    if shift > 0:
+        ry = (py >= Hp - window).long() + (py >= Hp - shift).long()
+        rx = (px >= Wp - window).long() + (px >= Wp - shift).long()
+        region = 3 * ry[:, None] + rx[None, :]
+    else:
+        region = torch.zeros(Hp, Wp, dtype=torch.long, device=device)
+
+    def cut(m):
+        return m.view(Hp // window, window, Wp // window, window).permute(0, 2, 1, 3).reshape(-1, window * window)
+    return cut(pix), cut(region)
+
+
+def bias_index(window, device=None):
+    """(window^2, window^2) int64: (i - i' + window - 1) (2 window - 1) + (j - j' + window - 1) for tokens t = i window + j, t' = i' window + j'"""
+    t = torch.arange(window * window, device=device)
+    i, j = t // window, t % window
+    return (i[:, None] - i[None, :] + window - 1) * (2 * window - 1) + (j[:, None] - j[None, :] + window - 1)
+
+
+def window_attention_torch(qkv, table, num_heads, window, shift, scale=None):
+    """The formula of :func:`window_attention` as torch operations in the operands' dtype (any device): gathers the windows' tokens by
+    pixel index, adds bias and the -100 region mask, and scatters the result back.  Differentiable by autograd."""
+    B, Hp, Wp, C3 = qkv.shape
+    C, N = C3 // 3, window * window
+    hd = C // num_heads
+    scale = hd ** -0.5 if scale is None else scale
+    pix, region = window_pixels(Hp, Wp, window, shift, qkv.device)
+    tok = qkv.reshape(B, Hp * Wp, 3, num_heads, hd)[:, pix]                      # (B, windows, N, 3, heads, hd)
+    q, k, v = tok[:, :, :, 0], tok[:, :, :, 1], tok[:, :, :, 2]
+    score = torch.einsum("bwnhd,bwmhd->bwhnm", q * scale, k)
+    score = score + table[bias_index(window, qkv.device)].permute(2, 0, 1)      # (heads, N, N)
+    if shift > 0:
+        differ = region[:, :, None] != region[:, None, :]                        # (windows, N, N)
+        score = score + (differ.to(score.dtype) * -100.0)[None, :, None]
+    o = torch.einsum("bwhnm,bwmhd->bwnhd", score.softmax(-1), v).reshape(B, -1, C)
+    out = torch.empty(B, Hp * Wp, C, dtype=o.dtype, device=o.device)
+    out = out.index_copy(1, pix.reshape(-1), o)
+    return out.view(B, Hp, Wp, C)
+
+
+# ---- the kernels ------------------------------------------------------------------------------------------------------------------------
+def workspace_bytes(B, Hp, Wp, channels, num_heads, window):
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().msda_swin_attn_workspace_bytes(B, Hp, Wp, channels, num_heads, window, ctypes.byref(n)))
+    return n.value
+
+
+def _check_operands(qkv, table, num_heads, window):
+    if not qkv.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    if qkv.dtype != torch.bfloat16:
+        raise RuntimeError(f"window_attention: bfloat16 qkv, got {qkv.dtype}")
+    if qkv.dim() != 4 or qkv.shape[-1] % 3:
+        raise RuntimeError(f"window_attention: qkv (B, Hp, Wp, 3 C), got {tuple(qkv.shape)}")
+    if not qkv.is_contiguous():
+        raise RuntimeError("window_attention: qkv must be contiguous")
+    if table.dim() != 2 or tuple(table.shape) != ((2 * window - 1) ** 2, num_heads):
+        raise RuntimeError(f"window_attention: table ((2 window - 1)^2, heads) = {((2 * window - 1) ** 2, num_heads)}, got {tuple(table.shape)}")
+    if table.device != qkv.device:
+        raise RuntimeError("window_attention: table and qkv on different devices")
+
+
+class _WindowAttentionFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, table, num_heads, window, shift):
+        _check_operands(qkv, table, num_heads, window)
+        B, Hp, Wp, C3 = qkv.shape
+        C = C3 // 3
+        tab = table.detach().float().contiguous()
+        out = torch.empty(B, Hp, Wp, C, dtype=torch.bfloat16, device=qkv.device)
+        lse = torch.empty(B, Hp, Wp, num_heads, dtype=torch.float32, device=qkv.device)
+        with _lib.on_device(qkv.device):
+            _lib.check(_lib.load().msda_swin_attn_forward_bf16(qkv.data_ptr(), tab.data_ptr(), B, Hp, Wp, C, num_heads, window, shift,
+                                                               out.data_ptr(), lse.data_ptr(), _lib.raw_stream(qkv.device)))
+        ctx.save_for_backward(qkv, tab, out, lse)
+        ctx.args = (num_heads, window, shift, table.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, tab, out, lse = ctx.saved_tensors
+        num_heads, window, shift, table_dtype = ctx.args
+        B, Hp, Wp, C3 = qkv.shape
+        C = C3 // 3
+        dout = dout.contiguous()
+        dqkv = torch.empty_like(qkv)
+        dtable = torch.empty_like(tab)
+        ws = torch.empty(workspace_bytes(B, Hp, Wp, C, num_heads, window) // 4, dtype=torch.float32, device=qkv.device)
+        with _lib.on_device(qkv.device):
+            _lib.check(_lib.load().msda_swin_attn_backward_bf16(qkv.data_ptr(), tab.data_ptr(), out.data_ptr(), lse.data_ptr(), dout.data_ptr(),
+                                                                B, Hp, Wp, C, num_heads, window, shift, dqkv.data_ptr(), dtable.data_ptr(),
+                                                                ws.data_ptr(), _lib.raw_stream(qkv.device)))
+        return dqkv, dtable.to(table_dtype), None, None, None
+
+
+def window_attention(qkv, table, num_heads, window, shift):
+    """qkv (B, Hp, Wp, 3 * 32 * num_heads) bfloat16 on the device, contiguous, Hp and Wp multiples of ``window``; table
+    ((2 window - 1)^2, num_heads) -> (B, Hp, Wp, 32 * num_heads) bfloat16.  Gradients for ``qkv`` and ``table``."""
+    return _WindowAttentionFunction.apply(qkv, table, num_heads, window, shift)
+
+
+# ---- the mirrors ------------------------------------------------------------------------------------------------------------------------
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _refuse(name, value):
+    if value:
+        raise NotImplementedError(f"richsem_amd.swin: {name}={value!r} is not supported (only {name}=0 / False)")
+
+
+class DropPath(nn.Module):
+    """per-sample stochastic depth on the residual branch (timm's DropPath, which the reference imports)"""
+
+    def __init__(self, drop_prob=0.):
+        super().__init__()
+        self.drop_prob = float(drop_prob)
+
+    def forward(self, x):
+        if self.drop_prob == 0. or not self.training:
+            return x
+        keep = 1. - self.drop_prob
+        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
+        return x / keep * mask
+
+
+class Mlp(nn.Module):
+    def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
+        super().__init__()
+        _refuse("drop", drop)
+        out_features = out_features or in_features
+        hidden_features = hidden_features or in_features
+        self.fc1 = nn.Linear(in_features, hidden_features)
+        self.act = act_layer()
+        self.fc2 = nn.Linear(hidden_features, out_features)
+
+    def forward(self, x):
+        return self.fc2(self.act(self.fc1(x)))
+
+
+class WindowAttention(nn.Module):
+    """``forward(x, shift)``: x (B, Hp, Wp, dim) in map layout, Hp and Wp multiples of the window -> the same shape (qkv, windowed
+    attention, proj: proj acts per token, so it commutes with window_reverse)"""
+
+    def __init__(self, dim, window_size, num_heads, qkv_bias=True, qk_scale=None, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        _refuse("attn_drop", attn_drop)
+        _refuse("drop", proj_drop)
+        self.dim = dim
+        self.window_size = _pair(window_size)
+        if self.window_size[0] != self.window_size[1]:
+            raise NotImplementedError("richsem_amd.swin: square windows only")
+        self.num_heads = num_heads
+        head_dim = dim // num_heads
+        self.scale = qk_scale or head_dim ** -0.5
+        w = self.window_size[0]
+        self.relative_position_bias_table = nn.Parameter(torch.zeros((2 * w - 1) * (2 * w - 1), num_heads))
+        self.register_buffer("relative_position_index", bias_index(w))
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.proj = nn.Linear(dim, dim)
+        nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
+
+    def forward(self, x, shift=0):
+        w = self.window_size[0]
+        qkv = self.qkv(x)
+        table = self.relative_position_bias_table
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            if self.dim != HEAD_DIM * self.num_heads:
+                raise RuntimeError(f"richsem_amd.swin: the kernels need head dimension {HEAD_DIM}, got {self.dim // self.num_heads}")
+            ratio = self.scale * HEAD_DIM ** 0.5
+            if abs(ratio - 1.) > 1e-12:      # a qk_scale of the caller's: into q
+                qkv = torch.cat([qkv[..., :self.dim] * ratio, qkv[..., self.dim:]], -1)
+            attn = window_attention(qkv.contiguous(), table, self.num_heads, w, shift)
+        else:
+            attn = window_attention_torch(qkv, table, self.num_heads, w, shift, self.scale)
+        return self.proj(attn)
+
+
+class SwinTransformerBlock(nn.Module):
+    def __init__(self, dim, num_heads, window_size=7, shift_size=0, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0., attn_drop=0.,
+                 drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm):
+        super().__init__()
+        _refuse("drop", drop)
+        _refuse("attn_drop", attn_drop)
+        self.dim = dim
+        self.num_heads = num_heads
+        self.window_size = window_size
+        self.shift_size = shift_size
+        self.mlp_ratio = mlp_ratio
+        assert 0 <= self.shift_size < self.window_size, "shift_size must in 0-window_size"
+        self.norm1 = norm_layer(dim)
+        self.attn = WindowAttention(dim, window_size=_pair(window_size), num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale,
+                                    attn_drop=attn_drop, proj_drop=drop)
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
+        self.H = None
+        self.W = None
+
+    def forward(self, x, mask_matrix=None):
+        """x (B, H * W, C) with self.H, self.W set by the layer.  ``mask_matrix`` is accepted for the reference's call and not used: the
+        regions are computed from the coordinates."""
+        B, L, C = x.shape
+        H, W, w = self.H, self.W, self.window_size
+        assert L == H * W, "input feature has wrong size"
+        shortcut = x
+        x = self.norm1(x).view(B, H, W, C)
+        pad_r, pad_b = (w - W % w) % w, (w - H % w) % w
+        if pad_r or pad_b:
+            x = F.pad(x, (0, 0, 0, pad_r, 0, pad_b))      # zeros AFTER the norm: padded tokens carry the qkv bias, as the reference's
+        x = self.attn(x, self.shift_size)
+        if pad_r or pad_b:
+            x = x[:, :H, :W, :].contiguous()
+        x = shortcut + self.drop_path(x.view(B, H * W, C))
+        return x + self.drop_path(self.mlp(self.norm2(x)))
+
+
+class PatchMerging(nn.Module):
+    def __init__(self, dim, norm_layer=nn.LayerNorm):
+        super().__init__()
+        self.dim = dim
+        self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
+        self.norm = norm_layer(4 * dim)
+
+    def forward(self, x, H, W):
+        B, L, C = x.shape
+        assert L == H * W, "input feature has wrong size"
+        x = x.view(B, H, W, C)
+        if H % 2 or W % 2:
+            x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
+        H2, W2 = (H + 1) // 2, (W + 1) // 2
+        # (B, H2, dy, W2, dx, C) -> channels ordered (dx, dy, C): the reference's cat of (0,0), (1,0), (0,1), (1,1) as (row, column) offsets
+        x = x.view(B, H2, 2, W2, 2, C).permute(0, 1, 3, 4, 2, 5).reshape(B, H2 * W2, 4 * C)
+        return self.reduction(self.norm(x))
+
+
+class BasicLayer(nn.Module):
+    def __init__(self, dim, depth, num_heads, window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0., attn_drop=0.,
+                 drop_path=0., norm_layer=nn.LayerNorm, downsample=None, use_checkpoint=False):
+        super().__init__()
+        _refuse("use_checkpoint", use_checkpoint)
+        _refuse("drop", drop)
+        _refuse("attn_drop", attn_drop)
+        self.window_size = window_size
+        self.shift_size = window_size // 2
+        self.depth = depth
+        self.use_checkpoint = use_checkpoint
+        self.blocks = nn.ModuleList([
+            SwinTransformerBlock(dim=dim, num_heads=num_heads, window_size=window_size, shift_size=0 if i % 2 == 0 else window_size // 2,
+                                 mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop, attn_drop=attn_drop,
+                                 drop_path=drop_path[i] if isinstance(drop_path, (list, tuple)) else drop_path, norm_layer=norm_layer)
+            for i in range(depth)])
+        self.downsample = downsample(dim=dim, norm_layer=norm_layer) if downsample is not None else None
+
+    def forward(self, x, H, W):
+        """x (B, H * W, C) -> (x, H, W, x_down, Wh, Ww) as the reference"""
+        for blk in self.blocks:
+            blk.H, blk.W = H, W
+            x = blk(x)
+        if self.downsample is not None:
+            return x, H, W, self.downsample(x, H, W), (H + 1) // 2, (W + 1) // 2
+        return x, H, W, x, H, W
+
+
+class PatchEmbed(nn.Module):
+    def __init__(self, patch_size=4, in_chans=3, embed_dim=96, norm_layer=None):
+        super().__init__()
+        self.patch_size = _pair(patch_size)
+        self.in_chans = in_chans
+        self.embed_dim = embed_dim
+        self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.patch_size)
+        self.norm = norm_layer(embed_dim) if norm_layer is not None else None
+
+    def forward(self, x):
+        _, _, H, W = x.shape
+        ph, pw = self.patch_size
+        if W % pw or H % ph:
+            x = F.pad(x, (0, (pw - W % pw) % pw, 0, (ph - H % ph) % ph))
+        x = self.proj(x)
+        if self.norm is not None:
+            Wh, Ww = x.shape[2], x.shape[3]
+            x = self.norm(x.flatten(2).transpose(1, 2)).transpose(1, 2).reshape(-1, self.embed_dim, Wh, Ww)
+        return x
+
+
+class SwinTransformer(nn.Module):
+    """``forward_raw(images)`` -> the tuple of (B, C_i, H_i, W_i) features of ``out_indices``; ``forward(images, mask)`` -> a list of
+    (feature, mask) pairs with the padding mask (B, H, W) bool interpolated to each level as the reference's NestedTensor wrapper does."""
+
+    def __init__(self, pretrain_img_size=224, patch_size=4, in_chans=3, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24),
+                 window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.2,
+                 norm_layer=nn.LayerNorm, ape=False, patch_norm=True, out_indices=(0, 1, 2, 3), frozen_stages=-1, dilation=False,
+                 use_checkpoint=False):
+        super().__init__()
+        _refuse("use_checkpoint", use_checkpoint)
+        _refuse("drop_rate", drop_rate)
+        _refuse("attn_drop_rate", attn_drop_rate)
+        self.pretrain_img_size = pretrain_img_size
+        self.num_layers = len(depths)
+        self.embed_dim = embed_dim
+        self.ape = ape
+        self.patch_norm = patch_norm
+        self.out_indices = out_indices
+        self.frozen_stages = frozen_stages
+        self.dilation = dilation
+        self.patch_embed = PatchEmbed(patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim,
+                                      norm_layer=norm_layer if patch_norm else None)
+        if ape:
+            size, patch = _pair(pretrain_img_size), _pair(patch_size)
+            self.absolute_pos_embed = nn.Parameter(torch.zeros(1, embed_dim, size[0] // patch[0], size[1] // patch[1]))
+            nn.init.trunc_normal_(self.absolute_pos_embed, std=.02)
+        dpr = [v.item() for v in torch.linspace(0, drop_path_rate, sum(depths))]
+        downsample = [PatchMerging] * self.num_layers
+        downsample[-1] = None
+        num_features = [int(embed_dim * 2 ** i) for i in range(self.num_layers)]
+        if dilation:
+            downsample[-2] = None
+            num_features[-1] = int(embed_dim * 2 ** (self.num_layers - 1)) // 2
+        self.layers = nn.ModuleList([
+            BasicLayer(dim=num_features[i], depth=depths[i], num_heads=num_heads[i], window_size=window_size, mlp_ratio=mlp_ratio,
+                       qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop_rate, attn_drop=attn_drop_rate,
+                       drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])], norm_layer=norm_layer, downsample=downsample[i],
+                       use_checkpoint=use_checkpoint)
+            for i in range(self.num_layers)])
+        self.num_features = num_features
+        for i in out_indices:
+            self.add_module(f"norm{i}", norm_layer(num_features[i]))
+        self._freeze_stages()
+
+    def _freeze_stages(self):
+        if self.frozen_stages >= 0:
+            self.patch_embed.eval()
+            for p in self.patch_embed.parameters():
+                p.requires_grad = False
+        if self.frozen_stages >= 1 and self.ape:
+            self.absolute_pos_embed.requires_grad = False
+        if self.frozen_stages >= 2:
+            for i in range(0, self.frozen_stages - 1):
+                m = self.layers[i]
+                m.eval()
+                for p in m.parameters():
+                    p.requires_grad = False
+
+    def forward_raw(self, x):
+        x = self.patch_embed(x)
+        Wh, Ww = x.shape[2], x.shape[3]
+        if self.ape:
+            x = x + F.interpolate(self.absolute_pos_embed, size=(Wh, Ww), mode="bicubic")
+        x = x.flatten(2).transpose(1, 2)
+        outs = []
+        for i, layer in enumerate(self.layers):
+            x_out, H, W, x, Wh, Ww = layer(x, Wh, Ww)
+            if i in self.out_indices:
+                x_out = getattr(self, f"norm{i}")(x_out)
+                outs.append(x_out.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2).contiguous())
+        return tuple(outs)
+
+    def forward(self, images, mask):
+        assert mask is not None
+        outs = self.forward_raw(images)
+        return [(o, F.interpolate(mask[None].float(), size=o.shape[-2:]).to(torch.bool)[0]) for o in outs]
+
+    def train(self, mode=True):
+        super().train(mode)
+        self._freeze_stages()
+        return self
