@@ -783,6 +783,34 @@ int msda_swin_attn_backward_bf16(const uint16_t *qkv, const float *table, const 
                                  int Hp, int Wp, int channels, int heads, int window, int shift, uint16_t *dqkv, float *dtable,
                                  void *workspace, msda_stream_t stream);
 
+/* ---- the rest of a Swin block: linear layers of general width with fused epilogues, LayerNorm of general width (reference
+ * models/richsem/swin_transformer.py:27-44 Mlp, :108-139 qkv / proj, :183-239 norm1, norm2 and the residual adds;
+ * csrc/swin_block_mfma.hip) -- bf16 storage, fp32 accumulation and element-wise arithmetic, one rounding per stored element ----------
+ * msda_swin_linear_bf16:  acc = x (tokens, K) . w (N, K)^T, both bf16 row-major (no packed form: the input gradient is the same call on
+ * the transposed weight); bias (N) fp32 or NULL; out (tokens, N) bf16.  `epilogue`:
+ *   0  out = rnd(acc + bias)
+ *   1  u = rnd(acc + bias) -> out2 (tokens, N) unless NULL;  out = rnd(gelu(u)) of the ROUNDED u, gelu(x) = x Phi(x) (the erf form)
+ *   2  out = rnd(acc + bias + aux), aux (tokens, N) bf16
+ *   3  out = rnd(acc gelu'(aux)), gelu'(x) = Phi(x) + x phi(x), aux = the u of epilogue 1;  out2 = rnd(gelu(aux)) unless NULL (bias unused)
+ * msda_swin_layernorm_forward_bf16:  out = rnd((x - mean) rstd gamma + beta) per token over C channels, biased variance in fp32;
+ * x, out (tokens, C) bf16, gamma, beta (C) fp32, mean, rstd (tokens) fp32 written unless NULL.
+ * msda_swin_layernorm_backward_bf16:  with xhat = (x - mean) rstd recomputed and g = dy gamma,
+ *   dx = rnd(add + rstd (g - mean_c(g) - xhat mean_c(g xhat))),  dgamma = sum_t dy xhat,  dbeta = sum_t dy
+ * add (tokens, C) bf16 or NULL (the residual stream's gradient, fused so that the sum is rounded once); dgamma, dbeta (C) fp32, each may be
+ * NULL; they are summed through `workspace` (msda_swin_layernorm_workspace_bytes, contents irrelevant on entry; may be NULL when both are)
+ * in a fixed order.  No atomics, the same bits on every call; no call allocates or synchronises.
+ * Limits: K, N multiples of 32 in [32, 8192], C a multiple of 32 in [32, 4096], tokens >= 1, epilogue in 0..3 (MSDA_ERR_BAD_DIMS);
+ * tokens K, tokens N, tokens C < 2^31 (MSDA_ERR_TOO_LARGE); the bf16 buffers 16-byte aligned, the fp32 ones 4 (MSDA_ERR_MISALIGNED); aux
+ * NULL for epilogue 2 or 3 is MSDA_ERR_NULL_POINTER.  Every check comes before any launch. */
+int msda_swin_linear_bf16(const uint16_t *x, const uint16_t *w, const float *bias, const uint16_t *aux, int epilogue, int tokens, int K, int N,
+                          uint16_t *out, uint16_t *out2, msda_stream_t stream);
+int msda_swin_layernorm_forward_bf16(const uint16_t *x, const float *gamma, const float *beta, float eps, int tokens, int C, uint16_t *out,
+                                     float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_layernorm_workspace_bytes(int tokens, int C, int64_t *bytes);
+int msda_swin_layernorm_backward_bf16(const uint16_t *dy, const uint16_t *x, const float *mean, const float *rstd, const float *gamma,
+                                      const uint16_t *add, int tokens, int C, uint16_t *dx, float *dgamma, float *dbeta, void *workspace,
+                                      msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

@@ -88,6 +88,7 @@ SYMBOLS = [
     "msda_cls_packed_elems", "msda_cls_pack", "msda_cls_max_scores",
     "msda_cls_head_packed_elems", "msda_cls_head_pack", "msda_cls_head_forward", "msda_cls_head_backward_rows", "msda_cls_head_workspace_bytes", "msda_cls_head_backward_weights",
     "msda_swin_attn_workspace_bytes", "msda_swin_attn_forward_bf16", "msda_swin_attn_backward_bf16",
+    "msda_swin_linear_bf16", "msda_swin_layernorm_forward_bf16", "msda_swin_layernorm_workspace_bytes", "msda_swin_layernorm_backward_bf16",
     "msda_conv_set_tiling", "msda_conv_set_ring", "msda_conv_dgrad_fused_bf16", "msda_conv_packed_elems", "msda_conv_pack_weight", "msda_conv_forward_bf16", "msda_conv_dgrad_bf16", "msda_conv_forward_workspace_bytes", "msda_conv_forward_ws_bf16", "msda_conv_dgrad_workspace_bytes", "msda_conv_dgrad_ws_bf16", "msda_pool_nhwc_bf16", "msda_groupnorm8_nhwc_bf16", "msda_groupnorm8_backward_nhwc_bf16", "msda_conv_wgrad_workspace_bytes", "msda_conv_wgrad_bf16", "msda_conv_set_wgrad_ring", "msda_conv_wgrad_group_workspace_bytes", "msda_conv_wgrad_group_bf16",
     "msda_optim_plan", "msda_optim_sumsq", "msda_optim_step", "msda_optim_ema",
     "msda_repack_plan", "msda_repack",
@@ -247,6 +248,14 @@ def load():
     L.msda_swin_attn_forward_bf16.restype = ci
     L.msda_swin_attn_backward_bf16.argtypes = [vp] * 5 + [ci] * 7 + [vp, vp, vp, vp]
     L.msda_swin_attn_backward_bf16.restype = ci
+    L.msda_swin_linear_bf16.argtypes = [vp] * 4 + [ci] * 4 + [vp, vp, vp]
+    L.msda_swin_linear_bf16.restype = ci
+    L.msda_swin_layernorm_forward_bf16.argtypes = [vp, vp, vp, ctypes.c_float, ci, ci] + [vp] * 4
+    L.msda_swin_layernorm_forward_bf16.restype = ci
+    L.msda_swin_layernorm_workspace_bytes.argtypes = [ci, ci, ctypes.POINTER(i64)]
+    L.msda_swin_layernorm_workspace_bytes.restype = ci
+    L.msda_swin_layernorm_backward_bf16.argtypes = [vp] * 6 + [ci, ci] + [vp] * 5
+    L.msda_swin_layernorm_backward_bf16.restype = ci
     L.msda_conv_pack_weight.argtypes = [vp, ci, ci, ci, ci, vp, vp]
     L.msda_conv_pack_weight.restype = ci
     L.msda_conv_set_tiling.argtypes = [ci, ci]

@@ -10,6 +10,13 @@ The classes mirror the reference's -- constructor arguments and state-dict keys 
 checkpoint loads with ``strict=True`` both ways.  bf16 tensors on the device take the kernels; CPU tensors and fp32 / fp64 tensors run
 :func:`window_attention_torch`, the same formula as a plain torch composition over map indices (what makes the mirrors testable in
 float64).  A bf16 device tensor never falls back to the composition: a missing library or a head dimension other than 32 raises.
+
+The rest of a block -- norm1, qkv, proj + residual, norm2, fc1, GELU, fc2 + residual -- runs on torch ops unless the block's plain
+attribute ``fused`` is set (``BasicLayer.set_fused`` / ``SwinTransformer.set_fused``; off by default, not a constructor argument and not
+in the state dict).  With it a bf16 device tensor takes :func:`swin_layernorm`, :func:`swin_linear` and :func:`swin_mlp`: a linear layer of
+general width with fused epilogues and a LayerNorm of general width (csrc/swin_block_mfma.hip; C ABI ``msda_swin_linear_bf16``,
+``msda_swin_layernorm_*``).  :func:`swin_mlp` is ONE autograd function for ``x + fc2(GELU(fc1(norm(x))))`` that saves the pre-activation
+``u`` and regenerates the hidden activation in its backward.  CPU, fp32 and fp64 tensors run the torch formula with ``fused`` set too.
 """
 import ctypes
 
@@ -18,9 +25,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .param_cache import VersionCache
 
-__all__ = ["window_attention", "window_attention_torch", "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer",
-           "PatchEmbed", "SwinTransformer", "Mlp", "DropPath"]
+__all__ = ["window_attention", "window_attention_torch", "swin_linear", "swin_layernorm", "swin_mlp", "WindowAttention",
+           "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer", "Mlp", "DropPath"]
 
 HEAD_DIM = 32      # what the kernels are built for (every Swin variant of the reference: swin_transformer.py:676-710)
 
@@ -133,6 +141,208 @@ def window_attention(qkv, table, num_heads, window, shift):
     return _WindowAttentionFunction.apply(qkv, table, num_heads, window, shift)
 
 
+# ---- the block's other kernels: linear with epilogues, LayerNorm ----------------------------------------------------------------------------
+EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BACKWARD = 0, 1, 2, 3      # `epilogue` of msda_swin_linear_bf16 (include/richsem_msda.h)
+BF16 = torch.bfloat16
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _rows(t, width, what):
+    if not t.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    if t.dtype != BF16 or t.shape[-1] != width:
+        raise RuntimeError(f"{what}: bfloat16 (..., {width}), got {t.dtype} {tuple(t.shape)}")
+    return t.reshape(-1, width).contiguous()
+
+
+def linear_kernel(x2, w16, b32=None, epilogue=EPI_BIAS, aux=None, want_out2=False):
+    """One call of ``msda_swin_linear_bf16`` (no autograd): x2 (tokens, K), w16 (N, K), aux (tokens, N) bf16 contiguous on the device, b32 (N)
+    float32 or None -> (out, out2), both (tokens, N) bf16; out2 is None unless ``want_out2`` (epilogues 1 and 3 write it)."""
+    T, K = x2.shape
+    N = w16.shape[0]
+    bias_ok = b32 is None or (b32.dtype == torch.float32 and b32.numel() == N and b32.is_contiguous())
+    if w16.dtype != BF16 or w16.shape[1] != K or not w16.is_contiguous() or not bias_ok:
+        raise RuntimeError(f"swin_linear: weight bfloat16 (N, {K}) contiguous and bias float32 (N), got {w16.dtype} {tuple(w16.shape)}")
+    if aux is not None and (aux.dtype != BF16 or tuple(aux.shape) != (T, N) or not aux.is_contiguous()):
+        raise RuntimeError(f"swin_linear: aux bfloat16 ({T}, {N}) contiguous, got {aux.dtype} {tuple(aux.shape)}")
+    out = torch.empty((T, N), dtype=BF16, device=x2.device)
+    out2 = torch.empty_like(out) if want_out2 else None
+    with _lib.on_device(x2.device):
+        _lib.check(_lib.load().msda_swin_linear_bf16(x2.data_ptr(), w16.data_ptr(), _ptr(b32), _ptr(aux), epilogue, T, K, N, out.data_ptr(),
+                                                     _ptr(out2), _lib.raw_stream(x2.device)))
+    return out, out2
+
+
+def layernorm_workspace_bytes(tokens, C):
+    n = ctypes.c_int64(0)
+    _lib.check(_lib.load().msda_swin_layernorm_workspace_bytes(tokens, C, ctypes.byref(n)))
+    return n.value
+
+
+def layernorm_kernel(x2, g32, b32, eps, want_stats=True):
+    """``msda_swin_layernorm_forward_bf16``: x2 (tokens, C) bf16 -> (out, mean, rstd); the statistics are None unless ``want_stats``"""
+    T, C = x2.shape
+    out = torch.empty_like(x2)
+    mean = torch.empty(T, dtype=torch.float32, device=x2.device) if want_stats else None
+    rstd = torch.empty_like(mean) if want_stats else None
+    with _lib.on_device(x2.device):
+        _lib.check(_lib.load().msda_swin_layernorm_forward_bf16(x2.data_ptr(), g32.data_ptr(), b32.data_ptr(), eps, T, C, out.data_ptr(),
+                                                                _ptr(mean), _ptr(rstd), _lib.raw_stream(x2.device)))
+    return out, mean, rstd
+
+
+def layernorm_backward_kernel(dy2, x2, mean, rstd, g32, add=None, want_gamma=True, want_beta=True):
+    """``msda_swin_layernorm_backward_bf16`` -> (dx bf16, dgamma float32 or None, dbeta float32 or None)"""
+    T, C = x2.shape
+    dx = torch.empty_like(x2)
+    dg = torch.empty(C, dtype=torch.float32, device=x2.device) if want_gamma else None
+    db = torch.empty(C, dtype=torch.float32, device=x2.device) if want_beta else None
+    ws = torch.empty(layernorm_workspace_bytes(T, C) // 4, dtype=torch.float32, device=x2.device) if want_gamma or want_beta else None
+    with _lib.on_device(x2.device):
+        _lib.check(_lib.load().msda_swin_layernorm_backward_bf16(dy2.data_ptr(), x2.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
+                                                                 _ptr(add), T, C, dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(ws),
+                                                                 _lib.raw_stream(x2.device)))
+    return dx, dg, db
+
+
+def _f32(p):
+    return p.detach().float().contiguous()
+
+
+def linear_forms(weight, bias):
+    """the forms the kernels read a linear layer from: ``w16`` (N, K) bf16, ``wt16`` (K, N) bf16 (the input gradient is the same kernel on
+    the transposed weight), ``b32`` float32 or None.  Kept per parameter version in a :class:`richsem_amd.param_cache.VersionCache`."""
+    w16 = weight.detach().to(BF16).contiguous()
+    return {"w16": w16, "wt16": w16.t().contiguous(), "b32": _f32(bias) if bias is not None else None}
+
+
+def _forms(cache, weight, bias):
+    if cache is None:
+        return linear_forms(weight, bias)
+    return cache.get([weight] + ([bias] if bias is not None else []), lambda: linear_forms(weight, bias))
+
+
+def _wgrad(ctx, iw, ib, dy2, x2, weight_dtype, bias_dtype):
+    """(dW, db) of one layer by the package's weight-gradient rule, in the parameters' dtypes; None where not needed"""
+    from .functions.linear import linear_bgrad, linear_wgrad
+    want_b = bias_dtype is not None and ctx.needs_input_grad[ib]
+    dw = db = None
+    if ctx.needs_input_grad[iw]:
+        dw, db = linear_wgrad(dy2, x2, want_b)
+        dw = dw.to(weight_dtype)
+    elif want_b:
+        db = linear_bgrad(dy2)
+    return dw, (db.to(bias_dtype) if want_b else None)
+
+
+class _SwinLinearFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, aux, forms):
+        K = weight.shape[1]
+        x2 = _rows(x, K, "swin_linear")
+        aux2 = _rows(aux, weight.shape[0], "swin_linear (aux)") if aux is not None else None
+        out, _ = linear_kernel(x2, forms["w16"], forms["b32"], EPI_RESIDUAL if aux is not None else EPI_BIAS, aux2)
+        ctx.save_for_backward(x2)
+        ctx.forms = forms
+        ctx.meta = (x.shape, aux.shape if aux is not None else None, weight.dtype, bias.dtype if bias is not None else None)
+        return out.view(x.shape[:-1] + (weight.shape[0],))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x2, = ctx.saved_tensors
+        shape, aux_shape, wdt, bdt = ctx.meta
+        dy2 = _rows(dy, ctx.forms["w16"].shape[0], "swin_linear (gradient)")
+        dx = linear_kernel(dy2, ctx.forms["wt16"])[0].view(shape) if ctx.needs_input_grad[0] else None
+        dw, db = _wgrad(ctx, 1, 2, dy2, x2, wdt, bdt)
+        return dx, dw, db, dy.reshape(aux_shape) if ctx.needs_input_grad[3] else None, None
+
+
+def swin_linear(x, weight, bias=None, epilogue=None, aux=None, cache=None):
+    """``x weight^T + bias`` (``epilogue=None``) or ``x weight^T + bias + aux`` (``epilogue="residual"``, the sum rounded once) on
+    ``msda_swin_linear_bf16``: x (..., K) bfloat16 on the device, weight (N, K), K and N multiples of 32 up to 8192 -> (..., N) bfloat16.
+    The input gradient is the same kernel on ``weight^T``; weight and bias gradients are ``functions.linear.linear_wgrad``'s, returned in
+    the parameters' dtypes.  ``cache``: a VersionCache that keeps the derived weight forms (:func:`linear_forms`) per parameter version.
+    The GELU epilogues belong to :func:`swin_mlp` (raw: :func:`linear_kernel`)."""
+    if epilogue not in (None, "residual") or (epilogue == "residual") != (aux is not None):
+        raise ValueError(f"swin_linear: epilogue None or 'residual' (with aux), got {epilogue!r}" + (" with aux" if aux is not None else ""))
+    return _SwinLinearFunction.apply(x, weight, bias, aux, _forms(cache, weight, bias))
+
+
+class _SwinLayerNormFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps):
+        x2 = _rows(x, weight.shape[0], "swin_layernorm")
+        g32 = _f32(weight)
+        need = any(ctx.needs_input_grad)
+        out, mean, rstd = layernorm_kernel(x2, g32, _f32(bias), eps, want_stats=need)
+        if need:
+            ctx.save_for_backward(x2, mean, rstd, g32)
+            ctx.meta = (x.shape, weight.dtype, bias.dtype)
+        return out.view(x.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x2, mean, rstd, g32 = ctx.saved_tensors
+        shape, wdt, bdt = ctx.meta
+        dx, dg, db = layernorm_backward_kernel(_rows(dy, x2.shape[1], "swin_layernorm (gradient)"), x2, mean, rstd, g32,
+                                               want_gamma=ctx.needs_input_grad[1], want_beta=ctx.needs_input_grad[2])
+        return (dx.view(shape) if ctx.needs_input_grad[0] else None, dg.to(wdt) if dg is not None else None,
+                db.to(bdt) if db is not None else None, None)
+
+
+def swin_layernorm(x, weight, bias, eps=1e-5):
+    """LayerNorm over the last dimension (C a multiple of 32 up to 4096) on ``msda_swin_layernorm_*``: x (..., C) bfloat16 on the device,
+    weight and bias (C) -> bfloat16.  Saves x and the fp32 statistics (nothing under ``no_grad``); gradients in the parameters' dtypes."""
+    return _SwinLayerNormFunction.apply(x, weight, bias, float(eps))
+
+
+class _SwinMlpFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, nw, nb, eps, w1, b1, w2, b2, f1, f2):
+        x2 = _rows(x, nw.shape[0], "swin_mlp")
+        g32 = _f32(nw)
+        need = any(ctx.needs_input_grad)
+        xn, mean, rstd = layernorm_kernel(x2, g32, _f32(nb), eps, want_stats=need)
+        h, u = linear_kernel(xn, f1["w16"], f1["b32"], EPI_GELU, want_out2=need)
+        out, _ = linear_kernel(h, f2["w16"], f2["b32"], EPI_RESIDUAL, x2)
+        if need:      # (the hidden activation h is not kept: the backward regenerates it from u)
+            ctx.save_for_backward(x2, xn, mean, rstd, u, g32)
+            ctx.forms = (f1, f2)
+            ctx.meta = (x.shape,) + tuple(p.dtype if p is not None else None for p in (nw, nb, w1, b1, w2, b2))
+        return out.view(x.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        x2, xn, mean, rstd, u, g32 = ctx.saved_tensors
+        (f1, f2), (shape, nwdt, nbdt, w1dt, b1dt, w2dt, b2dt) = ctx.forms, ctx.meta
+        d2 = _rows(dout, x2.shape[1], "swin_mlp (gradient)")
+        du, h = linear_kernel(d2, f2["wt16"], None, EPI_GELU_BACKWARD, u, want_out2=ctx.needs_input_grad[6])
+        dw2, db2 = _wgrad(ctx, 6, 7, d2, h, w2dt, b2dt)
+        dw1, db1 = _wgrad(ctx, 4, 5, du, xn, w1dt, b1dt)
+        dxn, _ = linear_kernel(du, f1["wt16"])
+        dx, dg, db = layernorm_backward_kernel(dxn, x2, mean, rstd, g32, add=d2, want_gamma=ctx.needs_input_grad[1],
+                                               want_beta=ctx.needs_input_grad[2])
+        return (dx.view(shape) if ctx.needs_input_grad[0] else None, dg.to(nwdt) if dg is not None else None,
+                db.to(nbdt) if db is not None else None, None, dw1, db1, dw2, db2, None, None)
+
+
+def swin_mlp(x, norm, fc1, fc2, caches=(None, None)):
+    """``x + fc2(GELU(fc1(norm(x))))`` as ONE autograd function: x (..., C) bfloat16 on the device, ``norm`` an ``nn.LayerNorm(C)``, ``fc1``
+    / ``fc2`` ``nn.Linear`` layers (C -> hidden -> C).  Forward: LayerNorm; fc1 with the GELU epilogue (the pre-activation u and
+    h = GELU(u)); fc2 with the residual epilogue.  Saved for the backward: x, norm(x), the statistics and u -- not h, which the backward
+    regenerates in the epilogue that forms du = (dout W2) gelu'(u); under ``no_grad`` neither u nor the statistics are written."""
+    if not isinstance(norm, nn.LayerNorm) or not norm.elementwise_affine or norm.bias is None:
+        raise RuntimeError("swin_mlp: norm must be an nn.LayerNorm with weight and bias")
+    return _SwinMlpFunction.apply(x, norm.weight, norm.bias, float(norm.eps), fc1.weight, fc1.bias, fc2.weight, fc2.bias,
+                                  _forms(caches[0], fc1.weight, fc1.bias), _forms(caches[1], fc2.weight, fc2.bias))
+
+
 # ---- the mirrors ------------------------------------------------------------------------------------------------------------------------
 def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
@@ -194,23 +404,33 @@ class WindowAttention(nn.Module):
         self.proj = nn.Linear(dim, dim)
         nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
 
+    def attend(self, qkv, shift):
+        """the kernels on a bf16 device ``qkv`` map (B, Hp, Wp, 3 dim) -> (B, Hp, Wp, dim)"""
+        if self.dim != HEAD_DIM * self.num_heads:
+            raise RuntimeError(f"richsem_amd.swin: the kernels need head dimension {HEAD_DIM}, got {self.dim // self.num_heads}")
+        ratio = self.scale * HEAD_DIM ** 0.5
+        if abs(ratio - 1.) > 1e-12:      # a qk_scale of the caller's: into q
+            qkv = torch.cat([qkv[..., :self.dim] * ratio, qkv[..., self.dim:]], -1)
+        return window_attention(qkv.contiguous(), self.relative_position_bias_table, self.num_heads, self.window_size[0], shift)
+
     def forward(self, x, shift=0):
-        w = self.window_size[0]
         qkv = self.qkv(x)
-        table = self.relative_position_bias_table
         if x.is_cuda and x.dtype == torch.bfloat16:
-            if self.dim != HEAD_DIM * self.num_heads:
-                raise RuntimeError(f"richsem_amd.swin: the kernels need head dimension {HEAD_DIM}, got {self.dim // self.num_heads}")
-            ratio = self.scale * HEAD_DIM ** 0.5
-            if abs(ratio - 1.) > 1e-12:      # a qk_scale of the caller's: into q
-                qkv = torch.cat([qkv[..., :self.dim] * ratio, qkv[..., self.dim:]], -1)
-            attn = window_attention(qkv.contiguous(), table, self.num_heads, w, shift)
+            attn = self.attend(qkv, shift)
         else:
-            attn = window_attention_torch(qkv, table, self.num_heads, w, shift, self.scale)
+            attn = window_attention_torch(qkv, self.relative_position_bias_table, self.num_heads, self.window_size[0], shift, self.scale)
         return self.proj(attn)
 
 
 class SwinTransformerBlock(nn.Module):
+    """The reference's block.  ``fused`` (a plain attribute, False by default; not a constructor argument, not in the state dict): a bf16
+    device tensor runs norm1, qkv, proj + residual and the whole second half on the library's kernels (:func:`swin_layernorm`,
+    :func:`swin_linear`, :func:`swin_mlp`) and never falls back -- a missing library or a width outside the kernels' limits raises.  CPU,
+    fp32 and fp64 tensors run the torch formula either way.  Stochastic depth is not fused: ``drop_path > 0`` in training mode raises
+    NotImplementedError under ``fused`` (``drop_path_rate=0.`` works; so does eval mode)."""
+
+    fused = False
+
     def __init__(self, dim, num_heads, window_size=7, shift_size=0, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop=0., attn_drop=0.,
                  drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm):
         super().__init__()
@@ -230,6 +450,26 @@ class SwinTransformerBlock(nn.Module):
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.H = None
         self.W = None
+        self._forms = {k: VersionCache() for k in ("qkv", "proj", "fc1", "fc2")}      # derived weight forms of the fused path
+
+    def _forward_fused(self, x):
+        B, L, C = x.shape
+        H, W, w = self.H, self.W, self.window_size
+        if isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0. and self.training:
+            raise NotImplementedError("richsem_amd.swin: fused blocks do not implement stochastic depth in training mode (drop_path_rate=0.)")
+        act = self.mlp.act
+        if not isinstance(self.norm1, nn.LayerNorm) or not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
+            raise NotImplementedError("richsem_amd.swin: fused blocks need nn.LayerNorm and the erf form of nn.GELU")
+        attn, shortcut = self.attn, x.contiguous()
+        x = swin_layernorm(shortcut, self.norm1.weight, self.norm1.bias, self.norm1.eps).view(B, H, W, C)
+        pad_r, pad_b = (w - W % w) % w, (w - H % w) % w
+        if pad_r or pad_b:
+            x = F.pad(x, (0, 0, 0, pad_r, 0, pad_b))
+        x = attn.attend(swin_linear(x, attn.qkv.weight, attn.qkv.bias, cache=self._forms["qkv"]), self.shift_size)
+        if pad_r or pad_b:
+            x = x[:, :H, :W, :].contiguous()      # proj acts per token: on the cropped map
+        x = swin_linear(x.view(B, L, C), attn.proj.weight, attn.proj.bias, epilogue="residual", aux=shortcut, cache=self._forms["proj"])
+        return swin_mlp(x, self.norm2, self.mlp.fc1, self.mlp.fc2, caches=(self._forms["fc1"], self._forms["fc2"]))
 
     def forward(self, x, mask_matrix=None):
         """x (B, H * W, C) with self.H, self.W set by the layer.  ``mask_matrix`` is accepted for the reference's call and not used: the
@@ -237,6 +477,8 @@ class SwinTransformerBlock(nn.Module):
         B, L, C = x.shape
         H, W, w = self.H, self.W, self.window_size
         assert L == H * W, "input feature has wrong size"
+        if self.fused and x.is_cuda and x.dtype == torch.bfloat16:
+            return self._forward_fused(x)
         shortcut = x
         x = self.norm1(x).view(B, H, W, C)
         pad_r, pad_b = (w - W % w) % w, (w - H % w) % w
@@ -285,6 +527,12 @@ class BasicLayer(nn.Module):
                                  drop_path=drop_path[i] if isinstance(drop_path, (list, tuple)) else drop_path, norm_layer=norm_layer)
             for i in range(depth)])
         self.downsample = downsample(dim=dim, norm_layer=norm_layer) if downsample is not None else None
+
+    def set_fused(self, flag=True):
+        """``fused`` of every block (:class:`SwinTransformerBlock`)"""
+        for blk in self.blocks:
+            blk.fused = bool(flag)
+        return self
 
     def forward(self, x, H, W):
         """x (B, H * W, C) -> (x, H, W, x_down, Wh, Ww) as the reference"""
@@ -374,6 +622,12 @@ class SwinTransformer(nn.Module):
                 m.eval()
                 for p in m.parameters():
                     p.requires_grad = False
+
+    def set_fused(self, flag=True):
+        """``fused`` of every block of every layer (:class:`SwinTransformerBlock`)"""
+        for layer in self.layers:
+            layer.set_fused(flag)
+        return self
 
     def forward_raw(self, x):
         x = self.patch_embed(x)
