@@ -811,6 +811,45 @@ int msda_swin_layernorm_backward_bf16(const uint16_t *dy, const uint16_t *x, con
                                       const uint16_t *add, int tokens, int C, uint16_t *dx, float *dgamma, float *dbeta, void *workspace,
                                       msda_stream_t stream);
 
+/* ---- where the Swin backbone changes layout: the merging norm, the output norms to NCHW, the patch rows (reference
+ * models/richsem/swin_transformer.py:242-277 PatchMerging, :399-434 PatchEmbed, :640-660 the output norms; csrc/swin_stage.hip) -- bf16
+ * storage, fp32 statistics and arithmetic, one rounding per stored element; the formulas of msda_swin_layernorm_* operation for operation
+ * (mean by a division, biased variance as the mean of squared deviations, dgamma / dbeta through the workspace of
+ * msda_swin_layernorm_workspace_bytes in a fixed order): only where a row's elements live changes -------------------------------------
+ * msda_swin_merge_norm_forward_bf16:  x (B, H, W, C) bf16, the map.  Rows (B H2 W2, 4 C), H2 = (H + 1) / 2, W2 = (W + 1) / 2: channel
+ *   q C + c of row (b, i, j) is pixel (2 i + (q & 1), 2 j + (q >> 1)); a pixel outside the map reads as zero and takes part in the
+ *   statistics as a zero.  out (B H2 W2, 4 C) = rnd((row - mean) rstd gamma + beta), gamma, beta (4 C) fp32; mean, rstd (B H2 W2) fp32
+ *   written unless NULL.
+ * msda_swin_merge_norm_backward_bf16:  dy (B H2 W2, 4 C), x the map, mean, rstd, gamma as above.  With xhat and g = dy gamma over the
+ *   gathered row,  dx = rnd(rstd (g - mean_c(g) - xhat mean_c(g xhat)))  stored at the pixel the element came from: dx (B, H, W, C), every
+ *   element written exactly once (nothing pre-zeroed); elements of quadrants outside the map are dropped.  dgamma = sum_rows dy xhat and
+ *   dbeta = sum_rows dy, (4 C) fp32, each may be NULL; a padded element's xhat = (0 - mean) rstd counts in dgamma.  workspace:
+ *   msda_swin_layernorm_workspace_bytes(B H2 W2, 4 C), may be NULL when both are.
+ *   Limits: C a multiple of 32, 4 C <= 4096, B, H, W >= 1 (MSDA_ERR_BAD_DIMS); B H W C and B H2 W2 4 C < 2^31 (MSDA_ERR_TOO_LARGE).
+ * msda_swin_norm_nchw_forward_bf16:  x (B, HW, C) tokens -> out (B, C, HW) = the LayerNorm of every token, stored transposed; mean, rstd
+ *   (B HW) written unless NULL.  HW is arbitrary: a channel row of out may start on any 2-byte boundary (ragged ends are stored
+ *   element by element, the 16-byte chunks of the buffer between them whole).
+ * msda_swin_norm_nchw_backward_bf16:  dy (B, C, HW), x tokens -> dx (B, HW, C) tokens by the row formula above, dgamma, dbeta (C) (64-token
+ *   parts of the B HW tokens, images back to back; workspace: msda_swin_layernorm_workspace_bytes(B HW, C)).
+ *   Limits: C a multiple of 32 in [32, 4096], B, HW >= 1 (MSDA_ERR_BAD_DIMS); B HW C < 2^31 (MSDA_ERR_TOO_LARGE).
+ * msda_swin_patch_rows_bf16:  img (B, Cin, H, W) bf16 -> rows (B Wh Ww, Kp), Wh = ceil(H / ph), Ww = ceil(W / pw), Kp = Cin ph pw rounded
+ *   up to a multiple of 32; column (c ph + dy) pw + dx of row (b, i, j) = img[b, c, i ph + dy, j pw + dx] (the order of a convolution
+ *   weight's flatten(1)); columns past Cin ph pw and pixels past the image are exact zeros.  Pure data movement: no rounding.
+ * msda_swin_patch_rows_backward_bf16:  the inverse, drows (B Wh Ww, Kp) -> dimg (B, Cin, H, W), every element written once; the padding
+ *   is dropped.   Limits: all extents >= 1, Kp <= 8192 (MSDA_ERR_BAD_DIMS); B Cin H W and B Wh Ww Kp < 2^31 (MSDA_ERR_TOO_LARGE).
+ * Alignment (MSDA_ERR_MISALIGNED): the bf16 buffers 16 bytes (img and dimg: 2), the fp32 ones 4.  Every check comes before any launch; no
+ * call allocates, synchronises or uses atomics; two calls give the same bits. */
+int msda_swin_merge_norm_forward_bf16(const uint16_t *x, const float *gamma, const float *beta, float eps, int B, int H, int W, int C,
+                                      uint16_t *out, float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_merge_norm_backward_bf16(const uint16_t *dy, const uint16_t *x, const float *mean, const float *rstd, const float *gamma, int B,
+                                       int H, int W, int C, uint16_t *dx, float *dgamma, float *dbeta, void *workspace, msda_stream_t stream);
+int msda_swin_norm_nchw_forward_bf16(const uint16_t *x, const float *gamma, const float *beta, float eps, int B, int HW, int C, uint16_t *out,
+                                     float *mean, float *rstd, msda_stream_t stream);
+int msda_swin_norm_nchw_backward_bf16(const uint16_t *dy, const uint16_t *x, const float *mean, const float *rstd, const float *gamma, int B,
+                                      int HW, int C, uint16_t *dx, float *dgamma, float *dbeta, void *workspace, msda_stream_t stream);
+int msda_swin_patch_rows_bf16(const uint16_t *img, int B, int Cin, int H, int W, int ph, int pw, uint16_t *rows, msda_stream_t stream);
+int msda_swin_patch_rows_backward_bf16(const uint16_t *drows, int B, int Cin, int H, int W, int ph, int pw, uint16_t *dimg, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

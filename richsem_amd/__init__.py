@@ -23,8 +23,8 @@ def __getattr__(name):      # PostProcess is exported from the package without i
     if name in ("denoising_queries", "dn_capacity", "DenoisingQueriesFunction"):      # the denoising queries from the counts on the device (dn.py)
         from . import dn
         return getattr(dn, name)
-    if name in ("window_attention", "swin_linear", "swin_layernorm", "swin_mlp", "WindowAttention", "SwinTransformerBlock", "PatchMerging",
-                "BasicLayer", "PatchEmbed", "SwinTransformer"):      # the Swin backbone and its kernels (swin.py)
+    if name in ("window_attention", "swin_linear", "swin_layernorm", "swin_mlp", "swin_merge_norm", "swin_norm_nchw", "swin_patch_rows",
+                "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer"):      # the Swin backbone and its kernels (swin.py)
         from . import swin
         return getattr(swin, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -30,6 +30,7 @@
 
 #include "mfma_common.h"
 #include "msda_host.h"
+#include "swin_rows.h"
 
 namespace {
 
@@ -38,10 +39,6 @@ constexpr int kBM = 128;            // tokens of a workgroup's tile
 constexpr int kBK = 64;             // K block
 constexpr int kLd = kBK;            // LDS row stride in shorts (128 bytes: two rows per 256-byte bank row)
 constexpr int kMaxWidth = 8192;     // linear: K and N
-constexpr int kMaxC = 4096;         // LayerNorm
-constexpr int kLnRows = 4;          // tokens (waves) per workgroup of the row kernels
-constexpr int kPartRows = 64;       // tokens per partial row of dgamma / dbeta
-constexpr int kColGroup = 128;      // channels per workgroup of the column kernel
 
 constexpr float kRsqrt2 = 0.70710678118654752f;
 constexpr float kRsqrt2Pi = 0.39894228040143268f;
@@ -50,19 +47,6 @@ __device__ __forceinline__ float norm_cdf(float x) { return 0.5f * erfcf(-x * kR
 __device__ __forceinline__ float gelu(float x) { return x * norm_cdf(x); }
 __device__ __forceinline__ float gelu_grad(float x) { return norm_cdf(x) + x * (kRsqrt2Pi * __expf(-0.5f * x * x)); }
 __device__ __forceinline__ float round_bf16(float v) { return bf16_lo(pack_bf16(v, 0.f)); }
-
-__device__ __forceinline__ void unpack8(u32x4 u, float (&v)[8])
-{
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        v[2 * i] = bf16_lo(u[i]);
-        v[2 * i + 1] = bf16_hi(u[i]);
-    }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8])
-{
-    return (u32x4){pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7])};
-}
 
 // ---- linear ----------------------------------------------------------------------------------------------------------------------------
 // The 16-byte slot `ks` (0..7) of LDS row `row` lives at slot ks ^ swizzle(row).  ds_read_b128 serves lanes {0-3, 12-15, 20-27} (and the
@@ -214,16 +198,7 @@ void launch_linear(int epilogue, dim3 grid, hipStream_t stream, const uint16_t *
     }
 }
 
-// ---- LayerNorm -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-constexpr int kLnChunks = kMaxC / 8 / 64;      // 16-byte chunks of a row per lane, at most
-
+// ---- LayerNorm (limits, unpack8 / pack8, wave_sum and the last stage of dgamma / dbeta: swin_rows.h) ---------------------------------------
 __global__ __launch_bounds__(kLnRows * 64) void swin_ln_fwd_kernel(const uint16_t *__restrict__ x, const float *__restrict__ gamma,
                                                                    const float *__restrict__ beta, float eps, int tokens, int C,
                                                                    uint16_t *__restrict__ out, float *__restrict__ mean, float *__restrict__ rstd)
@@ -346,26 +321,6 @@ __global__ __launch_bounds__(256) void swin_ln_bwd_cols_kernel(const uint16_t *_
         dst[C] = r[2];
         dst[C + 1] = r[3];
     }
-}
-
-__global__ __launch_bounds__(256) void swin_ln_bwd_sum_kernel(const float *__restrict__ workspace, int parts, int C, float *__restrict__ dgamma,
-                                                              float *__restrict__ dbeta)
-{
-    const int ch = blockIdx.x * 256 + threadIdx.x;
-    if (ch >= C) return;
-    float *dst = blockIdx.y ? dbeta : dgamma;
-    if (!dst) return;
-    const float *src = workspace + (size_t)blockIdx.y * C + ch;
-    float s = 0.f;
-    for (int p = 0; p < parts; ++p) s += src[(size_t)p * 2 * C];
-    dst[ch] = s;
-}
-
-int ln_dims(int tokens, int C)
-{
-    if (tokens < 1 || C < 32 || C > kMaxC || C % 32) return MSDA_ERR_BAD_DIMS;
-    if ((int64_t)tokens * C >= (int64_t)1 << 31) return MSDA_ERR_TOO_LARGE;
-    return MSDA_OK;
 }
 
 }  // namespace

@@ -17,6 +17,13 @@ in the state dict).  With it a bf16 device tensor takes :func:`swin_layernorm`, 
 general width with fused epilogues and a LayerNorm of general width (csrc/swin_block_mfma.hip; C ABI ``msda_swin_linear_bf16``,
 ``msda_swin_layernorm_*``).  :func:`swin_mlp` is ONE autograd function for ``x + fc2(GELU(fc1(norm(x))))`` that saves the pre-activation
 ``u`` and regenerates the hidden activation in its backward.  CPU, fp32 and fp64 tensors run the torch formula with ``fused`` set too.
+
+Where the backbone changes layout -- the patch embedding, the three PatchMerging layers and the output norms -- a second switch,
+``SwinTransformer.set_fused_stages`` (``PatchEmbed.fused``, ``PatchMerging.fused``, ``SwinTransformer.fused_stages``; off by default
+like ``fused``), puts the index arithmetic into kernels (csrc/swin_stage.hip; C ABI ``msda_swin_merge_norm_*``, ``msda_swin_norm_nchw_*``,
+``msda_swin_patch_rows_*``): :func:`swin_merge_norm` is the LayerNorm of the 2 x 2 gathered rows read straight from the map,
+:func:`swin_norm_nchw` a LayerNorm stored as (B, C, H, W), :func:`swin_patch_rows` the image as rows of patches for
+``msda_swin_linear_bf16``.  ``set_fused`` keeps meaning the blocks only.
 """
 import ctypes
 
@@ -27,7 +34,8 @@ import torch.nn.functional as F
 from . import _lib
 from .param_cache import VersionCache
 
-__all__ = ["window_attention", "window_attention_torch", "swin_linear", "swin_layernorm", "swin_mlp", "WindowAttention",
+__all__ = ["window_attention", "window_attention_torch", "swin_linear", "swin_layernorm", "swin_mlp", "swin_merge_norm", "swin_norm_nchw",
+           "swin_patch_rows", "WindowAttention",
            "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer", "Mlp", "DropPath"]
 
 HEAD_DIM = 32      # what the kernels are built for (every Swin variant of the reference: swin_transformer.py:676-710)
@@ -241,23 +249,25 @@ def _wgrad(ctx, iw, ib, dy2, x2, weight_dtype, bias_dtype):
 class _SwinLinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, aux, forms):
-        K = weight.shape[1]
+        K = forms["w16"].shape[1]      # (weight.shape[1], or the padded width of a convolution weight's form: PatchEmbed)
         x2 = _rows(x, K, "swin_linear")
         aux2 = _rows(aux, weight.shape[0], "swin_linear (aux)") if aux is not None else None
         out, _ = linear_kernel(x2, forms["w16"], forms["b32"], EPI_RESIDUAL if aux is not None else EPI_BIAS, aux2)
         ctx.save_for_backward(x2)
         ctx.forms = forms
-        ctx.meta = (x.shape, aux.shape if aux is not None else None, weight.dtype, bias.dtype if bias is not None else None)
+        ctx.meta = (x.shape, aux.shape if aux is not None else None, weight.dtype, bias.dtype if bias is not None else None, weight.shape)
         return out.view(x.shape[:-1] + (weight.shape[0],))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x2, = ctx.saved_tensors
-        shape, aux_shape, wdt, bdt = ctx.meta
+        shape, aux_shape, wdt, bdt, wshape = ctx.meta
         dy2 = _rows(dy, ctx.forms["w16"].shape[0], "swin_linear (gradient)")
         dx = linear_kernel(dy2, ctx.forms["wt16"])[0].view(shape) if ctx.needs_input_grad[0] else None
         dw, db = _wgrad(ctx, 1, 2, dy2, x2, wdt, bdt)
+        if dw is not None and dw.shape != wshape:      # the columns of padding are dropped
+            dw = dw[:, :wshape.numel() // wshape[0]].reshape(wshape)
         return dx, dw, db, dy.reshape(aux_shape) if ctx.needs_input_grad[3] else None, None
 
 
@@ -341,6 +351,191 @@ def swin_mlp(x, norm, fc1, fc2, caches=(None, None)):
         raise RuntimeError("swin_mlp: norm must be an nn.LayerNorm with weight and bias")
     return _SwinMlpFunction.apply(x, norm.weight, norm.bias, float(norm.eps), fc1.weight, fc1.bias, fc2.weight, fc2.bias,
                                   _forms(caches[0], fc1.weight, fc1.bias), _forms(caches[1], fc2.weight, fc2.bias))
+
+
+# ---- the stage boundaries: merging norm, output norm to NCHW, patch rows --------------------------------------------------------------------
+def _tokens(x, H, W, what):
+    if not x.is_cuda:
+        raise RuntimeError("Not implemented on the CPU")
+    if x.dtype != BF16 or x.dim() != 3 or x.shape[1] != H * W:
+        raise RuntimeError(f"{what}: bfloat16 (B, {H} * {W}, C), got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def _affine(weight, bias, width, what):
+    if weight is None or bias is None or tuple(weight.shape) != (width,) or tuple(bias.shape) != (width,):
+        raise RuntimeError(f"{what}: weight and bias ({width})")
+    return _f32(weight), _f32(bias)
+
+
+def merge_norm_kernel(x, H, W, g32, b32, eps, want_stats=True):
+    """``msda_swin_merge_norm_forward_bf16``: x (B, H * W, C) bf16 contiguous -> (out (B, H2 * W2, 4 C), mean, rstd)"""
+    B, _, C = x.shape
+    rows = ((H + 1) // 2) * ((W + 1) // 2)
+    out = torch.empty((B, rows, 4 * C), dtype=BF16, device=x.device)
+    mean = torch.empty(B * rows, dtype=torch.float32, device=x.device) if want_stats else None
+    rstd = torch.empty_like(mean) if want_stats else None
+    with _lib.on_device(x.device):
+        _lib.check(_lib.load().msda_swin_merge_norm_forward_bf16(x.data_ptr(), g32.data_ptr(), b32.data_ptr(), eps, B, H, W, C, out.data_ptr(),
+                                                                 _ptr(mean), _ptr(rstd), _lib.raw_stream(x.device)))
+    return out, mean, rstd
+
+
+def merge_norm_backward_kernel(dy, x, H, W, mean, rstd, g32, want_gamma=True, want_beta=True):
+    """``msda_swin_merge_norm_backward_bf16``: dy (B, H2 * W2, 4 C), x (B, H * W, C) -> (dx as x, dgamma, dbeta (4 C) float32 or None)"""
+    B, _, C = x.shape
+    dx = torch.empty_like(x)
+    dg = torch.empty(4 * C, dtype=torch.float32, device=x.device) if want_gamma else None
+    db = torch.empty(4 * C, dtype=torch.float32, device=x.device) if want_beta else None
+    ws = None
+    if want_gamma or want_beta:
+        ws = torch.empty(layernorm_workspace_bytes(mean.numel(), 4 * C) // 4, dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        _lib.check(_lib.load().msda_swin_merge_norm_backward_bf16(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
+                                                                  B, H, W, C, dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(ws),
+                                                                  _lib.raw_stream(x.device)))
+    return dx, dg, db
+
+
+def norm_nchw_kernel(x, g32, b32, eps, want_stats=True):
+    """``msda_swin_norm_nchw_forward_bf16``: x (B, HW, C) bf16 contiguous -> (out (B, C, HW), mean, rstd)"""
+    B, HW, C = x.shape
+    out = torch.empty((B, C, HW), dtype=BF16, device=x.device)
+    mean = torch.empty(B * HW, dtype=torch.float32, device=x.device) if want_stats else None
+    rstd = torch.empty_like(mean) if want_stats else None
+    with _lib.on_device(x.device):
+        _lib.check(_lib.load().msda_swin_norm_nchw_forward_bf16(x.data_ptr(), g32.data_ptr(), b32.data_ptr(), eps, B, HW, C, out.data_ptr(),
+                                                                _ptr(mean), _ptr(rstd), _lib.raw_stream(x.device)))
+    return out, mean, rstd
+
+
+def norm_nchw_backward_kernel(dy, x, mean, rstd, g32, want_gamma=True, want_beta=True):
+    """``msda_swin_norm_nchw_backward_bf16``: dy (B, C, HW), x (B, HW, C) -> (dx as x, dgamma, dbeta (C) float32 or None)"""
+    B, HW, C = x.shape
+    dx = torch.empty_like(x)
+    dg = torch.empty(C, dtype=torch.float32, device=x.device) if want_gamma else None
+    db = torch.empty(C, dtype=torch.float32, device=x.device) if want_beta else None
+    ws = torch.empty(layernorm_workspace_bytes(B * HW, C) // 4, dtype=torch.float32, device=x.device) if want_gamma or want_beta else None
+    with _lib.on_device(x.device):
+        _lib.check(_lib.load().msda_swin_norm_nchw_backward_bf16(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
+                                                                 B, HW, C, dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(ws),
+                                                                 _lib.raw_stream(x.device)))
+    return dx, dg, db
+
+
+def patch_grid(H, W, patch_size):
+    """-> (Wh, Ww) = (ceil(H / ph), ceil(W / pw))"""
+    ph, pw = _pair(patch_size)
+    return -(-H // ph), -(-W // pw)
+
+
+def patch_width(in_chans, patch_size):
+    """Kp: in_chans ph pw rounded up to a multiple of 32"""
+    ph, pw = _pair(patch_size)
+    return -(-in_chans * ph * pw // 32) * 32
+
+
+class _SwinMergeNormFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, H, W, weight, bias, eps):
+        x = _tokens(x, H, W, "swin_merge_norm")
+        g32, b32 = _affine(weight, bias, 4 * x.shape[2], "swin_merge_norm")
+        need = any(ctx.needs_input_grad)
+        out, mean, rstd = merge_norm_kernel(x, H, W, g32, b32, eps, want_stats=need)
+        if need:
+            ctx.save_for_backward(x, mean, rstd, g32)
+            ctx.meta = (H, W, weight.dtype, bias.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, mean, rstd, g32 = ctx.saved_tensors
+        H, W, wdt, bdt = ctx.meta
+        dx, dg, db = merge_norm_backward_kernel(dy.contiguous(), x, H, W, mean, rstd, g32, want_gamma=ctx.needs_input_grad[3],
+                                                want_beta=ctx.needs_input_grad[4])
+        return (dx if ctx.needs_input_grad[0] else None, None, None, dg.to(wdt) if dg is not None else None,
+                db.to(bdt) if db is not None else None, None)
+
+
+def swin_merge_norm(x, H, W, weight, bias, eps=1e-5):
+    """The norm of PatchMerging on ``msda_swin_merge_norm_*``: x (B, H * W, C) bfloat16 on the device, C a multiple of 32 up to 1024,
+    weight and bias (4 C) -> (B, H2 * W2, 4 C) bfloat16 with H2 = (H + 1) // 2, W2 = (W + 1) // 2: the LayerNorm of the rows whose channel
+    q C + c is pixel (2 i + (q & 1), 2 j + (q >> 1)), pixels outside the map being zeros that take part in the statistics (the reference
+    pads before the norm).  Saves x and the fp32 statistics (nothing under ``no_grad``); gradients in the parameters' dtypes."""
+    return _SwinMergeNormFunction.apply(x, int(H), int(W), weight, bias, float(eps))
+
+
+class _SwinNormNchwFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, H, W, weight, bias, eps):
+        x = _tokens(x, H, W, "swin_norm_nchw")
+        g32, b32 = _affine(weight, bias, x.shape[2], "swin_norm_nchw")
+        need = any(ctx.needs_input_grad)
+        out, mean, rstd = norm_nchw_kernel(x, g32, b32, eps, want_stats=need)
+        if need:
+            ctx.save_for_backward(x, mean, rstd, g32)
+            ctx.meta = (weight.dtype, bias.dtype)
+        return out.view(x.shape[0], x.shape[2], H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, mean, rstd, g32 = ctx.saved_tensors
+        wdt, bdt = ctx.meta
+        dx, dg, db = norm_nchw_backward_kernel(dy.contiguous(), x, mean, rstd, g32, want_gamma=ctx.needs_input_grad[3],
+                                               want_beta=ctx.needs_input_grad[4])
+        return (dx if ctx.needs_input_grad[0] else None, None, None, dg.to(wdt) if dg is not None else None,
+                db.to(bdt) if db is not None else None, None)
+
+
+def swin_norm_nchw(x, H, W, weight, bias, eps=1e-5):
+    """An output norm of the backbone on ``msda_swin_norm_nchw_*``: x (B, H * W, C) bfloat16 on the device, C a multiple of 32 up to 4096,
+    weight and bias (C) -> (B, C, H, W) bfloat16 contiguous: LayerNorm over C, stored transposed (any H * W).  Saves x and the fp32
+    statistics (nothing under ``no_grad``); gradients in the parameters' dtypes."""
+    return _SwinNormNchwFunction.apply(x, int(H), int(W), weight, bias, float(eps))
+
+
+class _SwinPatchRowsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, ph, pw):
+        if not img.is_cuda:
+            raise RuntimeError("Not implemented on the CPU")
+        if img.dtype != BF16 or img.dim() != 4:
+            raise RuntimeError(f"swin_patch_rows: bfloat16 (B, Cin, H, W), got {img.dtype} {tuple(img.shape)}")
+        img = img.contiguous()
+        B, Cin, H, W = img.shape
+        Wh, Ww = patch_grid(H, W, (ph, pw))
+        rows = torch.empty((B, Wh * Ww, patch_width(Cin, (ph, pw))), dtype=BF16, device=img.device)
+        with _lib.on_device(img.device):
+            _lib.check(_lib.load().msda_swin_patch_rows_bf16(img.data_ptr(), B, Cin, H, W, ph, pw, rows.data_ptr(), _lib.raw_stream(img.device)))
+        ctx.meta = (tuple(img.shape), ph, pw)
+        return rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, drows):
+        (B, Cin, H, W), ph, pw = ctx.meta
+        drows = drows.contiguous()
+        dimg = torch.empty((B, Cin, H, W), dtype=BF16, device=drows.device)
+        with _lib.on_device(drows.device):
+            _lib.check(_lib.load().msda_swin_patch_rows_backward_bf16(drows.data_ptr(), B, Cin, H, W, ph, pw, dimg.data_ptr(),
+                                                                      _lib.raw_stream(drows.device)))
+        return dimg, None, None
+
+
+def swin_patch_rows(img, patch_size):
+    """The image as rows of patches on ``msda_swin_patch_rows_*``: img (B, Cin, H, W) bfloat16 on the device -> (B, Wh * Ww, Kp) bfloat16,
+    Wh = ceil(H / ph), Ww = ceil(W / pw), Kp = Cin ph pw rounded up to a multiple of 32 (at most 8192); column (c ph + dy) pw + dx is the
+    image element (the order of ``proj.weight.flatten(1)``), columns of padding and pixels past the image are exact zeros.  Saves nothing;
+    the backward (run only when the image needs a gradient) is the inverse movement."""
+    ph, pw = _pair(patch_size)
+    return _SwinPatchRowsFunction.apply(img, int(ph), int(pw))
+
+
+def _need_layernorm(norm, what):
+    if not isinstance(norm, nn.LayerNorm) or not norm.elementwise_affine or norm.bias is None:
+        raise NotImplementedError(f"richsem_amd.swin: the fused {what} needs an nn.LayerNorm with weight and bias, got {type(norm).__name__}")
 
 
 # ---- the mirrors ------------------------------------------------------------------------------------------------------------------------
@@ -492,15 +687,26 @@ class SwinTransformerBlock(nn.Module):
 
 
 class PatchMerging(nn.Module):
+    """The reference's layer.  ``fused`` (a plain attribute, False by default; ``SwinTransformer.set_fused_stages``): a bf16 device tensor
+    takes :func:`swin_merge_norm` -- pad, 2 x 2 gather and LayerNorm in one pass over the map -- and :func:`swin_linear` for the reduction,
+    and never falls back: a ``norm_layer`` other than nn.LayerNorm or a width outside the kernels' limits raises."""
+
+    fused = False
+
     def __init__(self, dim, norm_layer=nn.LayerNorm):
         super().__init__()
         self.dim = dim
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
         self.norm = norm_layer(4 * dim)
+        self._forms = VersionCache()      # derived weight forms of the fused path
 
     def forward(self, x, H, W):
         B, L, C = x.shape
         assert L == H * W, "input feature has wrong size"
+        if self.fused and x.is_cuda and x.dtype == torch.bfloat16:
+            _need_layernorm(self.norm, "PatchMerging")
+            xn = swin_merge_norm(x, H, W, self.norm.weight, self.norm.bias, self.norm.eps)
+            return swin_linear(xn, self.reduction.weight, None, cache=self._forms)
         x = x.view(B, H, W, C)
         if H % 2 or W % 2:
             x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
@@ -545,6 +751,14 @@ class BasicLayer(nn.Module):
 
 
 class PatchEmbed(nn.Module):
+    """The reference's layer: ``forward(x)`` -> (B, embed_dim, Wh, Ww); ``tokens(x)`` -> (x (B, Wh * Ww, embed_dim), Wh, Ww), the same
+    numbers in the layout the first block reads.  ``fused`` (a plain attribute, False by default; ``SwinTransformer.set_fused_stages``): a
+    bf16 device image takes :func:`swin_patch_rows`, the projection as :func:`swin_linear` on the zero-padded (embed_dim, Kp) form of the
+    convolution weight, and :func:`swin_layernorm`; it never falls back (a ``norm_layer`` other than nn.LayerNorm, or an ``embed_dim`` that
+    is no multiple of 32, raises)."""
+
+    fused = False
+
     def __init__(self, patch_size=4, in_chans=3, embed_dim=96, norm_layer=None):
         super().__init__()
         self.patch_size = _pair(patch_size)
@@ -552,8 +766,45 @@ class PatchEmbed(nn.Module):
         self.embed_dim = embed_dim
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.patch_size)
         self.norm = norm_layer(embed_dim) if norm_layer is not None else None
+        self._forms = VersionCache()      # the zero-padded (embed_dim, Kp) weight forms of the fused path
+
+    def _padded_forms(self):
+        w, b = self.proj.weight, self.proj.bias
+
+        def build():
+            flat = w.detach().to(BF16).flatten(1)
+            return linear_forms(F.pad(flat, (0, patch_width(self.in_chans, self.patch_size) - flat.shape[1])), b)
+        return self._forms.get([w] + ([b] if b is not None else []), build)
+
+    def _fused_path(self, x):
+        return self.fused and x.is_cuda and x.dtype == torch.bfloat16
+
+    def tokens(self, x):
+        """x (B, in_chans, H, W) -> (tokens (B, Wh * Ww, embed_dim), Wh, Ww): projection and norm, without the NCHW detour"""
+        if self._fused_path(x):
+            if self.norm is not None:
+                _need_layernorm(self.norm, "PatchEmbed")
+            Wh, Ww = patch_grid(x.shape[2], x.shape[3], self.patch_size)
+            t = _SwinLinearFunction.apply(swin_patch_rows(x, self.patch_size), self.proj.weight, self.proj.bias, None, self._padded_forms())
+            if self.norm is not None:
+                t = swin_layernorm(t, self.norm.weight, self.norm.bias, self.norm.eps)
+            return t, Wh, Ww
+        x = self._project(x)
+        Wh, Ww = x.shape[2], x.shape[3]
+        x = x.flatten(2).transpose(1, 2)
+        return (self.norm(x) if self.norm is not None else x), Wh, Ww
+
+    def _project(self, x):
+        _, _, H, W = x.shape
+        ph, pw = self.patch_size
+        if W % pw or H % ph:
+            x = F.pad(x, (0, (pw - W % pw) % pw, 0, (ph - H % ph) % ph))
+        return self.proj(x)
 
     def forward(self, x):
+        if self._fused_path(x):
+            t, Wh, Ww = self.tokens(x)
+            return t.transpose(1, 2).reshape(-1, self.embed_dim, Wh, Ww)
         _, _, H, W = x.shape
         ph, pw = self.patch_size
         if W % pw or H % ph:
@@ -567,7 +818,11 @@ class PatchEmbed(nn.Module):
 
 class SwinTransformer(nn.Module):
     """``forward_raw(images)`` -> the tuple of (B, C_i, H_i, W_i) features of ``out_indices``; ``forward(images, mask)`` -> a list of
-    (feature, mask) pairs with the padding mask (B, H, W) bool interpolated to each level as the reference's NestedTensor wrapper does."""
+    (feature, mask) pairs with the padding mask (B, H, W) bool interpolated to each level as the reference's NestedTensor wrapper does.
+    ``fused_stages`` (a plain attribute, False by default; :meth:`set_fused_stages`): on a bf16 device tensor the output norms take
+    :func:`swin_norm_nchw` and, with ``ape`` off, the patch embedding's tokens go straight to the first layer."""
+
+    fused_stages = False
 
     def __init__(self, pretrain_img_size=224, patch_size=4, in_chans=3, embed_dim=96, depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24),
                  window_size=7, mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.2,
@@ -629,17 +884,36 @@ class SwinTransformer(nn.Module):
             layer.set_fused(flag)
         return self
 
+    def set_fused_stages(self, flag=True):
+        """the stage boundaries' switch: ``fused`` of the patch embedding and of every layer's ``downsample`` and ``fused_stages`` (the
+        output norms).  The blocks' ``fused`` is :meth:`set_fused`'s alone."""
+        flag = bool(flag)
+        self.patch_embed.fused = flag
+        for layer in self.layers:
+            if layer.downsample is not None:
+                layer.downsample.fused = flag
+        self.fused_stages = flag
+        return self
+
     def forward_raw(self, x):
-        x = self.patch_embed(x)
-        Wh, Ww = x.shape[2], x.shape[3]
-        if self.ape:
-            x = x + F.interpolate(self.absolute_pos_embed, size=(Wh, Ww), mode="bicubic")
-        x = x.flatten(2).transpose(1, 2)
+        if self.fused_stages and not self.ape:      # the tokens go straight to the first layer
+            x, Wh, Ww = self.patch_embed.tokens(x)
+        else:
+            x = self.patch_embed(x)
+            Wh, Ww = x.shape[2], x.shape[3]
+            if self.ape:
+                x = x + F.interpolate(self.absolute_pos_embed, size=(Wh, Ww), mode="bicubic")
+            x = x.flatten(2).transpose(1, 2)
         outs = []
         for i, layer in enumerate(self.layers):
             x_out, H, W, x, Wh, Ww = layer(x, Wh, Ww)
             if i in self.out_indices:
-                x_out = getattr(self, f"norm{i}")(x_out)
+                norm = getattr(self, f"norm{i}")
+                if self.fused_stages and x_out.is_cuda and x_out.dtype == torch.bfloat16:
+                    _need_layernorm(norm, "output norm")
+                    outs.append(swin_norm_nchw(x_out, H, W, norm.weight, norm.bias, norm.eps))
+                    continue
+                x_out = norm(x_out)
                 outs.append(x_out.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2).contiguous())
         return tuple(outs)
 
