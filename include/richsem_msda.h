@@ -850,6 +850,34 @@ int msda_swin_norm_nchw_backward_bf16(const uint16_t *dy, const uint16_t *x, con
 int msda_swin_patch_rows_bf16(const uint16_t *img, int B, int Cin, int H, int W, int ph, int pw, uint16_t *rows, msda_stream_t stream);
 int msda_swin_patch_rows_backward_bf16(const uint16_t *drows, int B, int Cin, int H, int W, int ph, int pw, uint16_t *dimg, msda_stream_t stream);
 
+/* ---- what a ConvNeXt block adds to the Swin kernels: depthwise 7 x 7 convolution and layer scale (reference
+ * models/richsem/convnext.py:18-53 Block; csrc/convnext_dw.hip) -- the map is channels-last (B, H, W, C) bf16 ("map layout"), fp32
+ * arithmetic and accumulation, one rounding per stored element --------------------------------------------------------------------------
+ * msda_dwconv7_bf16:  out[b,y,x,c] = rnd(add[b,y,x,c] + bias[c] + sum_{ky,kx} w[t(ky,kx), c] x[b, y+ky-3, x+kx-3, c]),  ky, kx in 0..6;
+ *   a pixel outside the image reads as zero, per image (a halo never reads the neighbouring image of the batch).  x, out, add (B, H, W, C)
+ *   bf16, add may be NULL; w (49, C) fp32, tap-major; bias (C) fp32 or NULL.  t = 7 ky + kx for flip = 0, t = 7 (6 - ky) + (6 - kx) for
+ *   flip = 1: with flip = 1, bias = NULL and add = the residual stream's gradient the call is the input gradient
+ *   dinput = rnd(dout + dwconv^T(dy)), rounded once.
+ * msda_dwconv7_wgrad_bf16:  dw[7 ky + kx, c] = sum_{b,y,x} dy[b,y,x,c] x[b, y+ky-3, x+kx-3, c], (49, C) fp32;  dbias[c] = sum_{b,y,x} dy,
+ *   (C) fp32 or NULL.  Summed as per-workgroup partial rows in `workspace` (msda_dwconv7_workspace_bytes, contents irrelevant on entry),
+ *   then one pass adds the parts in ascending order; the number of parts depends on the shape only.
+ * msda_layer_scale_forward_bf16:  out = rnd(res + gamma[c] z);  z, res, out (tokens, C) bf16, gamma (C) fp32.
+ * msda_layer_scale_backward_bf16:  dz = rnd(gamma[c] dout), (tokens, C) bf16;  dgamma[c] = sum_t dout z, (C) fp32 or NULL (then z and
+ *   workspace may be NULL too), summed as parts of 64 k tokens (k = 1 up to 16384 tokens, then the smallest that keeps the parts at 256 or
+ *   fewer) through `workspace` (msda_swin_layernorm_workspace_bytes(tokens, C), contents irrelevant on entry) in a fixed order.
+ * Limits: C a multiple of 32 in [32, 4096], B, H, W, tokens >= 1, flip 0 or 1 (MSDA_ERR_BAD_DIMS); B H W C and tokens C < 2^31
+ * (MSDA_ERR_TOO_LARGE); the bf16 buffers 16-byte aligned, the fp32 ones 4 (MSDA_ERR_MISALIGNED).  Every check comes before any launch; no
+ * call allocates, synchronises or uses atomics; two calls give the same bits. */
+int msda_dwconv7_bf16(const uint16_t *x, const float *w, const float *bias, const uint16_t *add, int flip, int B, int H, int W, int C,
+                      uint16_t *out, msda_stream_t stream);
+int msda_dwconv7_workspace_bytes(int B, int H, int W, int C, int64_t *bytes);
+int msda_dwconv7_wgrad_bf16(const uint16_t *dy, const uint16_t *x, int B, int H, int W, int C, float *dw, float *dbias, void *workspace,
+                            msda_stream_t stream);
+int msda_layer_scale_forward_bf16(const uint16_t *z, const float *gamma, const uint16_t *res, int tokens, int C, uint16_t *out,
+                                  msda_stream_t stream);
+int msda_layer_scale_backward_bf16(const uint16_t *dout, const uint16_t *z, const float *gamma, int tokens, int C, uint16_t *dz, float *dgamma,
+                                   void *workspace, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

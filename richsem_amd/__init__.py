@@ -27,6 +27,9 @@ def __getattr__(name):      # PostProcess is exported from the package without i
                 "WindowAttention", "SwinTransformerBlock", "PatchMerging", "BasicLayer", "PatchEmbed", "SwinTransformer"):      # the Swin backbone and its kernels (swin.py)
         from . import swin
         return getattr(swin, name)
+    if name in ("dwconv7", "layer_scale", "convnext_block", "ConvNeXt", "build_convnext"):      # the ConvNeXt backbone and its kernels (convnext.py)
+        from . import convnext
+        return getattr(convnext, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
