@@ -878,6 +878,38 @@ int msda_layer_scale_forward_bf16(const uint16_t *z, const float *gamma, const u
 int msda_layer_scale_backward_bf16(const uint16_t *dout, const uint16_t *z, const float *gamma, int tokens, int C, uint16_t *dz, float *dgamma,
                                    void *workspace, msda_stream_t stream);
 
+/* ---- the context aggregation of a FocalNet block (reference models/richsem/focal.py:84-110 FocalModulation.forward;
+ * csrc/focalnet_ctx.hip, whose header holds the formulas and the rounding points) -- channels-last bf16 maps, fp32 arithmetic ----------------
+ * L = focal level in 1..4, K_l = window + 2 l, every K_l in {3, 5, 7, 9}; s = 1 / (L + 1) with normalize = 1, else 1.  n = B H W C.
+ * ctx0 (B, H, W, C) bf16 with ld0 elements per pixel and gates (B, H, W, L + 1) bf16 with ldg elements per pixel are read in place (the
+ * output rows of the block's `f`); w fp32, tap-major (K_l K_l, C), level after level (sum K_l^2 rows); dw likewise.
+ * msda_fmod_context_forward_bf16:  u (L, B, H, W, C) bf16: u_l = rnd(dwconv_{K_l}(ctx_{l-1})), ctx_l = GELU(u_l) of the stored u_l (as the
+ *   input of the next convolution: rounded to bf16), zero padding per image;  mg (2, B, C) fp32: m = mean over the image of ctx_{L-1} and
+ *   g = GELU(m);  A (B, H, W, C) bf16 = rnd(s (sum_{l<L} gate_l ctx_l + gate_L g)).
+ * msda_fmod_context_backward_bf16:  from dA (B, H, W, C) bf16 and the forward's u, mg:  du (L, B, H, W, C) bf16, the gradients of the
+ *   pre-activations;  dctx0 (ldd0 elements per pixel) and dgates (L + 1 per pixel, lddg elements per pixel) bf16, written in place into
+ *   wider rows;  dw fp32 or NULL (then no weight gradient is formed).  Reductions run over per-workgroup parts in `workspace`, added in
+ *   ascending order.
+ * msda_fmod_workspace_bytes: the size of `workspace` for either call (contents irrelevant on entry).
+ * msda_fmod_modulate_forward_bf16:  out = rnd(q mod);  q (tokens, C) with ldq elements per token, mod and out dense.
+ * msda_fmod_modulate_backward_bf16:  dq = rnd(dout mod) (lddq elements per token), dmod = rnd(dout q).
+ * Limits: C a multiple of 32 in [32, 4096], B, H, W, tokens >= 1, L and window as above, normalize 0 or 1, ld0, ldd0, ldq, lddq multiples
+ * of 8 and >= C, ldg, lddg >= L + 1 (MSDA_ERR_BAD_DIMS); n and tokens C < 2^31 (MSDA_ERR_TOO_LARGE); the bf16 maps 16-byte aligned, gates
+ * 2, the fp32 buffers 4 (MSDA_ERR_MISALIGNED).  Every check comes before any launch; no call allocates, synchronises or uses atomics; two
+ * calls give the same bits. */
+int msda_fmod_workspace_bytes(int B, int H, int W, int C, int64_t *bytes);
+int msda_fmod_context_forward_bf16(const uint16_t *ctx0, int64_t ld0, const uint16_t *gates, int64_t ldg, const float *w, int B, int H, int W,
+                                   int C, int L, int window, int normalize, uint16_t *u, float *mg, uint16_t *A, void *workspace,
+                                   msda_stream_t stream);
+int msda_fmod_context_backward_bf16(const uint16_t *dA, const uint16_t *ctx0, int64_t ld0, const uint16_t *gates, int64_t ldg, const float *w,
+                                    const uint16_t *u, const float *mg, int B, int H, int W, int C, int L, int window, int normalize,
+                                    uint16_t *du, uint16_t *dctx0, int64_t ldd0, uint16_t *dgates, int64_t lddg, float *dw, void *workspace,
+                                    msda_stream_t stream);
+int msda_fmod_modulate_forward_bf16(const uint16_t *q, int64_t ldq, const uint16_t *mod, int64_t tokens, int C, uint16_t *out,
+                                    msda_stream_t stream);
+int msda_fmod_modulate_backward_bf16(const uint16_t *dout, const uint16_t *q, int64_t ldq, const uint16_t *mod, int64_t tokens, int C,
+                                     uint16_t *dq, int64_t lddq, uint16_t *dmod, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

@@ -30,6 +30,9 @@ def __getattr__(name):      # PostProcess is exported from the package without i
     if name in ("dwconv7", "layer_scale", "convnext_block", "ConvNeXt", "build_convnext"):      # the ConvNeXt backbone and its kernels (convnext.py)
         from . import convnext
         return getattr(convnext, name)
+    if name in ("focal_context", "modulate", "FocalModulation", "FocalModulationBlock", "FocalNet", "build_focalnet"):      # the FocalNet backbone and its kernels (focalnet.py)
+        from . import focalnet
+        return getattr(focalnet, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
