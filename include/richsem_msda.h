@@ -910,6 +910,46 @@ int msda_fmod_modulate_forward_bf16(const uint16_t *q, int64_t ldq, const uint16
 int msda_fmod_modulate_backward_bf16(const uint16_t *dout, const uint16_t *q, int64_t ldq, const uint16_t *mod, int64_t tokens, int C,
                                      uint16_t *dq, int64_t lddq, uint16_t *dmod, msda_stream_t stream);
 
+/* ---- the criterion's mask terms and the mask post-processor (csrc/mask_terms.hip; reference SetCriterion.loss_masks,
+ * models/richsem/richsem.py:1073-1100 with dice_loss / sigmoid_focal_loss of segmentation.py:168-211, and PostProcessSegm.forward,
+ * segmentation.py:214-242) ---------------------------------------------------------------------------------------------------------------
+ * pred (N, Q, h, w) fp32 / bf16, read as stored;  target uint8 (cap, Hp, Wp), one padded canvas per target SLOT (the reference's
+ * nested_tensor_from_tensor_list(masks): pixels outside a target's own mask are 0 and count in every mean and sum);  offsets (N + 1) int64
+ * and query_of_target (cap) int64 ON THE DEVICE: slot s < offsets[N] with 0 <= query_of_target[s] < Q is a pair of the image whose offsets
+ * bracket s; every other slot carries nothing;  num_boxes (1) fp32 on the device.  The resize is torch's bilinear interpolate with
+ * align_corners = False (scale in / out, source max(0, (dst + 0.5) scale - 0.5), i1 = min(i0 + 1, in - 1), fp32 weights); gamma = 2; a
+ * negative alpha switches the class weight off.
+ * msda_mask_loss_forward_*:  pair_sums (cap, 4) fp32 = per slot (sum focal, sum p t, sum p, sum t) over the canvas, zeros where there is no
+ *   pair;  losses (2) fp32 = loss_mask = sum_pairs (focal / (Hp Wp)) / num_boxes and loss_dice = sum_pairs (1 - (2 sum p t + 1) /
+ *   (sum p + sum t + 1)) / num_boxes.  Per-workgroup partial sums in `workspace`, added in fp64 in ascending order.
+ * msda_mask_loss_backward_*:  g (2) fp32 on the device = d / d loss_mask, d / d loss_dice;  grad_pred (N, Q, h, w) in pred's type, every
+ *   element written exactly once: zeros for a query without a pair and for a source pixel no canvas pixel reads.
+ * msda_mask_loss_workspace_bytes: the size of `workspace` for either call (contents irrelevant on entry).
+ * msda_mask_postprocess_*:  per image n of N, HOST arrays: item_indices[n] (rows[n] int64 on the device: the rows of pred[n] to take) or
+ *   item_indices == NULL (rows 0 .. rows[n] - 1), sizes[4 n ..] = (img_h, img_w, oh, ow), out[n] uint8 (rows[n], 1, oh, ow) on the device:
+ *   out = sigmoid(x4[min(floor(oy ch / oh), ch - 1), min(floor(ox cw / ow), cw - 1)]) > threshold with (ch, cw) = (min(img_h, 4 h),
+ *   min(img_w, 4 w)) and x4 the bilinear x4 map of the logits -- never materialised; the sigmoid is evaluated in fp32.
+ * Limits: N, Q, h, w, Hp, cap >= 1, Wp a multiple of 16, rows >= 0, sizes >= 1 (MSDA_ERR_BAD_DIMS); w <= 1024, N Q h w < 2^31, the LDS
+ * rows of a workgroup <= 64 KiB (MSDA_ERR_TOO_LARGE); target, workspace and out 16-byte aligned, the int64 buffers 8, fp32 4
+ * (MSDA_ERR_MISALIGNED).  Every check comes before any launch; no call allocates, synchronises or uses atomics; two calls give the same bits. */
+int msda_mask_loss_workspace_bytes(int N, int Q, int h, int w, int Hp, int Wp, int64_t cap, int64_t *bytes);
+int msda_mask_loss_forward_f32(const float *pred, const uint8_t *target, const int64_t *offsets, const int64_t *query_of_target,
+                               const float *num_boxes, int N, int Q, int h, int w, int Hp, int Wp, int64_t cap, float alpha, float *losses,
+                               float *pair_sums, void *workspace, msda_stream_t stream);
+int msda_mask_loss_forward_bf16(const uint16_t *pred, const uint8_t *target, const int64_t *offsets, const int64_t *query_of_target,
+                                const float *num_boxes, int N, int Q, int h, int w, int Hp, int Wp, int64_t cap, float alpha, float *losses,
+                                float *pair_sums, void *workspace, msda_stream_t stream);
+int msda_mask_loss_backward_f32(const float *pred, const uint8_t *target, const int64_t *offsets, const int64_t *query_of_target,
+                                const float *num_boxes, const float *pair_sums, const float *g, int N, int Q, int h, int w, int Hp, int Wp,
+                                int64_t cap, float alpha, float *grad_pred, void *workspace, msda_stream_t stream);
+int msda_mask_loss_backward_bf16(const uint16_t *pred, const uint8_t *target, const int64_t *offsets, const int64_t *query_of_target,
+                                 const float *num_boxes, const float *pair_sums, const float *g, int N, int Q, int h, int w, int Hp, int Wp,
+                                 int64_t cap, float alpha, uint16_t *grad_pred, void *workspace, msda_stream_t stream);
+int msda_mask_postprocess_f32(const float *pred, int N, int Q, int h, int w, const int64_t *const *item_indices, const int *rows, const int *sizes,
+                              float threshold, uint8_t *const *out, msda_stream_t stream);
+int msda_mask_postprocess_bf16(const uint16_t *pred, int N, int Q, int h, int w, const int64_t *const *item_indices, const int *rows,
+                               const int *sizes, float threshold, uint8_t *const *out, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

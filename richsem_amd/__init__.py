@@ -33,6 +33,9 @@ def __getattr__(name):      # PostProcess is exported from the package without i
     if name in ("focal_context", "modulate", "FocalModulation", "FocalModulationBlock", "FocalNet", "build_focalnet"):      # the FocalNet backbone and its kernels (focalnet.py)
         from . import focalnet
         return getattr(focalnet, name)
+    if name in ("MaskTargets", "mask_losses", "mask_losses_torch", "mask_losses_and_grads", "PostProcessSegm"):      # the criterion's mask terms and the mask post-processor (masks.py)
+        from . import masks
+        return getattr(masks, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
