@@ -1,13 +1,11 @@
 """The ConvNeXt backbone on the library's kernels.
 
 Reference: models/richsem/convnext.py (``build_backbone`` takes it for ``convnext_xlarge_22k``: models/richsem/backbone.py:291-293).  A block
-is ``x + gamma * pwconv2(GELU(pwconv1(LayerNorm(dwconv7x7(x)))))``.  Almost all of it is what the Swin blocks already run on
-(:mod:`richsem_amd.swin`: ``linear_kernel`` with the GELU epilogues, ``layernorm_kernel``, ``swin_norm_nchw``, ``swin_patch_rows``); the two
-operators that were missing are here (csrc/convnext_dw.hip; C ABI ``msda_dwconv7_*``, ``msda_layer_scale_*``):
-
-* :func:`dwconv7` -- the depthwise 7 x 7 convolution of a channels-last map (B, H, W, C), zero padding per image; its backward is the same
-  kernel with the taps flipped plus a weight-gradient kernel with a fixed summation order.
-* :func:`layer_scale` -- ``res + gamma * z`` with ``dgamma`` summed in a fixed order.
+is ``x + gamma * pwconv2(GELU(pwconv1(LayerNorm(dwconv7x7(x)))))``.  Almost all of it runs on the shared row operators of
+:mod:`richsem_amd.backbone_ops` (the linear layer with its GELU epilogues, the LayerNorms, the layer scale, the patch rows); the operator
+that is this backbone's alone is here: :func:`dwconv7` (csrc/convnext_dw.hip; C ABI ``msda_dwconv7_*``), the depthwise 7 x 7 convolution
+of a channels-last map (B, H, W, C), zero padding per image; its backward is the same kernel with the taps flipped plus a weight-gradient
+kernel with a fixed summation order.
 
 bf16 tensors on the device take the kernels and never fall back: a missing library or a width outside the kernels' limits raises.  CPU
 tensors and fp32 / fp64 tensors run a torch composition of the same formulas (what makes the mirrors testable in float64).
@@ -36,14 +34,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .backbone_ops import (EPI_BIAS, EPI_RESIDUAL, MAX_C, DropPath, cached_forms, cast, check_bf16, check_vector, depthwise_weight_grads, f32,
+                           gelu_mlp_backward, gelu_mlp_forward, layer_scale, layer_scale_backward_kernel, layer_scale_kernel,
+                           layernorm_backward_kernel, layernorm_kernel, linear_forms, linear_on_forms, mask_pyramid, need_erf_gelu, on_kernels,
+                           patch_linear, ptr, refuse_drop_path_in_training, swin_layernorm, swin_norm_nchw, swin_patch_rows)
 from .param_cache import VersionCache
-from .swin import (BF16, EPI_BIAS, EPI_GELU, EPI_GELU_BACKWARD, EPI_RESIDUAL, DropPath, _f32, _forms, _ptr, _SwinLinearFunction, _wgrad,
-                   layernorm_backward_kernel, layernorm_kernel, layernorm_workspace_bytes, linear_forms, linear_kernel, swin_layernorm,
-                   swin_norm_nchw, swin_patch_rows)
 
 __all__ = ["dwconv7", "layer_scale", "convnext_block", "dwconv7_weight_form", "LayerNorm", "Block", "ConvNeXt", "build_convnext"]
-
-MAX_C = 4096      # the kernels' widest map (include/richsem_msda.h)
 
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
@@ -51,18 +48,8 @@ def _check_map(x, what):
     """a (B, H, W, C) bf16 map on the device, C a multiple of 32 in [32, 4096] -> contiguous"""
     if x.dim() != 4:
         raise RuntimeError(f"{what}: a channels-last map (B, H, W, C), got {tuple(x.shape)}")
-    if x.shape[-1] % 32 or not 32 <= x.shape[-1] <= MAX_C:
-        raise RuntimeError(f"{what}: C a multiple of 32 in [32, {MAX_C}], got {x.shape[-1]}")
-    if x.dtype != BF16:
-        raise RuntimeError(f"{what}: bfloat16, got {x.dtype}")
-    if not x.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
+    check_bf16(x, x.shape[-1], what)
     return x.contiguous()
-
-
-def _check_vector(v, C, device, what):
-    if v is not None and (v.dtype != torch.float32 or tuple(v.shape) != (C,) or v.device != device or not v.is_contiguous()):
-        raise RuntimeError(f"{what}: float32 ({C}) on {device}, got {v.dtype} {tuple(v.shape)} on {v.device}")
 
 
 def dwconv7_weight_form(weight):
@@ -78,14 +65,14 @@ def dwconv7_kernel(x, w49, bias=None, add=None, flip=0):
     B, H, W, C = x.shape
     if w49.dtype != torch.float32 or tuple(w49.shape) != (49, C) or w49.device != x.device or not w49.is_contiguous():
         raise RuntimeError(f"dwconv7: weight form float32 (49, {C}) contiguous on {x.device}, got {w49.dtype} {tuple(w49.shape)} on {w49.device}")
-    _check_vector(bias, C, x.device, "dwconv7 (bias)")
+    check_vector(bias, C, x.device, "dwconv7 (bias)")
     if add is not None:
         add = _check_map(add, "dwconv7 (add)")
         if add.shape != x.shape or add.device != x.device:
             raise RuntimeError(f"dwconv7: add {tuple(x.shape)} on {x.device}, got {tuple(add.shape)} on {add.device}")
     out = torch.empty_like(x)
     with _lib.on_device(x.device):
-        _lib.check(_lib.load().msda_dwconv7_bf16(x.data_ptr(), w49.data_ptr(), _ptr(bias), _ptr(add), int(flip), B, H, W, C, out.data_ptr(),
+        _lib.check(_lib.load().msda_dwconv7_bf16(x.data_ptr(), w49.data_ptr(), ptr(bias), ptr(add), int(flip), B, H, W, C, out.data_ptr(),
                                                  _lib.raw_stream(x.device)))
     return out
 
@@ -107,61 +94,23 @@ def dwconv7_wgrad_kernel(dy, x, want_bias=True):
     db = torch.empty(C, dtype=torch.float32, device=x.device) if want_bias else None
     ws = torch.empty(dwconv7_workspace_bytes(B, H, W, C) // 4, dtype=torch.float32, device=x.device)
     with _lib.on_device(x.device):
-        _lib.check(_lib.load().msda_dwconv7_wgrad_bf16(dy.data_ptr(), x.data_ptr(), B, H, W, C, dw.data_ptr(), _ptr(db), ws.data_ptr(),
+        _lib.check(_lib.load().msda_dwconv7_wgrad_bf16(dy.data_ptr(), x.data_ptr(), B, H, W, C, dw.data_ptr(), ptr(db), ws.data_ptr(),
                                                        _lib.raw_stream(x.device)))
     return dw, db
 
 
-def _check_rows(t, C, what):
-    if t.shape[-1] != C or C % 32 or not 32 <= C <= MAX_C:
-        raise RuntimeError(f"{what}: (..., C) with C a multiple of 32 in [32, {MAX_C}], got {tuple(t.shape)} for C = {C}")
-    if t.dtype != BF16:
-        raise RuntimeError(f"{what}: bfloat16, got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    return t.reshape(-1, C).contiguous()
-
-
-def layer_scale_kernel(z, g32, res):
-    """``msda_layer_scale_forward_bf16``: z, res (..., C) bf16 on the device, g32 (C) float32 -> rnd(res + gamma z) in z's shape"""
-    C = g32.shape[0]
-    z2, r2 = _check_rows(z, C, "layer_scale"), _check_rows(res, C, "layer_scale (res)")
-    _check_vector(g32, C, z.device, "layer_scale (gamma)")
-    if r2.shape != z2.shape or res.device != z.device:
-        raise RuntimeError(f"layer_scale: res {tuple(z.shape)} on {z.device}, got {tuple(res.shape)} on {res.device}")
-    out = torch.empty_like(z2)
-    with _lib.on_device(z.device):
-        _lib.check(_lib.load().msda_layer_scale_forward_bf16(z2.data_ptr(), g32.data_ptr(), r2.data_ptr(), z2.shape[0], C, out.data_ptr(),
-                                                             _lib.raw_stream(z.device)))
-    return out.view(z.shape)
-
-
-def layer_scale_backward_kernel(dout, z, g32, want_gamma=True):
-    """``msda_layer_scale_backward_bf16`` -> (dz = rnd(gamma dout) in dout's shape, dgamma (C) float32 or None)"""
-    C = g32.shape[0]
-    d2 = _check_rows(dout, C, "layer_scale (gradient)")
-    z2 = _check_rows(z, C, "layer_scale") if want_gamma else None
-    _check_vector(g32, C, dout.device, "layer_scale (gamma)")
-    if z2 is not None and (z2.shape != d2.shape or z.device != dout.device):
-        raise RuntimeError(f"layer_scale: z {tuple(dout.shape)} on {dout.device}, got {tuple(z.shape)} on {z.device}")
-    T = d2.shape[0]
-    dz = torch.empty_like(d2)
-    dg = torch.empty(C, dtype=torch.float32, device=dout.device) if want_gamma else None
-    ws = torch.empty(layernorm_workspace_bytes(T, C) // 4, dtype=torch.float32, device=dout.device) if want_gamma else None
-    with _lib.on_device(dout.device):
-        _lib.check(_lib.load().msda_layer_scale_backward_bf16(d2.data_ptr(), _ptr(z2), g32.data_ptr(), T, C, dz.data_ptr(), _ptr(dg), _ptr(ws),
-                                                              _lib.raw_stream(dout.device)))
-    return dz.view(dout.shape), dg
-
-
-def _on_kernels(x):
-    return x.is_cuda and x.dtype == BF16
+def _dwconv7_wgrads(want_w, want_b, dy, x, wdt, wshape, bdt):
+    """(dweight, dbias) as the parameters are, from ONE call of the weight-gradient kernel -- none when neither is wanted"""
+    if not (want_w or want_b):
+        return None, None
+    dw, db = dwconv7_wgrad_kernel(dy, x, want_bias=want_b)
+    return depthwise_weight_grads(dw, [(wdt, wshape)], [want_w])[0], cast(db, bdt)
 
 
 class _DwConv7Function(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, w49):
-        out = dwconv7_kernel(x, w49, _f32(bias) if bias is not None else None)
+        out = dwconv7_kernel(x, w49, f32(bias) if bias is not None else None)
         ctx.save_for_backward(x, w49)
         ctx.meta = (weight.dtype, weight.shape, bias.dtype if bias is not None else None)
         return out
@@ -173,11 +122,7 @@ class _DwConv7Function(torch.autograd.Function):
         wdt, wshape, bdt = ctx.meta
         dy = dy.contiguous()
         dx = dwconv7_kernel(dy, w49, flip=1) if ctx.needs_input_grad[0] else None
-        dw = db = None
-        if ctx.needs_input_grad[1] or (bdt is not None and ctx.needs_input_grad[2]):
-            dw, db = dwconv7_wgrad_kernel(dy, x, want_bias=bdt is not None and ctx.needs_input_grad[2])
-            dw = dw.t().reshape(wshape).to(wdt) if ctx.needs_input_grad[1] else None
-            db = db.to(bdt) if db is not None else None
+        dw, db = _dwconv7_wgrads(ctx.needs_input_grad[1], bdt is not None and ctx.needs_input_grad[2], dy, x, wdt, wshape, bdt)
         return dx, dw, db, None
 
 
@@ -191,40 +136,10 @@ def dwconv7(x, weight, bias=None, cache=None):
         raise RuntimeError(f"dwconv7: a map (B, H, W, C) and a weight (C, 1, 7, 7), got {tuple(x.shape)} and {tuple(weight.shape)}")
     if bias is not None and tuple(bias.shape) != (x.shape[-1],):
         raise RuntimeError(f"dwconv7: bias ({x.shape[-1]}), got {tuple(bias.shape)}")
-    if not _on_kernels(x):
+    if not on_kernels(x):
         return F.conv2d(x.permute(0, 3, 1, 2), weight, bias, padding=3, groups=x.shape[-1]).permute(0, 2, 3, 1)
     w49 = dwconv7_weight_form(weight) if cache is None else cache.get([weight], lambda: dwconv7_weight_form(weight))
     return _DwConv7Function.apply(x, weight, bias, w49)
-
-
-class _LayerScaleFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, gamma, res):
-        g32 = _f32(gamma)
-        out = layer_scale_kernel(z, g32, res)
-        ctx.save_for_backward(z if ctx.needs_input_grad[1] else None, g32)
-        ctx.meta = gamma.dtype
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dout):
-        z, g32 = ctx.saved_tensors
-        dz = dg = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            dz, dg = layer_scale_backward_kernel(dout, z, g32, want_gamma=ctx.needs_input_grad[1])
-        return (dz if ctx.needs_input_grad[0] else None, dg.to(ctx.meta) if dg is not None else None,
-                dout if ctx.needs_input_grad[2] else None)
-
-
-def layer_scale(z, gamma, res):
-    """``res + gamma * z``, the sum rounded once: z, res (..., C), gamma (C).  bf16 device tensors take ``msda_layer_scale_*`` (dz = gamma
-    dout, dgamma = sum dout z in a fixed order, the residual's gradient is dout itself); any other tensor runs the torch formula."""
-    if gamma.dim() != 1 or z.shape[-1] != gamma.shape[0] or res.shape != z.shape:
-        raise RuntimeError(f"layer_scale: z and res (..., C) and gamma (C), got {tuple(z.shape)}, {tuple(res.shape)} and {tuple(gamma.shape)}")
-    if not _on_kernels(z):
-        return res + gamma * z
-    return _LayerScaleFunction.apply(z, gamma, res)
 
 
 class _ConvNeXtBlockFunction(torch.autograd.Function):
@@ -235,19 +150,18 @@ class _ConvNeXtBlockFunction(torch.autograd.Function):
         x = _check_map(x, "convnext_block")
         C = x.shape[-1]
         need = any(ctx.needs_input_grad)
-        y = dwconv7_kernel(x, w49, _f32(dw_b) if dw_b is not None else None).view(-1, C)
-        g32 = _f32(nw)
-        xn, mean, rstd = layernorm_kernel(y, g32, _f32(nb), eps, want_stats=need)
-        h, u = linear_kernel(xn, f1["w16"], f1["b32"], EPI_GELU, want_out2=need)
+        y = dwconv7_kernel(x, w49, f32(dw_b) if dw_b is not None else None).view(-1, C)
+        g32 = f32(nw)
+        xn, mean, rstd = layernorm_kernel(y, g32, f32(nb), eps, want_stats=need)
         x2 = x.view(-1, C)
         if gamma is None:
-            out, _ = linear_kernel(h, f2["w16"], f2["b32"], EPI_RESIDUAL, x2)
+            out, u = gelu_mlp_forward(xn, f1, f2, need, EPI_RESIDUAL, x2)
             z = gam32 = None
         else:
-            z, _ = linear_kernel(h, f2["w16"], f2["b32"], EPI_BIAS)
-            gam32 = _f32(gamma)
+            z, u = gelu_mlp_forward(xn, f1, f2, need, EPI_BIAS)
+            gam32 = f32(gamma)
             out = layer_scale_kernel(z, gam32, x2)
-        if need:      # (the hidden activation h is not kept: the backward regenerates it from u)
+        if need:
             ctx.save_for_backward(x, y, xn, mean, rstd, u, z if ctx.needs_input_grad[10] else None, g32, gam32, w49)
             ctx.forms = (f1, f2)
             ctx.meta = tuple(p.dtype if p is not None else None for p in (dw_w, dw_b, nw, nb, w1, b1, w2, b2, gamma)) + (dw_w.shape,)
@@ -257,7 +171,7 @@ class _ConvNeXtBlockFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
         x, y, xn, mean, rstd, u, z, g32, gam32, w49 = ctx.saved_tensors
-        (f1, f2), (dwdt, dbdt, nwdt, nbdt, w1dt, b1dt, w2dt, b2dt, gdt, wshape) = ctx.forms, ctx.meta
+        (f1, f2), (dwdt, dbdt, nwdt, nbdt, *dtypes, gdt, wshape) = ctx.forms, ctx.meta
         need = ctx.needs_input_grad
         C = x.shape[-1]
         dout = dout.contiguous()
@@ -267,38 +181,27 @@ class _ConvNeXtBlockFunction(torch.autograd.Function):
             dz, dgam = layer_scale_backward_kernel(d2, z, gam32, want_gamma=need[10])
         else:
             dz = d2
-        du, h = linear_kernel(dz, f2["wt16"], None, EPI_GELU_BACKWARD, u, want_out2=need[8])
-        dw2, db2 = _wgrad(ctx, 8, 9, dz, h, w2dt, b2dt)
-        dw1, db1 = _wgrad(ctx, 6, 7, du, xn, w1dt, b1dt)
-        dxn, _ = linear_kernel(du, f1["wt16"])
+        dxn, dw1, db1, dw2, db2 = gelu_mlp_backward(ctx, (6, 7, 8, 9), dtypes, dz, xn, u, f1, f2)      # pwconv1 (w, b), pwconv2 (w, b)
         dy, dg, db = layernorm_backward_kernel(dxn, y, mean, rstd, g32, want_gamma=need[3], want_beta=need[4])
         dy = dy.view(x.shape)
         dx = dwconv7_kernel(dy, w49, add=dout, flip=1) if need[0] else None      # dout + dwconv^T(dy), rounded once
-        ddw = ddb = None
-        if need[1] or (dbdt is not None and need[2]):
-            ddw, ddb = dwconv7_wgrad_kernel(dy, x, want_bias=dbdt is not None and need[2])
-            ddw = ddw.t().reshape(wshape).to(dwdt) if need[1] else None
-            ddb = ddb.to(dbdt) if ddb is not None else None
-        return (dx, ddw, ddb, dg.to(nwdt) if dg is not None else None, db.to(nbdt) if db is not None else None, None, dw1, db1, dw2, db2,
-                dgam.to(gdt) if dgam is not None else None, None, None, None)
+        ddw, ddb = _dwconv7_wgrads(need[1], dbdt is not None and need[2], dy, x, dwdt, wshape, dbdt)
+        return dx, ddw, ddb, cast(dg, nwdt), cast(db, nbdt), None, dw1, db1, dw2, db2, cast(dgam, gdt), None, None, None
 
 
 def convnext_block(x, block):
     """A :class:`Block` as ONE autograd function on library kernels: x (B, H, W, C) bfloat16 on the device, channels-last.  Forward:
-    ``msda_dwconv7_bf16``; LayerNorm; pwconv1 with the GELU epilogue (the pre-activation u and h = GELU(u)); pwconv2; the layer scale with
-    the residual (or, without ``gamma``, pwconv2's residual epilogue).  Saved for the backward: x, the convolution's output, norm(.), the
-    statistics, u and pwconv2's output -- not h, which the backward regenerates.  The backward ends with the flipped convolution with
-    ``dout`` as its ``add``: the input gradient is rounded once.  Stochastic depth is not part of it (``drop_path > 0`` in training mode
-    raises NotImplementedError)."""
-    if isinstance(block.drop_path, DropPath) and block.drop_path.drop_prob > 0. and block.training:
-        raise NotImplementedError("richsem_amd.convnext: fused blocks do not implement stochastic depth in training mode (drop_path_rate=0.)")
-    if not isinstance(block.act, nn.GELU) or getattr(block.act, "approximate", "none") != "none":
-        raise NotImplementedError("richsem_amd.convnext: fused blocks need the erf form of nn.GELU")
+    ``msda_dwconv7_bf16``; LayerNorm; pwconv1 and pwconv2 under the GELU-MLP policy of ``backbone_ops``; the layer scale with the residual
+    (or, without ``gamma``, pwconv2's residual epilogue).  Saved for the backward: x, the convolution's output, norm(.), the statistics, the
+    pre-activation and pwconv2's output.  The backward ends with the flipped convolution with ``dout`` as its ``add``: the input gradient
+    is rounded once.  Stochastic depth is not part of it (``drop_path > 0`` in training mode raises NotImplementedError)."""
+    refuse_drop_path_in_training(block, "convnext")
+    need_erf_gelu(block.act, "convnext")
     dw, norm, p1, p2 = block.dwconv, block.norm, block.pwconv1, block.pwconv2
     w49 = block._forms["dwconv"].get([dw.weight], lambda: dwconv7_weight_form(dw.weight))
     return _ConvNeXtBlockFunction.apply(x, dw.weight, dw.bias, norm.weight, norm.bias, float(norm.eps), p1.weight, p1.bias, p2.weight, p2.bias,
-                                        block.gamma, w49, _forms(block._forms["pwconv1"], p1.weight, p1.bias),
-                                        _forms(block._forms["pwconv2"], p2.weight, p2.bias))
+                                        block.gamma, w49, cached_forms(block._forms["pwconv1"], p1.weight, p1.bias),
+                                        cached_forms(block._forms["pwconv2"], p2.weight, p2.bias))
 
 
 # ---- the mirrors ------------------------------------------------------------------------------------------------------------------------
@@ -362,7 +265,7 @@ class Block(nn.Module):
         return x + self.drop_path(z)
 
     def forward(self, x):
-        if _on_kernels(x):
+        if on_kernels(x):
             return self.forward_map(x.permute(0, 2, 3, 1).contiguous()).permute(0, 3, 1, 2)
         z = self.dwconv(x).permute(0, 2, 3, 1)
         z = self.pwconv2(self.act(self.pwconv1(self.norm(z))))
@@ -419,13 +322,7 @@ class ConvNeXt(nn.Module):
         if not self.fused:
             return norm.on_map(F.conv2d(img, conv.weight, conv.bias, stride=conv.stride).permute(0, 2, 3, 1), False)
         rows = swin_patch_rows(img[:, :, :Hs * ph, :Ws * pw], (ph, pw))      # no padding: trailing rows and columns are dropped
-
-        def build():
-            flat = conv.weight.detach().to(BF16).flatten(1)
-            return linear_forms(F.pad(flat, (0, rows.shape[-1] - flat.shape[1])), conv.bias)
-        forms = self._forms[0].get([conv.weight] + ([conv.bias] if conv.bias is not None else []), build)
-        t = _SwinLinearFunction.apply(rows, conv.weight, conv.bias, None, forms)
-        return norm.on_map(t, True).view(B, Hs, Ws, -1)
+        return norm.on_map(patch_linear(rows, conv.weight, conv.bias, self._forms[0]), True).view(B, Hs, Ws, -1)
 
     def _downsample_map(self, i, x):
         norm, conv = self.downsample_layers[i]
@@ -438,8 +335,7 @@ class ConvNeXt(nn.Module):
         w2d = conv.weight.permute(0, 2, 3, 1).flatten(1)      # (N, dy, dx, C): the order of the gathered row
         if not self.fused:
             return F.linear(rows, w2d, conv.bias)
-        forms = self._forms[i].get([conv.weight] + ([conv.bias] if conv.bias is not None else []), lambda: linear_forms(w2d, conv.bias))
-        return _SwinLinearFunction.apply(rows, w2d, conv.bias, None, forms)
+        return linear_on_forms(rows, w2d, conv.bias, cached_forms(self._forms[i], conv.weight, conv.bias, lambda: linear_forms(w2d, conv.bias)))
 
     def _features_map(self, x):
         outs = []
@@ -457,7 +353,7 @@ class ConvNeXt(nn.Module):
         return tuple(outs)
 
     def forward_features(self, x):
-        if _on_kernels(x):
+        if on_kernels(x):
             return self._features_map(x)
         outs = []
         for i in range(4):
@@ -467,9 +363,7 @@ class ConvNeXt(nn.Module):
         return tuple(outs)
 
     def forward(self, images, mask):
-        assert mask is not None
-        outs = self.forward_features(images)
-        return [(o, F.interpolate(mask[None].float(), size=o.shape[-2:]).to(torch.bool)[0]) for o in outs]
+        return mask_pyramid(self.forward_features(images), mask)
 
 
 def build_convnext(modelname, pretrained, backbone_dir=None, **kw):

@@ -24,10 +24,10 @@ trains on the kernel path.
 The classes mirror the reference's -- constructor arguments and state-dict keys -- so a reference checkpoint loads with ``strict=True``
 both ways.  Without ``fused`` the linear layers, the norms and the layer scale run on torch ops.  The plain attribute ``fused``
 (``set_fused`` of the modulation, the block, the layer and the network; False by default, not a constructor argument, not in the state
-dict, bf16 on the device only) routes ``f``, ``h``, ``proj``, ``fc1`` + GELU and ``fc2`` through ``msda_swin_linear_bf16`` (``f``'s output
-rows padded to 2 C + 32, from which q, ctx0 and the gates are read in place and into whose gradient rows dq, dctx0 and the gate gradients
-are written in place), the norms through ``msda_swin_layernorm_*`` / ``msda_swin_norm_nchw_*`` and ``shortcut + gamma x`` through
-``msda_layer_scale_*``; it raises under ``drop_path > 0`` in training mode.  The stem and downsampling convolutions stay torch's on every
+dict, bf16 on the device only) routes ``f``, ``h``, ``proj``, ``fc1`` + GELU and ``fc2``, the norms and ``shortcut + gamma x`` through the
+shared row operators of :mod:`richsem_amd.backbone_ops` (``f``'s output rows padded to 2 C + 32, from which q, ctx0 and the gates are read
+in place and into whose gradient rows dq, dctx0 and the gate gradients are written in place); it raises under ``drop_path > 0`` in
+training mode.  The stem and downsampling convolutions stay torch's on every
 path.  ``forward(images, mask)`` returns (feature, mask) pairs as ``swin.py`` and ``convnext.py`` do.  Nothing here downloads
 anything: a pretrained path raises.  Capturing the device path into a HIP graph is untested.
 """
@@ -39,14 +39,14 @@ import torch.nn.functional as F
 import torch.utils.checkpoint as checkpoint
 
 from . import _lib
+from .backbone_ops import (BF16, EPI_BIAS, MAX_C, DropPath, bf16_rows, cached_forms, check_bf16, depthwise_weight_grads, gelu_mlp_backward,
+                           gelu_mlp_forward, kernel_width, layer_scale, linear_forms, linear_kernel, linear_on_forms, mask_pyramid, need_erf_gelu,
+                           need_layernorm, on_kernels, output_norm_nchw, pair, refuse_drop_path_in_training, swin_layernorm, swin_linear, wgrad)
 from .param_cache import VersionCache
-from .swin import (BF16, EPI_BIAS, EPI_GELU, EPI_GELU_BACKWARD, DropPath, _forms, _pair, _SwinLinearFunction, _wgrad, linear_forms,
-                   linear_kernel, swin_layernorm, swin_linear, swin_norm_nchw)
 
 __all__ = ["focal_context", "focal_context_torch", "modulate", "kernel_path", "focal_weight_form", "Mlp", "FocalModulation",
            "FocalModulationBlock", "BasicLayer", "PatchEmbed", "FocalNet", "build_focalnet"]
 
-MAX_C = 4096      # the kernels' widest map (include/richsem_msda.h)
 KERNEL_SIZES = (3, 5, 7, 9)
 MODELS = ("focalnet_L_384_22k", "focalnet_L_384_22k_fl4", "focalnet_XL_384_22k", "focalnet_H_224_22k_fl4_fd")
 
@@ -55,17 +55,13 @@ MODELS = ("focalnet_L_384_22k", "focalnet_L_384_22k_fl4", "focalnet_XL_384_22k",
 def kernel_shape(C, sizes):
     """do the kernels support width ``C`` and the levels' kernel sizes ``sizes`` (K_0, K_0 + 2, ...)?"""
     sizes = tuple(sizes)
-    return (C % 32 == 0 and 32 <= C <= MAX_C and 1 <= len(sizes) <= 4 and all(k in KERNEL_SIZES for k in sizes)
+    return (kernel_width(C) and 1 <= len(sizes) <= 4 and all(k in KERNEL_SIZES for k in sizes)
             and all(b - a == 2 for a, b in zip(sizes, sizes[1:])))
-
-
-def _on_kernels(x):
-    return x.is_cuda and x.dtype == BF16 and x.shape[-1] % 32 == 0 and 32 <= x.shape[-1] <= MAX_C
 
 
 def kernel_path(x, sizes):
     """THE RULE of the module docstring: bf16 on the device and a supported shape -> the kernels, always; everything else -> torch"""
-    return _on_kernels(x) and kernel_shape(x.shape[-1], sizes)
+    return on_kernels(x) and kernel_shape(x.shape[-1], sizes)
 
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------------------------
@@ -99,14 +95,11 @@ def _check_context(ctx0, gates, wform, sizes):
     if not kernel_shape(C, sizes):
         raise RuntimeError(f"focal_context: C a multiple of 32 in [32, {MAX_C}] and 1 to 4 kernel sizes from {KERNEL_SIZES} growing by 2, got "
                            f"C = {C} and {tuple(sizes)}")
-    for t, what in ((ctx0, "ctx0"), (gates, "gates")):
-        if t.dtype != BF16:
-            raise RuntimeError(f"focal_context ({what}): bfloat16, got {t.dtype}")
     rows = sum(k * k for k in sizes)
     if wform.dtype != torch.float32 or tuple(wform.shape) != (rows, C) or not wform.is_contiguous():
         raise RuntimeError(f"focal_context: weight form float32 ({rows}, {C}) contiguous, got {wform.dtype} {tuple(wform.shape)}")
-    if not ctx0.is_cuda or not gates.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
+    check_bf16(ctx0, C, "focal_context (ctx0)")
+    check_bf16(gates, len(sizes) + 1, "focal_context (gates)", limited=False)
     if wform.device != ctx0.device:
         raise RuntimeError(f"focal_context: weight form on {ctx0.device}, got {wform.device}")
     if gates.device != ctx0.device:
@@ -167,19 +160,9 @@ def context_backward_kernel(dA, ctx0, gates, wform, u, mg, sizes, normalize, wan
     return dctx0, dgates, dw, du
 
 
-def _check_tokens(t, C, what):
-    if t.dim() < 2 or t.shape[-1] != C or C % 32 or not 32 <= C <= MAX_C:
-        raise RuntimeError(f"{what}: (..., C) with C a multiple of 32 in [32, {MAX_C}], got {tuple(t.shape)}")
-    if t.dtype != BF16:
-        raise RuntimeError(f"{what}: bfloat16, got {t.dtype}")
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    return t.reshape(-1, C).contiguous()
-
-
 def _token_rows(t, C, what):
     """(..., C) bf16 on the device -> (t, ld): a (B, H, W, C) slice of wider rows as it is where the kernels can read it in place"""
-    _check_tokens(t[..., :1, :], C, what)      # (the checks alone: no copy of t)
+    check_bf16(t, C, what)
     if t.dim() == 4:
         return _pixel_rows(t, 8, 16)
     return t.reshape(-1, C).contiguous(), C
@@ -189,7 +172,7 @@ def modulate_kernel(q, mod):
     """``msda_fmod_modulate_forward_bf16``: q, mod (..., C) bf16 on the device (q may be a (B, H, W, C) slice of wider rows, read in place)
     -> rnd(q mod) in q's shape"""
     C = q.shape[-1]
-    (q2, ldq), m2 = _token_rows(q, C, "modulate"), _check_tokens(mod, C, "modulate (mod)")
+    (q2, ldq), m2 = _token_rows(q, C, "modulate"), bf16_rows(mod, C, "modulate (mod)")
     if mod.shape != q.shape or mod.device != q.device:
         raise RuntimeError(f"modulate: mod {tuple(q.shape)} on {q.device}, got {tuple(mod.shape)} on {mod.device}")
     out = torch.empty_like(m2)
@@ -203,7 +186,7 @@ def modulate_backward_kernel(dout, q, mod, into=None):
     """``msda_fmod_modulate_backward_bf16`` -> (dq = rnd(dout mod), dmod = rnd(dout q)) in q's shape.  ``into``: a (B, H, W, C) view of wider
     contiguous gradient rows that dq is written into in place"""
     C = q.shape[-1]
-    d2, (q2, ldq), m2 = _check_tokens(dout, C, "modulate (gradient)"), _token_rows(q, C, "modulate"), _check_tokens(mod, C, "modulate (mod)")
+    d2, (q2, ldq), m2 = bf16_rows(dout, C, "modulate (gradient)"), _token_rows(q, C, "modulate"), bf16_rows(mod, C, "modulate (mod)")
     if not (dout.shape == q.shape == mod.shape) or not (dout.device == q.device == mod.device):
         raise RuntimeError(f"modulate: dout, q and mod of one shape on one device, got {tuple(dout.shape)}, {tuple(q.shape)}, {tuple(mod.shape)}")
     if into is None:
@@ -235,11 +218,8 @@ class _FocalContextFunction(torch.autograd.Function):
         sizes, normalize, wmeta = ctx.meta
         want_w = any(ctx.needs_input_grad[4:])
         dctx0, dgates, dw, _ = context_backward_kernel(dA, ctx0, gates, wform, u, mg, sizes, normalize, want_weights=want_w)
-        dws, row = [], 0
-        for i, (k, (dt, shape)) in enumerate(zip(sizes, wmeta)):
-            dws.append(dw[row:row + k * k].t().reshape(shape).to(dt) if want_w and ctx.needs_input_grad[4 + i] else None)
-            row += k * k
-        return (dctx0 if ctx.needs_input_grad[0] else None, dgates if ctx.needs_input_grad[1] else None, None, None) + tuple(dws)
+        return ((dctx0 if ctx.needs_input_grad[0] else None, dgates if ctx.needs_input_grad[1] else None, None, None)
+                + depthwise_weight_grads(dw, wmeta, ctx.needs_input_grad[4:]))
 
 
 def focal_context_torch(ctx0, gates, weights, normalize):
@@ -293,7 +273,7 @@ def modulate(q, mod):
     """``q * mod``: bf16 device tensors of a width the kernels support take ``msda_fmod_modulate_*``, anything else the torch product"""
     if q.shape != mod.shape:
         raise RuntimeError(f"modulate: q and mod of one shape, got {tuple(q.shape)} and {tuple(mod.shape)}")
-    if not (_on_kernels(q) and mod.dtype == BF16):
+    if not (on_kernels(q) and kernel_width(q.shape[-1]) and mod.dtype == BF16):
         return q * mod
     return _ModulateFunction.apply(q, mod)
 
@@ -332,27 +312,23 @@ class _FusedModulationFunction(torch.autograd.Function):
         _, dmod = modulate_backward_kernel(dout.contiguous(), q, mod, into=drows[..., :C])
         dmod2 = dmod.view(-1, C)
         dA, _ = linear_kernel(dmod2, ctx.hforms["wt16"])
-        dhw, dhb = _wgrad(ctx, 3, 4, dmod2, A.view(-1, C), hwdt, hbdt)
+        dhw, dhb = wgrad(ctx, 3, 4, dmod2, A.view(-1, C), hwdt, hbdt)
         want_w = any(ctx.needs_input_grad[6:])
         _, _, dw, _ = context_backward_kernel(dA.view(A.shape), ctx0, gates, wform, u, mg, sizes, normalize, want_weights=want_w,
                                               into=(drows[..., C:2 * C], drows[..., 2 * C:2 * C + L + 1]))
-        dws, row = [], 0
-        for i, (k, (dt, shape)) in enumerate(zip(sizes, wmeta)):
-            dws.append(dw[row:row + k * k].t().reshape(shape).to(dt) if want_w and ctx.needs_input_grad[6 + i] else None)
-            row += k * k
-        return (drows, None, None, dhw.reshape(hwshape) if dhw is not None else None, dhb, None) + tuple(dws)
+        return ((drows, None, None, dhw.reshape(hwshape) if dhw is not None else None, dhb, None)
+                + depthwise_weight_grads(dw, wmeta, ctx.needs_input_grad[6:]))
 
 
 class _FocalMlpFunction(torch.autograd.Function):
-    """``fc2(GELU(fc1(x)))`` on ``msda_swin_linear_bf16`` with the GELU epilogues (:func:`richsem_amd.swin.swin_mlp` without its norm and
-    residual: a post-LN block norms the OUTPUT): the pre-activation u is saved, the hidden activation regenerated in the backward"""
+    """``fc2(GELU(fc1(x)))`` under the GELU-MLP policy of ``backbone_ops`` (``swin_mlp`` without its norm and residual: a post-LN block norms
+    the OUTPUT): saves x and the pre-activation u"""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, f1, f2):
         x2 = x.reshape(-1, x.shape[-1]).contiguous()
         need = any(ctx.needs_input_grad)
-        h, u = linear_kernel(x2, f1["w16"], f1["b32"], EPI_GELU, want_out2=need)
-        out, _ = linear_kernel(h, f2["w16"], f2["b32"], EPI_BIAS)
+        out, u = gelu_mlp_forward(x2, f1, f2, need, EPI_BIAS)
         if need:
             ctx.save_for_backward(x2, u)
             ctx.forms = (f1, f2)
@@ -363,17 +339,14 @@ class _FocalMlpFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
         x2, u = ctx.saved_tensors
-        (f1, f2), (shape, w1dt, b1dt, w2dt, b2dt) = ctx.forms, ctx.meta
+        (f1, f2), (shape, *dtypes) = ctx.forms, ctx.meta
         d2 = dout.reshape(-1, dout.shape[-1]).contiguous()
-        du, h = linear_kernel(d2, f2["wt16"], None, EPI_GELU_BACKWARD, u, want_out2=ctx.needs_input_grad[3])
-        dw2, db2 = _wgrad(ctx, 3, 4, d2, h, w2dt, b2dt)
-        dw1, db1 = _wgrad(ctx, 1, 2, du, x2, w1dt, b1dt)
-        dx = linear_kernel(du, f1["wt16"])[0].view(shape) if ctx.needs_input_grad[0] else None
-        return dx, dw1, db1, dw2, db2, None, None
+        dx, dw1, db1, dw2, db2 = gelu_mlp_backward(ctx, (1, 2, 3, 4), dtypes, d2, x2, u, f1, f2, want_dxn=ctx.needs_input_grad[0])      # w1, b1, w2, b2
+        return dx.view(shape) if dx is not None else None, dw1, db1, dw2, db2, None, None
 
 
 def _need_fused(x, what):
-    if not (x.is_cuda and x.dtype == BF16):
+    if not on_kernels(x):
         raise RuntimeError(f"richsem_amd.focalnet: fused {what} needs a bfloat16 tensor on the device, got {x.dtype} on {x.device}")
 
 
@@ -438,10 +411,9 @@ class FocalModulation(nn.Module):
                                f"{[w.shape[-1] for w in weights]}")
         pad = F_PAD - (L + 1)
         wpad, bpad = F.pad(self.f.weight, (0, 0, 0, pad)), F.pad(self.f.bias, (0, pad))      # (differentiable: their gradients' padding is dropped)
-        forms = self._forms["f"].get([self.f.weight, self.f.bias], lambda: linear_forms(wpad, bpad))
-        rows = _SwinLinearFunction.apply(x, wpad, bpad, None, forms)
+        rows = linear_on_forms(x, wpad, bpad, cached_forms(self._forms["f"], self.f.weight, self.f.bias, lambda: linear_forms(wpad, bpad)))
         hw = self.h.weight
-        hforms = self._forms["h"].get([hw, self.h.bias], lambda: linear_forms(hw.view(C, C), self.h.bias))
+        hforms = cached_forms(self._forms["h"], hw, self.h.bias, lambda: linear_forms(hw.view(C, C), self.h.bias))
         wform = self._form.get(weights, lambda: focal_weight_form(weights))
         out = _FusedModulationFunction.apply(rows, self.normalize_modulator, wform, hw, self.h.bias, hforms, *weights)
         if self.use_postln_in_modulation:
@@ -497,22 +469,20 @@ class FocalModulationBlock(nn.Module):
         return self
 
     def _forward_fused(self, x):
-        from .convnext import layer_scale
-        if isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0. and self.training:
-            raise NotImplementedError("richsem_amd.focalnet: fused blocks do not implement stochastic depth in training mode (drop_path_rate=0.)")
-        if not isinstance(self.mlp.act, nn.GELU) or getattr(self.mlp.act, "approximate", "none") != "none" or self.mlp.drop.p > 0.:
-            raise NotImplementedError("richsem_amd.focalnet: fused blocks need the erf form of nn.GELU and drop=0.")
+        refuse_drop_path_in_training(self, "focalnet")
+        need_erf_gelu(self.mlp.act, "focalnet")
+        if self.mlp.drop.p > 0.:
+            raise NotImplementedError("richsem_amd.focalnet: fused blocks need drop=0.")
         for norm in (self.norm1, self.norm2):
-            if not isinstance(norm, nn.LayerNorm) or not norm.elementwise_affine or norm.bias is None:
-                raise NotImplementedError("richsem_amd.focalnet: fused blocks need nn.LayerNorm with weight and bias")
+            need_layernorm(norm, "focalnet", "block")
         _need_fused(x, "block")
         B, N, C = x.shape
         H, W = self.H, self.W
         ln = lambda t, norm: swin_layernorm(t, norm.weight, norm.bias, norm.eps)      # noqa: E731
         scale = lambda z, gamma, res: layer_scale(z, gamma, res) if self.use_layerscale else res + z      # noqa: E731
         mlp = lambda t: _FocalMlpFunction.apply(t, self.mlp.fc1.weight, self.mlp.fc1.bias, self.mlp.fc2.weight, self.mlp.fc2.bias,      # noqa: E731
-                                                _forms(self._forms["fc1"], self.mlp.fc1.weight, self.mlp.fc1.bias),
-                                                _forms(self._forms["fc2"], self.mlp.fc2.weight, self.mlp.fc2.bias))
+                                                cached_forms(self._forms["fc1"], self.mlp.fc1.weight, self.mlp.fc1.bias),
+                                                cached_forms(self._forms["fc2"], self.mlp.fc2.weight, self.mlp.fc2.bias))
         z = self.modulation((x if self.use_postln else ln(x, self.norm1)).view(B, H, W, C)).reshape(B, N, C)
         x = scale(ln(z, self.norm1) if self.use_postln else z, self.gamma_1, x)
         return scale(ln(mlp(x), self.norm2) if self.use_postln else mlp(ln(x, self.norm2)), self.gamma_2, x)
@@ -587,7 +557,7 @@ class PatchEmbed(nn.Module):
 
     def __init__(self, patch_size=4, in_chans=3, embed_dim=96, norm_layer=None, use_conv_embed=False, is_stem=False):
         super().__init__()
-        self.patch_size = _pair(patch_size)
+        self.patch_size = pair(patch_size)
         self.in_chans = in_chans
         self.embed_dim = embed_dim
         if use_conv_embed:
@@ -607,7 +577,8 @@ class PatchEmbed(nn.Module):
         if self.norm is not None:
             Wh, Ww = x.shape[2], x.shape[3]
             t = x.flatten(2).transpose(1, 2)
-            if self.fused and t.is_cuda and t.dtype == BF16 and isinstance(self.norm, nn.LayerNorm):
+            if self.fused and on_kernels(t):
+                need_layernorm(self.norm, "focalnet", "PatchEmbed")
                 t = swin_layernorm(t, self.norm.weight, self.norm.bias, self.norm.eps)
             else:
                 t = self.norm(t)
@@ -676,18 +647,11 @@ class FocalNet(nn.Module):
         for i, layer in enumerate(self.layers):
             x_out, H, W, x, Wh, Ww = layer(x, Wh, Ww)
             if i in self.out_indices:
-                norm = getattr(self, f"norm{i}")
-                if self.fused and x_out.is_cuda and x_out.dtype == BF16 and isinstance(norm, nn.LayerNorm):
-                    outs.append(swin_norm_nchw(x_out, H, W, norm.weight, norm.bias, norm.eps))
-                    continue
-                x_out = norm(x_out)
-                outs.append(x_out.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2).contiguous())
+                outs.append(output_norm_nchw(getattr(self, f"norm{i}"), x_out, H, W, self.fused, "focalnet"))
         return tuple(outs)
 
     def forward(self, images, mask):
-        assert mask is not None
-        outs = self.forward_features(images)
-        return [(o, F.interpolate(mask[None].float(), size=o.shape[-2:]).to(torch.bool)[0]) for o in outs]
+        return mask_pyramid(self.forward_features(images), mask)
 
     def train(self, mode=True):
         super().train(mode)

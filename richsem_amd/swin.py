@@ -13,17 +13,14 @@ float64).  A bf16 device tensor never falls back to the composition: a missing l
 
 The rest of a block -- norm1, qkv, proj + residual, norm2, fc1, GELU, fc2 + residual -- runs on torch ops unless the block's plain
 attribute ``fused`` is set (``BasicLayer.set_fused`` / ``SwinTransformer.set_fused``; off by default, not a constructor argument and not
-in the state dict).  With it a bf16 device tensor takes :func:`swin_layernorm`, :func:`swin_linear` and :func:`swin_mlp`: a linear layer of
-general width with fused epilogues and a LayerNorm of general width (csrc/swin_block_mfma.hip; C ABI ``msda_swin_linear_bf16``,
-``msda_swin_layernorm_*``).  :func:`swin_mlp` is ONE autograd function for ``x + fc2(GELU(fc1(norm(x))))`` that saves the pre-activation
-``u`` and regenerates the hidden activation in its backward.  CPU, fp32 and fp64 tensors run the torch formula with ``fused`` set too.
-
-Where the backbone changes layout -- the patch embedding, the three PatchMerging layers and the output norms -- a second switch,
-``SwinTransformer.set_fused_stages`` (``PatchEmbed.fused``, ``PatchMerging.fused``, ``SwinTransformer.fused_stages``; off by default
-like ``fused``), puts the index arithmetic into kernels (csrc/swin_stage.hip; C ABI ``msda_swin_merge_norm_*``, ``msda_swin_norm_nchw_*``,
-``msda_swin_patch_rows_*``): :func:`swin_merge_norm` is the LayerNorm of the 2 x 2 gathered rows read straight from the map,
-:func:`swin_norm_nchw` a LayerNorm stored as (B, C, H, W), :func:`swin_patch_rows` the image as rows of patches for
-``msda_swin_linear_bf16``.  ``set_fused`` keeps meaning the blocks only.
+in the state dict).  With it a bf16 device tensor takes the shared row operators of :mod:`richsem_amd.backbone_ops` (``swin_layernorm``,
+``swin_linear``) and :func:`swin_mlp`, ONE autograd function for ``x + fc2(GELU(fc1(norm(x))))`` under that module's GELU-MLP policy.  CPU,
+fp32 and fp64 tensors run the torch formula with ``fused`` set too.  Where the backbone changes layout -- the patch embedding, the three
+PatchMerging layers and the output norms -- a second switch, ``SwinTransformer.set_fused_stages`` (``PatchEmbed.fused``,
+``PatchMerging.fused``, ``SwinTransformer.fused_stages``; off by default like ``fused``), puts the index arithmetic into kernels
+(csrc/swin_stage.hip): :func:`swin_merge_norm`, here, is the LayerNorm of the 2 x 2 gathered rows read straight from the map (C ABI
+``msda_swin_merge_norm_*``); the output norms and the patch rows are ``backbone_ops.swin_norm_nchw`` and ``swin_patch_rows``.
+``set_fused`` keeps meaning the blocks only.
 """
 import ctypes
 
@@ -32,6 +29,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+# (the operators that lived here before backbone_ops.py stay reachable as swin.<name>: tests and tools call swin.linear_kernel and others)
+from .backbone_ops import (BF16, EPI_BIAS, EPI_GELU, EPI_GELU_BACKWARD, EPI_RESIDUAL, DropPath, bf16_rows, cached_forms, cast,      # noqa: F401
+                           check_bf16, column_sums, f32, gelu_mlp_backward, gelu_mlp_forward, layernorm_backward_kernel, layernorm_kernel,
+                           layernorm_workspace_bytes, linear_forms, linear_kernel, mask_pyramid, need_erf_gelu, need_layernorm,
+                           norm_nchw_backward_kernel, norm_nchw_kernel, on_kernels, output_norm_nchw, pair, patch_grid, patch_linear, patch_width,
+                           ptr, refuse_drop_path_in_training, swin_layernorm, swin_linear, swin_norm_nchw, swin_patch_rows, token_norm_operands)
 from .param_cache import VersionCache
 
 __all__ = ["window_attention", "window_attention_torch", "swin_linear", "swin_layernorm", "swin_mlp", "swin_merge_norm", "swin_norm_nchw",
@@ -96,10 +99,7 @@ def workspace_bytes(B, Hp, Wp, channels, num_heads, window):
 
 
 def _check_operands(qkv, table, num_heads, window):
-    if not qkv.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    if qkv.dtype != torch.bfloat16:
-        raise RuntimeError(f"window_attention: bfloat16 qkv, got {qkv.dtype}")
+    check_bf16(qkv, qkv.shape[-1], "window_attention (qkv)", limited=False)
     if qkv.dim() != 4 or qkv.shape[-1] % 3:
         raise RuntimeError(f"window_attention: qkv (B, Hp, Wp, 3 C), got {tuple(qkv.shape)}")
     if not qkv.is_contiguous():
@@ -149,178 +149,16 @@ def window_attention(qkv, table, num_heads, window, shift):
     return _WindowAttentionFunction.apply(qkv, table, num_heads, window, shift)
 
 
-# ---- the block's other kernels: linear with epilogues, LayerNorm ----------------------------------------------------------------------------
-EPI_BIAS, EPI_GELU, EPI_RESIDUAL, EPI_GELU_BACKWARD = 0, 1, 2, 3      # `epilogue` of msda_swin_linear_bf16 (include/richsem_msda.h)
-BF16 = torch.bfloat16
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _rows(t, width, what):
-    if not t.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    if t.dtype != BF16 or t.shape[-1] != width:
-        raise RuntimeError(f"{what}: bfloat16 (..., {width}), got {t.dtype} {tuple(t.shape)}")
-    return t.reshape(-1, width).contiguous()
-
-
-def linear_kernel(x2, w16, b32=None, epilogue=EPI_BIAS, aux=None, want_out2=False):
-    """One call of ``msda_swin_linear_bf16`` (no autograd): x2 (tokens, K), w16 (N, K), aux (tokens, N) bf16 contiguous on the device, b32 (N)
-    float32 or None -> (out, out2), both (tokens, N) bf16; out2 is None unless ``want_out2`` (epilogues 1 and 3 write it)."""
-    T, K = x2.shape
-    N = w16.shape[0]
-    bias_ok = b32 is None or (b32.dtype == torch.float32 and b32.numel() == N and b32.is_contiguous())
-    if w16.dtype != BF16 or w16.shape[1] != K or not w16.is_contiguous() or not bias_ok:
-        raise RuntimeError(f"swin_linear: weight bfloat16 (N, {K}) contiguous and bias float32 (N), got {w16.dtype} {tuple(w16.shape)}")
-    if aux is not None and (aux.dtype != BF16 or tuple(aux.shape) != (T, N) or not aux.is_contiguous()):
-        raise RuntimeError(f"swin_linear: aux bfloat16 ({T}, {N}) contiguous, got {aux.dtype} {tuple(aux.shape)}")
-    out = torch.empty((T, N), dtype=BF16, device=x2.device)
-    out2 = torch.empty_like(out) if want_out2 else None
-    with _lib.on_device(x2.device):
-        _lib.check(_lib.load().msda_swin_linear_bf16(x2.data_ptr(), w16.data_ptr(), _ptr(b32), _ptr(aux), epilogue, T, K, N, out.data_ptr(),
-                                                     _ptr(out2), _lib.raw_stream(x2.device)))
-    return out, out2
-
-
-def layernorm_workspace_bytes(tokens, C):
-    n = ctypes.c_int64(0)
-    _lib.check(_lib.load().msda_swin_layernorm_workspace_bytes(tokens, C, ctypes.byref(n)))
-    return n.value
-
-
-def layernorm_kernel(x2, g32, b32, eps, want_stats=True):
-    """``msda_swin_layernorm_forward_bf16``: x2 (tokens, C) bf16 -> (out, mean, rstd); the statistics are None unless ``want_stats``"""
-    T, C = x2.shape
-    out = torch.empty_like(x2)
-    mean = torch.empty(T, dtype=torch.float32, device=x2.device) if want_stats else None
-    rstd = torch.empty_like(mean) if want_stats else None
-    with _lib.on_device(x2.device):
-        _lib.check(_lib.load().msda_swin_layernorm_forward_bf16(x2.data_ptr(), g32.data_ptr(), b32.data_ptr(), eps, T, C, out.data_ptr(),
-                                                                _ptr(mean), _ptr(rstd), _lib.raw_stream(x2.device)))
-    return out, mean, rstd
-
-
-def layernorm_backward_kernel(dy2, x2, mean, rstd, g32, add=None, want_gamma=True, want_beta=True):
-    """``msda_swin_layernorm_backward_bf16`` -> (dx bf16, dgamma float32 or None, dbeta float32 or None)"""
-    T, C = x2.shape
-    dx = torch.empty_like(x2)
-    dg = torch.empty(C, dtype=torch.float32, device=x2.device) if want_gamma else None
-    db = torch.empty(C, dtype=torch.float32, device=x2.device) if want_beta else None
-    ws = torch.empty(layernorm_workspace_bytes(T, C) // 4, dtype=torch.float32, device=x2.device) if want_gamma or want_beta else None
-    with _lib.on_device(x2.device):
-        _lib.check(_lib.load().msda_swin_layernorm_backward_bf16(dy2.data_ptr(), x2.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
-                                                                 _ptr(add), T, C, dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(ws),
-                                                                 _lib.raw_stream(x2.device)))
-    return dx, dg, db
-
-
-def _f32(p):
-    return p.detach().float().contiguous()
-
-
-def linear_forms(weight, bias):
-    """the forms the kernels read a linear layer from: ``w16`` (N, K) bf16, ``wt16`` (K, N) bf16 (the input gradient is the same kernel on
-    the transposed weight), ``b32`` float32 or None.  Kept per parameter version in a :class:`richsem_amd.param_cache.VersionCache`."""
-    w16 = weight.detach().to(BF16).contiguous()
-    return {"w16": w16, "wt16": w16.t().contiguous(), "b32": _f32(bias) if bias is not None else None}
-
-
-def _forms(cache, weight, bias):
-    if cache is None:
-        return linear_forms(weight, bias)
-    return cache.get([weight] + ([bias] if bias is not None else []), lambda: linear_forms(weight, bias))
-
-
-def _wgrad(ctx, iw, ib, dy2, x2, weight_dtype, bias_dtype):
-    """(dW, db) of one layer by the package's weight-gradient rule, in the parameters' dtypes; None where not needed"""
-    from .functions.linear import linear_bgrad, linear_wgrad
-    want_b = bias_dtype is not None and ctx.needs_input_grad[ib]
-    dw = db = None
-    if ctx.needs_input_grad[iw]:
-        dw, db = linear_wgrad(dy2, x2, want_b)
-        dw = dw.to(weight_dtype)
-    elif want_b:
-        db = linear_bgrad(dy2)
-    return dw, (db.to(bias_dtype) if want_b else None)
-
-
-class _SwinLinearFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, aux, forms):
-        K = forms["w16"].shape[1]      # (weight.shape[1], or the padded width of a convolution weight's form: PatchEmbed)
-        x2 = _rows(x, K, "swin_linear")
-        aux2 = _rows(aux, weight.shape[0], "swin_linear (aux)") if aux is not None else None
-        out, _ = linear_kernel(x2, forms["w16"], forms["b32"], EPI_RESIDUAL if aux is not None else EPI_BIAS, aux2)
-        ctx.save_for_backward(x2)
-        ctx.forms = forms
-        ctx.meta = (x.shape, aux.shape if aux is not None else None, weight.dtype, bias.dtype if bias is not None else None, weight.shape)
-        return out.view(x.shape[:-1] + (weight.shape[0],))
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        x2, = ctx.saved_tensors
-        shape, aux_shape, wdt, bdt, wshape = ctx.meta
-        dy2 = _rows(dy, ctx.forms["w16"].shape[0], "swin_linear (gradient)")
-        dx = linear_kernel(dy2, ctx.forms["wt16"])[0].view(shape) if ctx.needs_input_grad[0] else None
-        dw, db = _wgrad(ctx, 1, 2, dy2, x2, wdt, bdt)
-        if dw is not None and dw.shape != wshape:      # the columns of padding are dropped
-            dw = dw[:, :wshape.numel() // wshape[0]].reshape(wshape)
-        return dx, dw, db, dy.reshape(aux_shape) if ctx.needs_input_grad[3] else None, None
-
-
-def swin_linear(x, weight, bias=None, epilogue=None, aux=None, cache=None):
-    """``x weight^T + bias`` (``epilogue=None``) or ``x weight^T + bias + aux`` (``epilogue="residual"``, the sum rounded once) on
-    ``msda_swin_linear_bf16``: x (..., K) bfloat16 on the device, weight (N, K), K and N multiples of 32 up to 8192 -> (..., N) bfloat16.
-    The input gradient is the same kernel on ``weight^T``; weight and bias gradients are ``functions.linear.linear_wgrad``'s, returned in
-    the parameters' dtypes.  ``cache``: a VersionCache that keeps the derived weight forms (:func:`linear_forms`) per parameter version.
-    The GELU epilogues belong to :func:`swin_mlp` (raw: :func:`linear_kernel`)."""
-    if epilogue not in (None, "residual") or (epilogue == "residual") != (aux is not None):
-        raise ValueError(f"swin_linear: epilogue None or 'residual' (with aux), got {epilogue!r}" + (" with aux" if aux is not None else ""))
-    return _SwinLinearFunction.apply(x, weight, bias, aux, _forms(cache, weight, bias))
-
-
-class _SwinLayerNormFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, weight, bias, eps):
-        x2 = _rows(x, weight.shape[0], "swin_layernorm")
-        g32 = _f32(weight)
-        need = any(ctx.needs_input_grad)
-        out, mean, rstd = layernorm_kernel(x2, g32, _f32(bias), eps, want_stats=need)
-        if need:
-            ctx.save_for_backward(x2, mean, rstd, g32)
-            ctx.meta = (x.shape, weight.dtype, bias.dtype)
-        return out.view(x.shape)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        x2, mean, rstd, g32 = ctx.saved_tensors
-        shape, wdt, bdt = ctx.meta
-        dx, dg, db = layernorm_backward_kernel(_rows(dy, x2.shape[1], "swin_layernorm (gradient)"), x2, mean, rstd, g32,
-                                               want_gamma=ctx.needs_input_grad[1], want_beta=ctx.needs_input_grad[2])
-        return (dx.view(shape) if ctx.needs_input_grad[0] else None, dg.to(wdt) if dg is not None else None,
-                db.to(bdt) if db is not None else None, None)
-
-
-def swin_layernorm(x, weight, bias, eps=1e-5):
-    """LayerNorm over the last dimension (C a multiple of 32 up to 4096) on ``msda_swin_layernorm_*``: x (..., C) bfloat16 on the device,
-    weight and bias (C) -> bfloat16.  Saves x and the fp32 statistics (nothing under ``no_grad``); gradients in the parameters' dtypes."""
-    return _SwinLayerNormFunction.apply(x, weight, bias, float(eps))
-
-
+# ---- the second half of a block ---------------------------------------------------------------------------------------------------------------
 class _SwinMlpFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, nw, nb, eps, w1, b1, w2, b2, f1, f2):
-        x2 = _rows(x, nw.shape[0], "swin_mlp")
-        g32 = _f32(nw)
+        x2 = bf16_rows(x, nw.shape[0], "swin_mlp")
+        g32 = f32(nw)
         need = any(ctx.needs_input_grad)
-        xn, mean, rstd = layernorm_kernel(x2, g32, _f32(nb), eps, want_stats=need)
-        h, u = linear_kernel(xn, f1["w16"], f1["b32"], EPI_GELU, want_out2=need)
-        out, _ = linear_kernel(h, f2["w16"], f2["b32"], EPI_RESIDUAL, x2)
-        if need:      # (the hidden activation h is not kept: the backward regenerates it from u)
+        xn, mean, rstd = layernorm_kernel(x2, g32, f32(nb), eps, want_stats=need)
+        out, u = gelu_mlp_forward(xn, f1, f2, need, EPI_RESIDUAL, x2)
+        if need:
             ctx.save_for_backward(x2, xn, mean, rstd, u, g32)
             ctx.forms = (f1, f2)
             ctx.meta = (x.shape,) + tuple(p.dtype if p is not None else None for p in (nw, nb, w1, b1, w2, b2))
@@ -330,44 +168,25 @@ class _SwinMlpFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
         x2, xn, mean, rstd, u, g32 = ctx.saved_tensors
-        (f1, f2), (shape, nwdt, nbdt, w1dt, b1dt, w2dt, b2dt) = ctx.forms, ctx.meta
-        d2 = _rows(dout, x2.shape[1], "swin_mlp (gradient)")
-        du, h = linear_kernel(d2, f2["wt16"], None, EPI_GELU_BACKWARD, u, want_out2=ctx.needs_input_grad[6])
-        dw2, db2 = _wgrad(ctx, 6, 7, d2, h, w2dt, b2dt)
-        dw1, db1 = _wgrad(ctx, 4, 5, du, xn, w1dt, b1dt)
-        dxn, _ = linear_kernel(du, f1["wt16"])
+        (f1, f2), (shape, nwdt, nbdt, *dtypes) = ctx.forms, ctx.meta
+        d2 = bf16_rows(dout, x2.shape[1], "swin_mlp (gradient)")      # (4, 5, 6, 7): w1, b1, w2, b2 among forward's arguments
+        dxn, dw1, db1, dw2, db2 = gelu_mlp_backward(ctx, (4, 5, 6, 7), dtypes, d2, xn, u, f1, f2)
         dx, dg, db = layernorm_backward_kernel(dxn, x2, mean, rstd, g32, add=d2, want_gamma=ctx.needs_input_grad[1],
                                                want_beta=ctx.needs_input_grad[2])
-        return (dx.view(shape) if ctx.needs_input_grad[0] else None, dg.to(nwdt) if dg is not None else None,
-                db.to(nbdt) if db is not None else None, None, dw1, db1, dw2, db2, None, None)
+        return dx.view(shape) if ctx.needs_input_grad[0] else None, cast(dg, nwdt), cast(db, nbdt), None, dw1, db1, dw2, db2, None, None
 
 
 def swin_mlp(x, norm, fc1, fc2, caches=(None, None)):
     """``x + fc2(GELU(fc1(norm(x))))`` as ONE autograd function: x (..., C) bfloat16 on the device, ``norm`` an ``nn.LayerNorm(C)``, ``fc1``
-    / ``fc2`` ``nn.Linear`` layers (C -> hidden -> C).  Forward: LayerNorm; fc1 with the GELU epilogue (the pre-activation u and
-    h = GELU(u)); fc2 with the residual epilogue.  Saved for the backward: x, norm(x), the statistics and u -- not h, which the backward
-    regenerates in the epilogue that forms du = (dout W2) gelu'(u); under ``no_grad`` neither u nor the statistics are written."""
-    if not isinstance(norm, nn.LayerNorm) or not norm.elementwise_affine or norm.bias is None:
-        raise RuntimeError("swin_mlp: norm must be an nn.LayerNorm with weight and bias")
+    / ``fc2`` ``nn.Linear`` layers (C -> hidden -> C).  Forward: LayerNorm, then ``backbone_ops.gelu_mlp_forward`` with fc2's residual
+    epilogue.  Saved for the backward: x, norm(x), the statistics and the pre-activation u -- not h = GELU(u) (the policy of
+    ``backbone_ops``); under ``no_grad`` neither u nor the statistics are written."""
+    need_layernorm(norm, "swin", "swin_mlp")
     return _SwinMlpFunction.apply(x, norm.weight, norm.bias, float(norm.eps), fc1.weight, fc1.bias, fc2.weight, fc2.bias,
-                                  _forms(caches[0], fc1.weight, fc1.bias), _forms(caches[1], fc2.weight, fc2.bias))
+                                  cached_forms(caches[0], fc1.weight, fc1.bias), cached_forms(caches[1], fc2.weight, fc2.bias))
 
 
-# ---- the stage boundaries: merging norm, output norm to NCHW, patch rows --------------------------------------------------------------------
-def _tokens(x, H, W, what):
-    if not x.is_cuda:
-        raise RuntimeError("Not implemented on the CPU")
-    if x.dtype != BF16 or x.dim() != 3 or x.shape[1] != H * W:
-        raise RuntimeError(f"{what}: bfloat16 (B, {H} * {W}, C), got {x.dtype} {tuple(x.shape)}")
-    return x.contiguous()
-
-
-def _affine(weight, bias, width, what):
-    if weight is None or bias is None or tuple(weight.shape) != (width,) or tuple(bias.shape) != (width,):
-        raise RuntimeError(f"{what}: weight and bias ({width})")
-    return _f32(weight), _f32(bias)
-
-
+# ---- the merging norm ---------------------------------------------------------------------------------------------------------------------
 def merge_norm_kernel(x, H, W, g32, b32, eps, want_stats=True):
     """``msda_swin_merge_norm_forward_bf16``: x (B, H * W, C) bf16 contiguous -> (out (B, H2 * W2, 4 C), mean, rstd)"""
     B, _, C = x.shape
@@ -377,7 +196,7 @@ def merge_norm_kernel(x, H, W, g32, b32, eps, want_stats=True):
     rstd = torch.empty_like(mean) if want_stats else None
     with _lib.on_device(x.device):
         _lib.check(_lib.load().msda_swin_merge_norm_forward_bf16(x.data_ptr(), g32.data_ptr(), b32.data_ptr(), eps, B, H, W, C, out.data_ptr(),
-                                                                 _ptr(mean), _ptr(rstd), _lib.raw_stream(x.device)))
+                                                                 ptr(mean), ptr(rstd), _lib.raw_stream(x.device)))
     return out, mean, rstd
 
 
@@ -385,61 +204,18 @@ def merge_norm_backward_kernel(dy, x, H, W, mean, rstd, g32, want_gamma=True, wa
     """``msda_swin_merge_norm_backward_bf16``: dy (B, H2 * W2, 4 C), x (B, H * W, C) -> (dx as x, dgamma, dbeta (4 C) float32 or None)"""
     B, _, C = x.shape
     dx = torch.empty_like(x)
-    dg = torch.empty(4 * C, dtype=torch.float32, device=x.device) if want_gamma else None
-    db = torch.empty(4 * C, dtype=torch.float32, device=x.device) if want_beta else None
-    ws = None
-    if want_gamma or want_beta:
-        ws = torch.empty(layernorm_workspace_bytes(mean.numel(), 4 * C) // 4, dtype=torch.float32, device=x.device)
+    dg, db, ws = column_sums(want_gamma, want_beta, mean.numel(), 4 * C, x.device)
     with _lib.on_device(x.device):
         _lib.check(_lib.load().msda_swin_merge_norm_backward_bf16(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
-                                                                  B, H, W, C, dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(ws),
+                                                                  B, H, W, C, dx.data_ptr(), ptr(dg), ptr(db), ptr(ws),
                                                                   _lib.raw_stream(x.device)))
     return dx, dg, db
-
-
-def norm_nchw_kernel(x, g32, b32, eps, want_stats=True):
-    """``msda_swin_norm_nchw_forward_bf16``: x (B, HW, C) bf16 contiguous -> (out (B, C, HW), mean, rstd)"""
-    B, HW, C = x.shape
-    out = torch.empty((B, C, HW), dtype=BF16, device=x.device)
-    mean = torch.empty(B * HW, dtype=torch.float32, device=x.device) if want_stats else None
-    rstd = torch.empty_like(mean) if want_stats else None
-    with _lib.on_device(x.device):
-        _lib.check(_lib.load().msda_swin_norm_nchw_forward_bf16(x.data_ptr(), g32.data_ptr(), b32.data_ptr(), eps, B, HW, C, out.data_ptr(),
-                                                                _ptr(mean), _ptr(rstd), _lib.raw_stream(x.device)))
-    return out, mean, rstd
-
-
-def norm_nchw_backward_kernel(dy, x, mean, rstd, g32, want_gamma=True, want_beta=True):
-    """``msda_swin_norm_nchw_backward_bf16``: dy (B, C, HW), x (B, HW, C) -> (dx as x, dgamma, dbeta (C) float32 or None)"""
-    B, HW, C = x.shape
-    dx = torch.empty_like(x)
-    dg = torch.empty(C, dtype=torch.float32, device=x.device) if want_gamma else None
-    db = torch.empty(C, dtype=torch.float32, device=x.device) if want_beta else None
-    ws = torch.empty(layernorm_workspace_bytes(B * HW, C) // 4, dtype=torch.float32, device=x.device) if want_gamma or want_beta else None
-    with _lib.on_device(x.device):
-        _lib.check(_lib.load().msda_swin_norm_nchw_backward_bf16(dy.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
-                                                                 B, HW, C, dx.data_ptr(), _ptr(dg), _ptr(db), _ptr(ws),
-                                                                 _lib.raw_stream(x.device)))
-    return dx, dg, db
-
-
-def patch_grid(H, W, patch_size):
-    """-> (Wh, Ww) = (ceil(H / ph), ceil(W / pw))"""
-    ph, pw = _pair(patch_size)
-    return -(-H // ph), -(-W // pw)
-
-
-def patch_width(in_chans, patch_size):
-    """Kp: in_chans ph pw rounded up to a multiple of 32"""
-    ph, pw = _pair(patch_size)
-    return -(-in_chans * ph * pw // 32) * 32
 
 
 class _SwinMergeNormFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, H, W, weight, bias, eps):
-        x = _tokens(x, H, W, "swin_merge_norm")
-        g32, b32 = _affine(weight, bias, 4 * x.shape[2], "swin_merge_norm")
+        x, g32, b32 = token_norm_operands(x, H, W, weight, bias, 4, "swin_merge_norm")
         need = any(ctx.needs_input_grad)
         out, mean, rstd = merge_norm_kernel(x, H, W, g32, b32, eps, want_stats=need)
         if need:
@@ -454,8 +230,7 @@ class _SwinMergeNormFunction(torch.autograd.Function):
         H, W, wdt, bdt = ctx.meta
         dx, dg, db = merge_norm_backward_kernel(dy.contiguous(), x, H, W, mean, rstd, g32, want_gamma=ctx.needs_input_grad[3],
                                                 want_beta=ctx.needs_input_grad[4])
-        return (dx if ctx.needs_input_grad[0] else None, None, None, dg.to(wdt) if dg is not None else None,
-                db.to(bdt) if db is not None else None, None)
+        return dx if ctx.needs_input_grad[0] else None, None, None, cast(dg, wdt), cast(db, bdt), None
 
 
 def swin_merge_norm(x, H, W, weight, bias, eps=1e-5):
@@ -466,101 +241,10 @@ def swin_merge_norm(x, H, W, weight, bias, eps=1e-5):
     return _SwinMergeNormFunction.apply(x, int(H), int(W), weight, bias, float(eps))
 
 
-class _SwinNormNchwFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, H, W, weight, bias, eps):
-        x = _tokens(x, H, W, "swin_norm_nchw")
-        g32, b32 = _affine(weight, bias, x.shape[2], "swin_norm_nchw")
-        need = any(ctx.needs_input_grad)
-        out, mean, rstd = norm_nchw_kernel(x, g32, b32, eps, want_stats=need)
-        if need:
-            ctx.save_for_backward(x, mean, rstd, g32)
-            ctx.meta = (weight.dtype, bias.dtype)
-        return out.view(x.shape[0], x.shape[2], H, W)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        x, mean, rstd, g32 = ctx.saved_tensors
-        wdt, bdt = ctx.meta
-        dx, dg, db = norm_nchw_backward_kernel(dy.contiguous(), x, mean, rstd, g32, want_gamma=ctx.needs_input_grad[3],
-                                               want_beta=ctx.needs_input_grad[4])
-        return (dx if ctx.needs_input_grad[0] else None, None, None, dg.to(wdt) if dg is not None else None,
-                db.to(bdt) if db is not None else None, None)
-
-
-def swin_norm_nchw(x, H, W, weight, bias, eps=1e-5):
-    """An output norm of the backbone on ``msda_swin_norm_nchw_*``: x (B, H * W, C) bfloat16 on the device, C a multiple of 32 up to 4096,
-    weight and bias (C) -> (B, C, H, W) bfloat16 contiguous: LayerNorm over C, stored transposed (any H * W).  Saves x and the fp32
-    statistics (nothing under ``no_grad``); gradients in the parameters' dtypes."""
-    return _SwinNormNchwFunction.apply(x, int(H), int(W), weight, bias, float(eps))
-
-
-class _SwinPatchRowsFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, img, ph, pw):
-        if not img.is_cuda:
-            raise RuntimeError("Not implemented on the CPU")
-        if img.dtype != BF16 or img.dim() != 4:
-            raise RuntimeError(f"swin_patch_rows: bfloat16 (B, Cin, H, W), got {img.dtype} {tuple(img.shape)}")
-        img = img.contiguous()
-        B, Cin, H, W = img.shape
-        Wh, Ww = patch_grid(H, W, (ph, pw))
-        rows = torch.empty((B, Wh * Ww, patch_width(Cin, (ph, pw))), dtype=BF16, device=img.device)
-        with _lib.on_device(img.device):
-            _lib.check(_lib.load().msda_swin_patch_rows_bf16(img.data_ptr(), B, Cin, H, W, ph, pw, rows.data_ptr(), _lib.raw_stream(img.device)))
-        ctx.meta = (tuple(img.shape), ph, pw)
-        return rows
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, drows):
-        (B, Cin, H, W), ph, pw = ctx.meta
-        drows = drows.contiguous()
-        dimg = torch.empty((B, Cin, H, W), dtype=BF16, device=drows.device)
-        with _lib.on_device(drows.device):
-            _lib.check(_lib.load().msda_swin_patch_rows_backward_bf16(drows.data_ptr(), B, Cin, H, W, ph, pw, dimg.data_ptr(),
-                                                                      _lib.raw_stream(drows.device)))
-        return dimg, None, None
-
-
-def swin_patch_rows(img, patch_size):
-    """The image as rows of patches on ``msda_swin_patch_rows_*``: img (B, Cin, H, W) bfloat16 on the device -> (B, Wh * Ww, Kp) bfloat16,
-    Wh = ceil(H / ph), Ww = ceil(W / pw), Kp = Cin ph pw rounded up to a multiple of 32 (at most 8192); column (c ph + dy) pw + dx is the
-    image element (the order of ``proj.weight.flatten(1)``), columns of padding and pixels past the image are exact zeros.  Saves nothing;
-    the backward (run only when the image needs a gradient) is the inverse movement."""
-    ph, pw = _pair(patch_size)
-    return _SwinPatchRowsFunction.apply(img, int(ph), int(pw))
-
-
-def _need_layernorm(norm, what):
-    if not isinstance(norm, nn.LayerNorm) or not norm.elementwise_affine or norm.bias is None:
-        raise NotImplementedError(f"richsem_amd.swin: the fused {what} needs an nn.LayerNorm with weight and bias, got {type(norm).__name__}")
-
-
 # ---- the mirrors ------------------------------------------------------------------------------------------------------------------------
-def _pair(v):
-    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-
-
 def _refuse(name, value):
     if value:
         raise NotImplementedError(f"richsem_amd.swin: {name}={value!r} is not supported (only {name}=0 / False)")
-
-
-class DropPath(nn.Module):
-    """per-sample stochastic depth on the residual branch (timm's DropPath, which the reference imports)"""
-
-    def __init__(self, drop_prob=0.):
-        super().__init__()
-        self.drop_prob = float(drop_prob)
-
-    def forward(self, x):
-        if self.drop_prob == 0. or not self.training:
-            return x
-        keep = 1. - self.drop_prob
-        mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep)
-        return x / keep * mask
 
 
 class Mlp(nn.Module):
@@ -586,7 +270,7 @@ class WindowAttention(nn.Module):
         _refuse("attn_drop", attn_drop)
         _refuse("drop", proj_drop)
         self.dim = dim
-        self.window_size = _pair(window_size)
+        self.window_size = pair(window_size)
         if self.window_size[0] != self.window_size[1]:
             raise NotImplementedError("richsem_amd.swin: square windows only")
         self.num_heads = num_heads
@@ -610,7 +294,7 @@ class WindowAttention(nn.Module):
 
     def forward(self, x, shift=0):
         qkv = self.qkv(x)
-        if x.is_cuda and x.dtype == torch.bfloat16:
+        if on_kernels(x):
             attn = self.attend(qkv, shift)
         else:
             attn = window_attention_torch(qkv, self.relative_position_bias_table, self.num_heads, self.window_size[0], shift, self.scale)
@@ -638,7 +322,7 @@ class SwinTransformerBlock(nn.Module):
         self.mlp_ratio = mlp_ratio
         assert 0 <= self.shift_size < self.window_size, "shift_size must in 0-window_size"
         self.norm1 = norm_layer(dim)
-        self.attn = WindowAttention(dim, window_size=_pair(window_size), num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale,
+        self.attn = WindowAttention(dim, window_size=pair(window_size), num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale,
                                     attn_drop=attn_drop, proj_drop=drop)
         self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
         self.norm2 = norm_layer(dim)
@@ -650,11 +334,9 @@ class SwinTransformerBlock(nn.Module):
     def _forward_fused(self, x):
         B, L, C = x.shape
         H, W, w = self.H, self.W, self.window_size
-        if isinstance(self.drop_path, DropPath) and self.drop_path.drop_prob > 0. and self.training:
-            raise NotImplementedError("richsem_amd.swin: fused blocks do not implement stochastic depth in training mode (drop_path_rate=0.)")
-        act = self.mlp.act
-        if not isinstance(self.norm1, nn.LayerNorm) or not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
-            raise NotImplementedError("richsem_amd.swin: fused blocks need nn.LayerNorm and the erf form of nn.GELU")
+        refuse_drop_path_in_training(self, "swin")
+        need_layernorm(self.norm1, "swin", "block")
+        need_erf_gelu(self.mlp.act, "swin")
         attn, shortcut = self.attn, x.contiguous()
         x = swin_layernorm(shortcut, self.norm1.weight, self.norm1.bias, self.norm1.eps).view(B, H, W, C)
         pad_r, pad_b = (w - W % w) % w, (w - H % w) % w
@@ -672,7 +354,7 @@ class SwinTransformerBlock(nn.Module):
         B, L, C = x.shape
         H, W, w = self.H, self.W, self.window_size
         assert L == H * W, "input feature has wrong size"
-        if self.fused and x.is_cuda and x.dtype == torch.bfloat16:
+        if self.fused and on_kernels(x):
             return self._forward_fused(x)
         shortcut = x
         x = self.norm1(x).view(B, H, W, C)
@@ -703,8 +385,8 @@ class PatchMerging(nn.Module):
     def forward(self, x, H, W):
         B, L, C = x.shape
         assert L == H * W, "input feature has wrong size"
-        if self.fused and x.is_cuda and x.dtype == torch.bfloat16:
-            _need_layernorm(self.norm, "PatchMerging")
+        if self.fused and on_kernels(x):
+            need_layernorm(self.norm, "swin", "PatchMerging")
             xn = swin_merge_norm(x, H, W, self.norm.weight, self.norm.bias, self.norm.eps)
             return swin_linear(xn, self.reduction.weight, None, cache=self._forms)
         x = x.view(B, H, W, C)
@@ -761,59 +443,35 @@ class PatchEmbed(nn.Module):
 
     def __init__(self, patch_size=4, in_chans=3, embed_dim=96, norm_layer=None):
         super().__init__()
-        self.patch_size = _pair(patch_size)
+        self.patch_size = pair(patch_size)
         self.in_chans = in_chans
         self.embed_dim = embed_dim
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=self.patch_size, stride=self.patch_size)
         self.norm = norm_layer(embed_dim) if norm_layer is not None else None
         self._forms = VersionCache()      # the zero-padded (embed_dim, Kp) weight forms of the fused path
 
-    def _padded_forms(self):
-        w, b = self.proj.weight, self.proj.bias
-
-        def build():
-            flat = w.detach().to(BF16).flatten(1)
-            return linear_forms(F.pad(flat, (0, patch_width(self.in_chans, self.patch_size) - flat.shape[1])), b)
-        return self._forms.get([w] + ([b] if b is not None else []), build)
-
-    def _fused_path(self, x):
-        return self.fused and x.is_cuda and x.dtype == torch.bfloat16
-
     def tokens(self, x):
         """x (B, in_chans, H, W) -> (tokens (B, Wh * Ww, embed_dim), Wh, Ww): projection and norm, without the NCHW detour"""
-        if self._fused_path(x):
+        if self.fused and on_kernels(x):
             if self.norm is not None:
-                _need_layernorm(self.norm, "PatchEmbed")
+                need_layernorm(self.norm, "swin", "PatchEmbed")
             Wh, Ww = patch_grid(x.shape[2], x.shape[3], self.patch_size)
-            t = _SwinLinearFunction.apply(swin_patch_rows(x, self.patch_size), self.proj.weight, self.proj.bias, None, self._padded_forms())
+            t = patch_linear(swin_patch_rows(x, self.patch_size), self.proj.weight, self.proj.bias, self._forms)
             if self.norm is not None:
                 t = swin_layernorm(t, self.norm.weight, self.norm.bias, self.norm.eps)
             return t, Wh, Ww
-        x = self._project(x)
-        Wh, Ww = x.shape[2], x.shape[3]
-        x = x.flatten(2).transpose(1, 2)
-        return (self.norm(x) if self.norm is not None else x), Wh, Ww
-
-    def _project(self, x):
-        _, _, H, W = x.shape
-        ph, pw = self.patch_size
-        if W % pw or H % ph:
-            x = F.pad(x, (0, (pw - W % pw) % pw, 0, (ph - H % ph) % ph))
-        return self.proj(x)
-
-    def forward(self, x):
-        if self._fused_path(x):
-            t, Wh, Ww = self.tokens(x)
-            return t.transpose(1, 2).reshape(-1, self.embed_dim, Wh, Ww)
         _, _, H, W = x.shape
         ph, pw = self.patch_size
         if W % pw or H % ph:
             x = F.pad(x, (0, (pw - W % pw) % pw, 0, (ph - H % ph) % ph))
         x = self.proj(x)
-        if self.norm is not None:
-            Wh, Ww = x.shape[2], x.shape[3]
-            x = self.norm(x.flatten(2).transpose(1, 2)).transpose(1, 2).reshape(-1, self.embed_dim, Wh, Ww)
-        return x
+        Wh, Ww = x.shape[2], x.shape[3]
+        x = x.flatten(2).transpose(1, 2)
+        return (self.norm(x) if self.norm is not None else x), Wh, Ww
+
+    def forward(self, x):
+        t, Wh, Ww = self.tokens(x)
+        return t.transpose(1, 2).reshape(-1, self.embed_dim, Wh, Ww)
 
 
 class SwinTransformer(nn.Module):
@@ -843,7 +501,7 @@ class SwinTransformer(nn.Module):
         self.patch_embed = PatchEmbed(patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim,
                                       norm_layer=norm_layer if patch_norm else None)
         if ape:
-            size, patch = _pair(pretrain_img_size), _pair(patch_size)
+            size, patch = pair(pretrain_img_size), pair(patch_size)
             self.absolute_pos_embed = nn.Parameter(torch.zeros(1, embed_dim, size[0] // patch[0], size[1] // patch[1]))
             nn.init.trunc_normal_(self.absolute_pos_embed, std=.02)
         dpr = [v.item() for v in torch.linspace(0, drop_path_rate, sum(depths))]
@@ -908,19 +566,11 @@ class SwinTransformer(nn.Module):
         for i, layer in enumerate(self.layers):
             x_out, H, W, x, Wh, Ww = layer(x, Wh, Ww)
             if i in self.out_indices:
-                norm = getattr(self, f"norm{i}")
-                if self.fused_stages and x_out.is_cuda and x_out.dtype == torch.bfloat16:
-                    _need_layernorm(norm, "output norm")
-                    outs.append(swin_norm_nchw(x_out, H, W, norm.weight, norm.bias, norm.eps))
-                    continue
-                x_out = norm(x_out)
-                outs.append(x_out.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2).contiguous())
+                outs.append(output_norm_nchw(getattr(self, f"norm{i}"), x_out, H, W, self.fused_stages, "swin"))
         return tuple(outs)
 
     def forward(self, images, mask):
-        assert mask is not None
-        outs = self.forward_raw(images)
-        return [(o, F.interpolate(mask[None].float(), size=o.shape[-2:]).to(torch.bool)[0]) for o in outs]
+        return mask_pyramid(self.forward_raw(images), mask)
 
     def train(self, mode=True):
         super().train(mode)

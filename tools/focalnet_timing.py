@@ -94,11 +94,11 @@ def backbone_rows(model, B, dev):
                 p.fill_(1.)
     img = torch.randn(B, 3, *IMAGE, device=dev).to(BF).requires_grad_(True)
     params = list(net.parameters())
-    rule = focalnet._on_kernels
+    rule = focalnet.on_kernels
 
     def fb(on, fused=False):
         def run():
-            focalnet._on_kernels = rule if on else (lambda x: False)
+            focalnet.on_kernels = rule if on else (lambda x: False)
             net.set_fused(fused)
             try:
                 img.grad = None
@@ -106,7 +106,7 @@ def backbone_rows(model, B, dev):
                     p.grad = None
                 sum(o.float().sum() for o in net.forward_features(img)).backward()
             finally:
-                focalnet._on_kernels = rule
+                focalnet.on_kernels = rule
         return run
     return {"backbone forward + backward": {"fused off": fb(True), "fused on": fb(True, True), "torch composition": fb(False)}}
 
