@@ -950,6 +950,39 @@ int msda_mask_postprocess_f32(const float *pred, int N, int Q, int h, int w, con
 int msda_mask_postprocess_bf16(const uint16_t *pred, int N, int Q, int h, int w, const int64_t *const *item_indices, const int *rows,
                                const int *sizes, float threshold, uint8_t *const *out, msda_stream_t stream);
 
+/* ---- the CondInst dynamic mask head (csrc/dynamic_masks.hip; reference MaskBranch.dynamic_mask_with_coords, models/richsem/cond_inst.py:
+ * 337-435, with compute_locations, parse_dynamic_params and aligned_bilinear of the same file) ----------------------------------------------
+ * feat (N, C, H, W), params (N, Q, P) and out (N, R, F H, F W) fp32 / bf16, read and written as stored;  ref (N, Q, 2) fp32 the normalised
+ * reference point (x, y);  sizes (N, 2) fp32 the image size (h, w);  inst (N, R) int32 ON THE DEVICE: the query of output row r, a value
+ * outside [0, Q) = no query.  C = 8 or 16, hidden width 8, F = `factor` = 2 (mask_out_stride 4) or 1 (mask_out_stride 8).  Per image n, row r
+ * with query q and stride-8 pixel (y, x):
+ *   in = [ref_x size_w - (8 x + 4), ref_y size_h - (8 y + 4), feat[n, :, y, x]]  (rel_coord = 0: the features alone; ref, sizes may be NULL)
+ *   t  = w2 . relu(W1 relu(W0 in + b0) + b1) + b2,  a parameter row = W0 (8, Cin) row-major, W1 (8, 8), w2 (8), b0 (8), b1 (8), b2 (1),
+ *        P = 8 Cin + 89 (169 / 233 with the coordinates)
+ *   out[n, r] = aligned_bilinear(t, F): per axis F[0] = T[0], F[2 k + 1] = T[k], F[2 k] = (T[k - 1] + T[k]) / 2; a row without a query is zeros.
+ * msda_dynmask_table: fills inst from `rows` (N, R) int64 (a value outside [0, Q): -1), else from offsets (N + 1) / query_of_target (cap), the
+ *   operands of msda_mask_loss_* (R = Q; inst[n, q] = q where image n has a pair for q, else -1), else -- all three NULL -- the identity.
+ * msda_dynmask_backward_*: grad_out (N, R, F H, F W) -> grad_params (N, Q, P) (every element written once; zeros for a query no row names;
+ *   rows naming one query are added in ascending order), grad_feat (N, C, H, W), and, when non-NULL, grad_ref (N, Q, 2) fp32, the gradient for
+ *   the normalised point.  The chain is recomputed; per-tile partial sums in `workspace`, added in ascending order.
+ * Limits: N, H, W, Q, R >= 1, C in {8, 16}, factor in {1, 2}, rel_coord in {0, 1}, R = Q for the tables without `rows` (MSDA_ERR_BAD_DIMS);
+ * N <= 65535, H, W <= 2^14, R <= 2^20, N R 4 H W < 2^40 (MSDA_ERR_TOO_LARGE); workspace 16-byte aligned, out `factor` elements, the others their
+ * element (MSDA_ERR_MISALIGNED).  Every check comes before any launch; no call allocates, synchronises or uses atomics; two calls give the
+ * same bits. */
+int msda_dynmask_workspace_bytes(int N, int C, int H, int W, int Q, int R, int64_t *bytes);
+int msda_dynmask_table(const int64_t *rows, const int64_t *offsets, const int64_t *query_of_target, int N, int R, int Q, int64_t cap, int *inst,
+                       msda_stream_t stream);
+int msda_dynmask_forward_f32(const float *feat, const float *params, const float *ref, const float *sizes, const int *inst, int N, int C, int H,
+                             int W, int Q, int R, int rel_coord, int factor, float *out, msda_stream_t stream);
+int msda_dynmask_forward_bf16(const uint16_t *feat, const uint16_t *params, const float *ref, const float *sizes, const int *inst, int N, int C,
+                              int H, int W, int Q, int R, int rel_coord, int factor, uint16_t *out, msda_stream_t stream);
+int msda_dynmask_backward_f32(const float *grad_out, const float *feat, const float *params, const float *ref, const float *sizes, const int *inst,
+                              int N, int C, int H, int W, int Q, int R, int rel_coord, int factor, float *grad_params, float *grad_feat,
+                              float *grad_ref, void *workspace, msda_stream_t stream);
+int msda_dynmask_backward_bf16(const uint16_t *grad_out, const uint16_t *feat, const uint16_t *params, const float *ref, const float *sizes,
+                               const int *inst, int N, int C, int H, int W, int Q, int R, int rel_coord, int factor, uint16_t *grad_params,
+                               uint16_t *grad_feat, float *grad_ref, void *workspace, msda_stream_t stream);
+
 /* ---- attention core of CLIP's AttentionPool2d for its single query token (reference
  * clip/model.py:58-91, called at models/richsem/richsem.py:753 on the ROIAlign output) -----------------------------------
  * With one query per head the key / value projections move to the other side of the attention (csrc/msda_attnpool.h): the caller

@@ -36,6 +36,9 @@ def __getattr__(name):      # PostProcess is exported from the package without i
     if name in ("MaskTargets", "mask_losses", "mask_losses_torch", "mask_losses_and_grads", "PostProcessSegm"):      # the criterion's mask terms and the mask post-processor (masks.py)
         from . import masks
         return getattr(masks, name)
+    if name in ("dynamic_masks", "dynamic_masks_torch", "dynamic_masks_and_grads", "MaskBranch", "MaskHeadSmallConv"):      # the CondInst dynamic mask head (cond_inst.py)
+        from . import cond_inst
+        return getattr(cond_inst, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

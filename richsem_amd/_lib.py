@@ -93,6 +93,7 @@ SYMBOLS = [
     "msda_dwconv7_bf16", "msda_dwconv7_workspace_bytes", "msda_dwconv7_wgrad_bf16", "msda_layer_scale_forward_bf16", "msda_layer_scale_backward_bf16",
     "msda_fmod_workspace_bytes", "msda_fmod_context_forward_bf16", "msda_fmod_context_backward_bf16", "msda_fmod_modulate_forward_bf16", "msda_fmod_modulate_backward_bf16",
     "msda_mask_loss_workspace_bytes", "msda_mask_loss_forward_f32", "msda_mask_loss_forward_bf16", "msda_mask_loss_backward_f32", "msda_mask_loss_backward_bf16", "msda_mask_postprocess_f32", "msda_mask_postprocess_bf16",
+    "msda_dynmask_workspace_bytes", "msda_dynmask_table", "msda_dynmask_forward_f32", "msda_dynmask_forward_bf16", "msda_dynmask_backward_f32", "msda_dynmask_backward_bf16",
     "msda_conv_set_tiling", "msda_conv_set_ring", "msda_conv_dgrad_fused_bf16", "msda_conv_packed_elems", "msda_conv_pack_weight", "msda_conv_forward_bf16", "msda_conv_dgrad_bf16", "msda_conv_forward_workspace_bytes", "msda_conv_forward_ws_bf16", "msda_conv_dgrad_workspace_bytes", "msda_conv_dgrad_ws_bf16", "msda_pool_nhwc_bf16", "msda_groupnorm8_nhwc_bf16", "msda_groupnorm8_backward_nhwc_bf16", "msda_conv_wgrad_workspace_bytes", "msda_conv_wgrad_bf16", "msda_conv_set_wgrad_ring", "msda_conv_wgrad_group_workspace_bytes", "msda_conv_wgrad_group_bf16",
     "msda_optim_plan", "msda_optim_sumsq", "msda_optim_step", "msda_optim_ema",
     "msda_repack_plan", "msda_repack",
@@ -303,6 +304,17 @@ def load():
         f.restype = ci
         f = getattr(L, "msda_mask_postprocess_" + sfx)
         f.argtypes = [vp] + [ci] * 4 + [vp, vp, vp, ctypes.c_float, vp, vp]
+        f.restype = ci
+    L.msda_dynmask_workspace_bytes.argtypes = [ci] * 6 + [ctypes.POINTER(i64)]
+    L.msda_dynmask_workspace_bytes.restype = ci
+    L.msda_dynmask_table.argtypes = [vp, vp, vp, ci, ci, ci, i64, vp, vp]
+    L.msda_dynmask_table.restype = ci
+    for sfx in ("f32", "bf16"):
+        f = getattr(L, "msda_dynmask_forward_" + sfx)
+        f.argtypes = [vp] * 5 + [ci] * 8 + [vp, vp]
+        f.restype = ci
+        f = getattr(L, "msda_dynmask_backward_" + sfx)
+        f.argtypes = [vp] * 6 + [ci] * 8 + [vp] * 5
         f.restype = ci
     L.msda_conv_pack_weight.argtypes = [vp, ci, ci, ci, ci, vp, vp]
     L.msda_conv_pack_weight.restype = ci
